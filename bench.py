@@ -11,7 +11,17 @@ pack weights -> forward -> Lovasz hinge -> backward (bucketed RCCL all-reduce on
 W untimed warm-up steps, then EXACTLY K timed steps bracketed by barrier + torch.cuda.synchronize(), MAX over ranks.
 Rank 0 prints ONE JSON line.  Inputs are resident in HBM before the timed region (no PCIe inside it).
 
-Extra objects in the line:
+A plain run does only that: set up, warm up, time the K steps, write the outputs (--dump-outputs DIR) and print the line
+(`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step` = milliseconds of one timed step).  Everything else - the
+median-step leg, the per-operator roofline, the fit_e2e leg, the other BASELINE configurations, the data-parallel leg and the CPU
+baseline - runs only with --full (--no-cpu-baseline / --no-iou / --no-configs leave legs of a --full run out).
+
+--dump-outputs DIR: after the timed steps (before anything else runs on the model), rank 0 writes what the last timed step handed its
+caller, float32 / float64 .npy: loss.npy (the step's loss), logits.npy (its forward's fp32 logits), params_sample.npy (a fixed,
+seeded sample of the updated state_dict) and param_norms.npy (the L2 norm of every floating state_dict entry, in key order).
+The inputs and the initial weights are seeded, so two builds run with the same arguments can be compared output for output.
+
+Extra objects in the line (--full):
   roofline     the kernel that takes the most time in a step, measured live with HIP event pairs on the launch stream
                (salt_program_run_timed): achieved = algorithmic FLOPs of its launches / their summed duration.
   cpu_baseline the oracle (plain-PyTorch CPU restatement, kind "port") timed on this box's host cores on a bounded sample.
@@ -36,7 +46,7 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
-MFMA_PEAK_TFLOPS = {'bf16': 2500.0, 'f32': 157.3}      # dense peaks, /opt/skills/guides/MI355X_MICROARCH.md
+MFMA_PEAK_TFLOPS = {'bf16': 2500.0, 'f32': 157.3}      # dense peaks, MI355X_MICROARCH.md
 HBM_PEAK_GBS = 8000.0
 
 
@@ -428,8 +438,9 @@ RANK_MS = []
 STEP_MS = []
 
 
-def train_config(workload, dtype, B, loss, steps, warmup, dev, rank=0, world=1, reps=1):
-    """Build the model of one training configuration, run `warmup` + `steps` timed fused steps on resident data; -> (model, batches, s)."""
+def train_config(workload, dtype, B, loss, steps, warmup, dev, rank=0, world=1, reps=1, median=True):
+    """Build the model of one training configuration, run `warmup` + `steps` timed fused steps on resident data; -> (model, batches, s).
+    median=False leaves out the median-step leg behind the timed region (main() runs it after --dump-outputs, with --full only)."""
     from salt_amd.models import SegmentationModel
     arch_name, channels, _ = WORKLOADS[workload]
     arch = {'model_params': {'architecture': arch_name, 'out_channels': 2, 'activation': 'sigmoid', 'loss': loss, 'compute_dtype': dtype},
@@ -464,18 +475,9 @@ def train_config(workload, dtype, B, loss, steps, warmup, dev, rank=0, world=1, 
     elapsed = time.perf_counter() - t0
     global RANK_MS, STEP_MS
     RANK_MS = [1e3 * elapsed / steps]
-    # SURVEY 8d asks for the MEDIAN step: a second leg behind the contract's timed region, one event per step on the compute stream
-    # (rank 0's own steps; >= 50 of them), reported beside the mean of the K timed steps
-    n_med = max(50, steps)
-    evs = [torch.cuda.Event(enable_timing=True) for _ in range(n_med + 1)]
-    evs[0].record()
-    for i in range(n_med):
-        model._fit_loop(list(batches[(warmup + steps + i) % pool_batches]))
-        evs[i + 1].record()
-    torch.cuda.synchronize()
-    if world > 1:
-        dist.barrier()
-    STEP_MS = sorted(evs[i].elapsed_time(evs[i + 1]) for i in range(n_med))
+    STEP_MS = []
+    if median:
+        median_leg(model, batches, warmup + steps, max(50, steps), world)
     if world > 1:
         te = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         every = [torch.zeros_like(te) for _ in range(world)]
@@ -484,6 +486,52 @@ def train_config(workload, dtype, B, loss, steps, warmup, dev, rank=0, world=1, 
         dist.all_reduce(te, op=dist.ReduceOp.MAX)
         elapsed = float(te[0])
     return model, batches, elapsed, float(loss_v['sum'])
+
+
+def median_leg(model, batches, start, n_med, world=1):
+    """SURVEY 8d asks for the MEDIAN step: a second leg behind the contract's timed region, one event per step on the compute stream
+    (rank 0's own steps; >= 50 of them), reported beside the mean of the K timed steps.  Sets STEP_MS (sorted)."""
+    global STEP_MS
+    evs = [torch.cuda.Event(enable_timing=True) for _ in range(n_med + 1)]
+    evs[0].record()
+    for i in range(n_med):
+        model._fit_loop(list(batches[(start + i) % len(batches)]))
+        evs[i + 1].record()
+    torch.cuda.synchronize()
+    if world > 1:
+        dist.barrier()
+    STEP_MS = sorted(evs[i].elapsed_time(evs[i + 1]) for i in range(n_med))
+
+
+DUMP_PARAM_SAMPLE = 1 << 22          # 16 MB of float32 from the ~52 M floating state_dict values of the ResNet34 network
+DUMP_LOGITS_MAX = 1 << 23            # 32 MB: larger logits (batch > 256) are sampled the same way
+
+
+def _seeded_sample(flat, k, seed):
+    """`flat` (1-D tensor) whole when it has at most k elements, else k of them at sorted positions drawn with a fixed seed."""
+    if flat.numel() <= k:
+        return flat
+    idx = np.sort(np.random.default_rng(seed).choice(flat.numel(), k, replace=False))
+    return flat[torch.from_numpy(idx).to(flat.device)]
+
+
+def dump_outputs(path, model, net, loss):
+    """--dump-outputs: what the last timed step handed its caller (bench.py's docstring lists the files); float32 / float64 .npy."""
+    os.makedirs(path, exist_ok=True)
+    torch.cuda.synchronize()
+    sd = [v.detach() for v in model.model.state_dict().values() if v.is_floating_point()]
+    flat = torch.cat([v.reshape(-1).float().to(net.logits.device) for v in sd])
+    logits = net.logits.detach().float()
+    if logits.numel() > DUMP_LOGITS_MAX:
+        logits = _seeded_sample(logits.reshape(-1), DUMP_LOGITS_MAX, 1)
+    arrays = {'loss': np.array([loss], np.float32),
+              'logits': logits.cpu().numpy(),
+              'params_sample': _seeded_sample(flat, DUMP_PARAM_SAMPLE, 0).cpu().numpy(),
+              'param_norms': torch.stack([v.double().norm() for v in sd]).cpu().numpy()}
+    del flat
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + '.npy'), a)
+    return sorted(arrays)
 
 
 def fit_e2e_leg(dev, workload, dtype, B, loss, n_train=3200, n_val=800, epochs=2):
@@ -819,9 +867,12 @@ def main():
     ap.add_argument('--workload', default='r34_hyper', choices=['r34_hyper', 'ternaus34', 'vanilla'])
     ap.add_argument('--batch', type=int, default=32, help='images per GPU per step')
     ap.add_argument('--loss', default='lovasz', choices=['lovasz', 'bce_dice'])
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-iou', action='store_true', help='skip the fit_e2e leg (SegmentationModel.fit over host tiles with the callback stack + validation IoU)')
-    ap.add_argument('--no-configs', action='store_true', help='skip the other BASELINE configurations (C1, fp32, C3 shape, C4)')
+    ap.add_argument('--full', action='store_true', help='also run every leg beyond the headline: median-step leg, per-operator roofline, fit_e2e, '
+                    'the other BASELINE configurations, the data-parallel leg and the CPU baseline (a plain run times the K steps only)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None, help='write what the last timed step computed as DIR/<name>.npy (float32 / float64)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline leg')
+    ap.add_argument('--no-iou', action='store_true', help='with --full: skip the fit_e2e leg (SegmentationModel.fit over host tiles with the callback stack + validation IoU)')
+    ap.add_argument('--no-configs', action='store_true', help='with --full: skip the other BASELINE configurations (C1, fp32, C3 shape, C4)')
     ap.add_argument('--cpu-leg', default=None, help=argparse.SUPPRESS)       # child mode of the cpu_baseline leg
     ap.add_argument('--dp-leg', action='store_true', help=argparse.SUPPRESS)     # child mode of configs.dp_path_1rank
     ap.add_argument('--cpu-threads', type=int, default=0, help=argparse.SUPPRESS)
@@ -867,8 +918,12 @@ def main():
 
     arch_name, channels, wl_desc = WORKLOADS[args.workload]
     B = args.batch
-    model, batches, elapsed, final_loss = train_config(args.workload, args.dtype, B, args.loss, args.steps, args.warmup, dev, rank, world)
+    model, batches, elapsed, final_loss = train_config(args.workload, args.dtype, B, args.loss, args.steps, args.warmup, dev, rank, world, median=False)
     value = world * B * args.steps / elapsed
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, model, model.model.engine().net((B, channels, 128, 128), True), final_loss)
+    if args.full:
+        median_leg(model, batches, args.warmup + args.steps, max(50, args.steps), world)
 
     out = {'metric': 'training images/sec, U-Net ResNet34 101x101 (pad->128) bs32/GPU', 'value': round(value, 2), 'unit': 'images/s',
            'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': round(1e3 * elapsed / args.steps, 3),
@@ -902,11 +957,12 @@ def main():
         # per bucket: when its gradients were final and when its all-reduce had finished, relative to the END of backward on the compute
         # stream (negative = underneath backward): 6 extra steps behind the timed region, every rank takes part in their collectives
         model.dp.measure = False
-        model.dp.timeline = True
-        for i in range(6):
-            model._fit_loop(list(batches[i % len(batches)]))
-        out['allreduce']['bucket_timeline_rank0'] = model.dp.bucket_timeline()
-        model.dp.timeline = False
+        if args.full:
+            model.dp.timeline = True
+            for i in range(6):
+                model._fit_loop(list(batches[i % len(batches)]))
+            out['allreduce']['bucket_timeline_rank0'] = model.dp.bucket_timeline()
+            model.dp.timeline = False
         if out['rccl_ranks'] != args.gpus:
             sys.stderr.write('bench.py: --gpus %d but the RCCL communicator has %d ranks\n' % (args.gpus, out['rccl_ranks']))
             if dist.is_initialized():
@@ -914,7 +970,7 @@ def main():
             sys.exit(4)
 
     # ------------------------------------------------------------------ live roofline (rank 0): event pair around every operator
-    if rank == 0:
+    if rank == 0 and args.full:
         eng = model.model.engine()
         net = eng.net((B, channels, 128, 128), True)
         net.x.copy_(batches[0][0]); net.target.copy_(batches[0][1])
@@ -967,7 +1023,7 @@ def main():
                                 'contractions at 1/16 .. 1/256 of the pixels + a vector-ALU stencil; roofline fractions are priced on EXECUTED matrix FLOPs'}
 
     # ------------------------------------------------------------------ end to end: SegmentationModel.fit() over host tiles (N = 1 only)
-    fit_pending = not args.no_iou and rank == 0 and world == 1
+    fit_pending = args.full and not args.no_iou and rank == 0 and world == 1
 
     if rank == 0 and 'roofline_by_class' in out:           # the fused Adam + L2 kernel (28 bytes per parameter), timed after the evaluation
         aprog = model.optimizer._adam_pack_program() or model.optimizer.prog      # (bf16: Adam also writes the forward weight packs, 2 more bytes per packed parameter)
@@ -989,7 +1045,7 @@ def main():
         out['val_iou_note'] = ('validation IoU (reference metric, threshold from the sweep) on %d held-out synthetic tiles after fit(): %d epochs x %d '
                                'steps from random init - a signal that the shipped trainer learns, not an accuracy result; convergence PARITY is '
                                'tests/test_gpu_convergence.py' % (fe['n_val'], fe['epochs'], fe['steps'] // fe['epochs']))
-    if rank == 0 and world == 1 and not args.no_configs:
+    if rank == 0 and world == 1 and args.full and not args.no_configs:
         if model is not None:
             del model, batches
             torch.cuda.empty_cache()
@@ -1002,7 +1058,7 @@ def main():
             out['configs']['dp_path_1rank'] = dp_leg_subprocess(args.workload, args.dtype, B, args.loss)
 
     # ------------------------------------------------------------------ CPU baseline: the oracle on the host cores (bounded sample)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         out['cpu_baseline'] = cpu_baseline_subprocess(args.loss, arch_name)
         if not args.no_configs:
             # BASELINE C0: the vanilla U-Net on the CPU (batch 8), the reference's own CPU-runnable case

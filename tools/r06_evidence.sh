@@ -12,7 +12,7 @@ rm -f $O/${tag}_parity_counts.json
 SALT_PARITY_COUNTS=$R/$O/${tag}_parity_counts.json timeout 1500 python -m pytest tests/test_gpu_models.py tests/test_gpu_fused_step.py tests/test_gpu_baseline_configs.py \
   tests/test_gpu_convergence.py -m gpu -q -k "c1_shape or c2_shape or c4 or 20_steps" > $O/${tag}_parity_tests.log 2>&1
 tail -3 $O/${tag}_parity_tests.log
-python bench.py > $O/${tag}_c2_bf16_r34hyper_b32_bench.json 2> $O/${tag}_bench.err
+python bench.py --full > $O/${tag}_c2_bf16_r34hyper_b32_bench.json 2> $O/${tag}_bench.err
 cut -c1-400 $O/${tag}_c2_bf16_r34hyper_b32_bench.json
 prof() {   # prof <name> <cmd...>: rocprofv3 --kernel-trace --stats -> db path in $DB
   cd /tmp && export TMPDIR=/tmp

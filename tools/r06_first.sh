@@ -6,6 +6,6 @@ timeout 1500 python -m pytest tests/test_gpu_two_ranks.py tests/test_gpu_blocks.
 tail -15 $O/r06_first_tests.log
 for rep in 1 2; do for z in 1 0; do
   echo "== SALT_STEP_ZERO_COPY=$z"
-  SALT_STEP_ZERO_COPY=$z python bench.py --steps 40 --warmup 10 --no-cpu-baseline --no-iou --no-configs 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('C2', d['value'], d['ms_per_step'], d.get('ms_per_step_median'), d['roofline'].get('kernel_symbol'))"
+  SALT_STEP_ZERO_COPY=$z python bench.py --full --steps 40 --warmup 10 --no-cpu-baseline --no-iou --no-configs 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('C2', d['value'], d['ms_per_step'], d.get('ms_per_step_median'), d['roofline'].get('kernel_symbol'))"
 done; done > $O/r06_zero_copy_ab.txt 2>&1
 cat $O/r06_zero_copy_ab.txt
