@@ -913,6 +913,113 @@ typedef struct {
 } salt_preprocess_args;
 int salt_preprocess(const salt_preprocess_args*, void* stream);
 
+/* on-device training augmentation fused with the train-branch preprocessing (main.py:130-133, loaders.py:124-150,
+ * augmentation.py:34-65).  Per image b (one workgroup, planes in LDS, every stage written back onto the uint8 grid with
+ * round-half-up + clip; the mask is binarised (!= 0) after every stage):
+ *   affine_seq: stages A | B | C in a random permutation
+ *     A  SomeOf((1, 2), [Fliplr(p), Sharpen(alpha, lightness), Emboss(alpha, strength), Affine(rotate, translate x, mode edge)]),
+ *        picks among the ENABLED children only, applied in list order (no child enabled: A is a no-op)
+ *     B  Sometimes(p, PiecewiseAffine(scale)): 4x4 control points at linspace(0, h, 4) x linspace(0, w, 4) jittered by
+ *        N(0, s) * h (y) / N(0, s) * w (x); every grid cell is split along its top-left -> bottom-right diagonal; the output pixel's
+ *        triangle of the regular grid maps affinely onto the jittered triangle; bilinear, 0 outside
+ *     C  Sometimes(p, PerspectiveTransform(scale)): corners tl (jx, jy), tr (w - jx, jy), br (w - jx, h - jy), bl (jx, h - jy) with
+ *        j = (|N(0, s)| mod 1) * size; rectified size max(int(|br - bl|), int(|tr - tl|)) x max(int(|bl - tl|), int(|br - tr|)),
+ *        clamped to [2, SALT_AUG_RECT_MAX]; bilinear, 0 outside; then the float cubic (a = -0.75, replicated border) back to h x w
+ *   resize + edge pad exactly as salt_preprocess interpolation 2 (the fixed-point cubic)
+ *   intensity_seq on the padded uint8 grid: Invert(p), Sometimes(p, ContrastNormalization(alpha)), OneOf([Noop, OneOf([Add,
+ *     AddElementwise, Multiply, MultiplyElementwise])]) (Noop with p_noop, else uniform among the enabled four)
+ *   Normalize + AddDepthChannels + one-hot target exactly as salt_preprocess.
+ * RNG (splitmix64; all arithmetic mod 2^64):
+ *   mix(z) = z += 0x9E3779B97F4A7C15; z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9; z = (z ^ z >> 27) * 0x94D049BB133111EB; z ^ z >> 31
+ *   key    = mix(mix(mix(seed) ^ counter) ^ b);   bits(slot) = mix(key + slot * 0x9E3779B97F4A7C15)
+ *   uniform u = (bits >> 40) * 2^-24 (float, exact);  integer in [lo, hi]: lo + ((bits >> 32) * (hi - lo + 1) >> 32)
+ *   float in [lo, hi): lo + u * (hi - lo) (float32, rounded per operation);  normal k: Box-Muller on slots 64 + 2k, 65 + 2k with
+ *   u1 = ((bits >> 40) + 1) * 2^-24, sqrt(-2 ln u1) * cos(2 pi u2)
+ *   per-pixel draws (AddElementwise / MultiplyElementwise) use slot 1024 + Y * W + X of the padded output grid.
+ * Parameter slots: 0 order, 1 SomeOf n, 2 / 3 SomeOf picks, 4 flip, 5 angle, 6 shift, 7 / 8 piecewise on / scale, 10 / 11 perspective
+ *   on / scale, 12 invert, 13 / 14 contrast on / alpha, 15 / 16 intensity Noop / pick, 17 add / multiply value.
+ * Enable bits and probabilities apply to drawing; a replayed record (params_given) is applied as it is. */
+#define SALT_AUG_FLIPLR 1
+#define SALT_AUG_SHARPEN 2
+#define SALT_AUG_EMBOSS 4
+#define SALT_AUG_AFFINE 8
+#define SALT_AUG_PIECEWISE 16
+#define SALT_AUG_PERSPECTIVE 32
+#define SALT_AUG_INVERT 64
+#define SALT_AUG_CONTRAST 128
+#define SALT_AUG_ADD 256
+#define SALT_AUG_ADD_ELEMENTWISE 512
+#define SALT_AUG_MULTIPLY 1024
+#define SALT_AUG_MULTIPLY_ELEMENTWISE 2048
+#define SALT_AUG_MAX_TILE 128     /* h, w <= this */
+#define SALT_AUG_RECT_MAX 182     /* rectified perspective edge <= ceil(tile diagonal) */
+/* params record, fp32 [B, SALT_AUG_PARAMS] per image:
+ *   0 stage order: index into the permutations of (A, B, C) in lexicographic order: ABC ACB BAC BCA CAB CBA
+ *   1 SomeOf n (0: A applies nothing)         2..5 chosen: Fliplr, Sharpen, Emboss, Affine (0 / 1)
+ *   6 flip fires (0 / 1)                      7 rotation, degrees            8 shift, fraction of w (pixels = shift * w)
+ *   9 piecewise on (0 / 1)                    10 piecewise scale             11..42 jitter of control point k = 4 i + j: (dy, dx)
+ *                                                                                    at 11 + 2k, 12 + 2k, fractions of h / w
+ *   43 perspective on (0 / 1)                 44 perspective scale           45..52 corner offsets (x, y) of tl, tr, br, bl,
+ *                                                                                    fractions of w / h in [0, 1)
+ *   53 invert (0 / 1)                         54 contrast on (0 / 1)         55 contrast alpha
+ *   56 intensity op: 0 Noop, 1 Add, 2 AddElementwise, 3 Multiply, 4 MultiplyElementwise
+ *   57 Add value (integer) or Multiply factor  58..63 zero */
+#define SALT_AUG_PARAMS 64
+typedef struct {
+    int enable;               /* SALT_AUG_* bits */
+    float p_fliplr;           /* 0.5 */
+    float sharpen_alpha;      /* 0.5; matrix (1 - alpha) I + alpha [[-1,-1,-1],[-1,8+L,-1],[-1,-1,-1]] */
+    float sharpen_lightness;  /* 1 */
+    float emboss_alpha;       /* 0.5; matrix (1 - alpha) I + alpha [[-1-s,-s,0],[-s,1,s],[0,s,1+s]] */
+    float emboss_strength;    /* 1 */
+    float rotate_min;         /* -10 degrees */
+    float rotate_max;         /* 10 */
+    float shift_min;          /* -0.05 of w */
+    float shift_max;          /* 0.05 */
+    float p_piecewise;        /* 0.3 */
+    float piecewise_scale_min;  /* 0.04 */
+    float piecewise_scale_max;  /* 0.08 */
+    float p_perspective;      /* 0.3 */
+    float perspective_scale_min;  /* 0.05 */
+    float perspective_scale_max;  /* 0.1 */
+    float p_invert;           /* 0.3 */
+    float p_contrast;         /* 0.3 */
+    float contrast_min;       /* 0.5 */
+    float contrast_max;       /* 1.5 */
+    float p_intensity_noop;   /* 0.5 */
+    int add_min;              /* -10 (Add and AddElementwise, discrete uniform) */
+    int add_max;              /* 10 */
+    float mul_min;            /* 0.95 (Multiply and MultiplyElementwise) */
+    float mul_max;            /* 1.05 */
+} salt_augment_config;
+typedef struct {
+    const uint8_t* img;       /* [B,h,w] uint8, h, w <= SALT_AUG_MAX_TILE */
+    const uint8_t* mask;      /* [B,h,w] {0,1} (binarised != 0) or NULL */
+    int B;
+    int h;
+    int w;
+    int resize_h;             /* 0 = no resize; otherwise the fixed-point cubic of salt_preprocess interpolation 2 */
+    int resize_w;
+    int top;
+    int left;
+    int H;
+    int W;
+    int channels;             /* 1 | 3 */
+    float mean[3];
+    float std[3];
+    float* x;                 /* out fp32 NCHW [B,channels,H,W] */
+    float* target;            /* out fp32 NCHW [B,2,H,W]; required when mask != NULL */
+    salt_augment_config cfg;
+    uint64_t seed;
+    uint64_t counter;         /* the draws of image b are a pure function of (seed, counter, b) */
+    float* params;            /* [B, SALT_AUG_PARAMS] record: written when drawing, read when params_given; NULL = not recorded */
+    int params_given;         /* 1: replay `params` instead of drawing (per-pixel noise still from (seed, counter, b, pixel)) */
+    uint8_t* geo_img;         /* debug out [B,h,w]: the tile after the geometric stages, or NULL */
+    uint8_t* geo_mask;        /* debug out [B,h,w]: the binarised mask after the geometric stages, or NULL */
+    uint8_t* gray;            /* debug out [B,H,W]: the padded tile after the intensity stage, or NULL */
+} salt_augment_preprocess_args;
+int salt_augment_preprocess(const salt_augment_preprocess_args*, void* stream);
+
 /* centre crop + binarize one class of a probability map (postprocessing.py:24-43, utils.py:308-313): mask = prob[cls] > threshold */
 typedef struct {
     const float* prob;        /* fp32 NCHW [B,C,H,W] */

@@ -10,7 +10,7 @@
 //     -> Grayscale(3) + ToTensor + Normalize(mean, std) per channel
 //     -> AddDepthChannels: ch1 := linspace(0, 1, H)[row], ch2 := ch0 * ch1                                (3-channel mode)
 //   mask tile [h, w] -> nearest resize -> same pad -> one-hot {1 - m, m} target [2, H, W]
-#include "common.h"
+#include "preprocess_common.h"
 
 namespace {
 
@@ -25,40 +25,8 @@ __device__ __forceinline__ float src_index(int dst, float scale) {      // torch
     return s < 0.f ? 0.f : s;
 }
 
-// cv2.INTER_CUBIC / imgaug 0.2.5 iaa.Scale default: Keys cubic convolution, a = -0.75, taps at floor(s) - 1 .. floor(s) + 2 of the
-// half-pixel-centred source coordinate s = (dst + 0.5) * in / out - 0.5, indices clamped to the image (BORDER_REPLICATE)
-__device__ __forceinline__ void cubic_w(float t, float (&w)[4]) {
-    const float A = -0.75f;
-    w[0] = ((A * (t + 1.f) - 5.f * A) * (t + 1.f) + 8.f * A) * (t + 1.f) - 4.f * A;
-    w[1] = ((A + 2.f) * t - (A + 3.f)) * t * t + 1.f;
-    w[2] = ((A + 2.f) * (1.f - t) - (A + 3.f)) * (1.f - t) * (1.f - t) + 1.f;
-    w[3] = 1.f - w[0] - w[1] - w[2];
-}
-
-// cv2.resize(..., INTER_CUBIC) on CV_8U as opencv_python 3.4.0.12 (environment.yml:16) evaluates it (modules/imgproc/src/resize.cpp:
-// resizeGeneric_<HResizeCubic<uchar, int, short>, VResizeCubic<uchar, int, short, FixedPtCast<int, uchar, 22>, ...>>), restated:
-//   per axis   fx = (float)((d + 0.5) * scale - 0.5) with scale = 1 / ((double)out / in);  s = floor(fx);  t = fx - s   (float)
-//              coefficients interpolateCubic(t) in float32 (A = -0.75f, the four expressions below, no FMA contraction), each
-//              rounded on its own to a short: cvRound(c * 2048)   (their sum is 2047 .. 2049)
-//   horizontal int sums of uchar x short over taps s - 1 .. s + 2 (indices clamped = BORDER_REPLICATE)
-//   vertical   int sum of those x short, then saturate_cast<uchar>((v + (1 << 21)) >> 22)
-// (the SSE2 build of that release runs the vertical pass of whole 8-pixel groups in float32 with round-to-nearest-even: the same
-//  value except where v / 2^22 sits within float rounding of a tie - the integer form is the documented one and is what is restated.)
-__device__ __forceinline__ void cubic_coef_fixed(int d, double scale, int& s0, int (&c)[4]) {
-    const float fx = (float)(((double)d + 0.5) * scale - 0.5);
-    const float sf = floorf(fx);
-    const float t = __fsub_rn(fx, sf);
-    s0 = (int)sf - 1;
-    const float A = -0.75f;
-    const float x1 = __fadd_rn(t, 1.f);
-    const float c0 = __fsub_rn(__fmul_rn(__fadd_rn(__fmul_rn(__fsub_rn(__fmul_rn(A, x1), __fmul_rn(5.f, A)), x1), __fmul_rn(8.f, A)), x1), __fmul_rn(4.f, A));
-    const float c1 = __fadd_rn(__fmul_rn(__fmul_rn(__fsub_rn(__fmul_rn(__fadd_rn(A, 2.f), t), __fadd_rn(A, 3.f)), t), t), 1.f);
-    const float u = __fsub_rn(1.f, t);
-    const float c2 = __fadd_rn(__fmul_rn(__fmul_rn(__fsub_rn(__fmul_rn(__fadd_rn(A, 2.f), u), __fadd_rn(A, 3.f)), u), u), 1.f);
-    const float c3 = __fsub_rn(__fsub_rn(__fsub_rn(1.f, c0), c1), c2);
-    c[0] = __float2int_rn(__fmul_rn(c0, 2048.f)); c[1] = __float2int_rn(__fmul_rn(c1, 2048.f));
-    c[2] = __float2int_rn(__fmul_rn(c2, 2048.f)); c[3] = __float2int_rn(__fmul_rn(c3, 2048.f));
-}
+using salt_pre::cubic_w;
+using salt_pre::cubic_coef_fixed;
 
 __global__ void preprocess_kernel(PreKP p) {
     const int64_t n = (int64_t)p.B * p.H * p.W;
@@ -79,22 +47,11 @@ __global__ void preprocess_kernel(PreKP p) {
             int y0, x0, cy[4], cx[4];
             cubic_coef_fixed(ry, 1.0 / ((double)p.rh / (double)p.h), y0, cy);
             cubic_coef_fixed(rx, 1.0 / ((double)p.rw / (double)p.w), x0, cx);
-            int acc = 0, macc = 0;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int yy = min(max(y0 + i, 0), p.h - 1);
-                int row = 0, mrow = 0;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const int xx = min(max(x0 + j, 0), p.w - 1);
-                    row += cx[j] * (int)im8[yy * p.w + xx];
-                    if (mk8) mrow += cx[j] * (int)(mk8[yy * p.w + xx] != 0);  // the uint8 mask goes through the same augment_image call, binarised first like the float path / oracle.inputs (a 0 / 255 mask must not dilate)
-                }
-                acc += cy[i] * row; macc += cy[i] * mrow;
+            g = (float)salt_pre::fixed_to_u8(salt_pre::cubic_fixed_acc(im8, p.h, p.w, y0, cy, x0, cx, false)) * (1.f / 255.f);
+            if (mk8) {
+                mres = (float)salt_pre::fixed_to_u8(salt_pre::cubic_fixed_acc(mk8, p.h, p.w, y0, cy, x0, cx, true));
+                mres = mres > 0.5f ? 1.f : 0.f;
             }
-            g = (float)min(max((acc + (1 << 21)) >> 22, 0), 255) * (1.f / 255.f);
-            mres = (float)min(max((macc + (1 << 21)) >> 22, 0), 255);
-            mres = mres > 0.5f ? 1.f : 0.f;
         } else if (p.cubic) {
             const float fy = ((float)ry + 0.5f) * sy - 0.5f, fx = ((float)rx + 0.5f) * sx - 0.5f;
             const float y0f = floorf(fy), x0f = floorf(fx);
@@ -125,24 +82,14 @@ __global__ void preprocess_kernel(PreKP p) {
             const float hy = 1.f - ly, hx = 1.f - lx;
             g = hy * (hx * px(y0, x0) + lx * px(y0, x1)) + ly * (hx * px(y1, x0) + lx * px(y1, x1));
         }
-        const int64_t hw = (int64_t)p.H * p.W;
-        float* xo = p.x + (int64_t)b * p.channels * hw + (int64_t)Y * p.W + X;
-        const float c0 = (g - p.mean[0]) * p.inv_std[0];
-        xo[0] = c0;
-        if (p.channels == 3) {
-            const float depth = p.H > 1 ? (float)((double)Y / (double)(p.H - 1)) : 0.f;              // np.linspace(0, 1, H)[Y]
-            xo[hw] = depth;
-            xo[2 * hw] = c0 * depth;
-        }
+        float m = 0.f;
         if (p.mask) {
             // nearest: torch 'nearest' picks floor(dst * in / out)
             const int my = p.rh == p.h ? ry : min((int)floorf((float)ry * sy), p.h - 1);
             const int mx = p.rw == p.w ? rx : min((int)floorf((float)rx * sx), p.w - 1);
-            const float m = mres >= 0.f ? mres : (p.mask[((int64_t)b * p.h + my) * p.w + mx] ? 1.f : 0.f);
-            float* to = p.target + (int64_t)b * 2 * hw + (int64_t)Y * p.W + X;
-            to[0] = 1.f - m;
-            to[hw] = m;
+            m = mres >= 0.f ? mres : (p.mask[((int64_t)b * p.h + my) * p.w + mx] ? 1.f : 0.f);
         }
+        salt_pre::store_x_target(p.x, p.mask ? p.target : nullptr, b, Y, X, p.H, p.W, p.channels, p.mean, p.inv_std, g, m);
     }
 }
 

@@ -8,10 +8,21 @@ The reference prepares every tile on the CPU with PIL / imgaug / torchvision and
     inference  edge-pad to the next multiple of 64 with the reference's split: top 13 / bottom 14, left 14 / right 13
     both       Grayscale(3) + ToTensor + Normalize(ImageNet) + AddDepthChannels; mask -> {background, salt} one-hot
 
-Geometric augmentation (imgaug affine / intensity sequences) stays out of scope.
+Training augmentation (the reference's affine_seq / intensity_seq, main.py:130-133, augmentation.py:34-65) runs on the device too,
+fused into the same pass (csrc/augment.hip, `salt_augment_preprocess`).  It is off by default; a main.py-style caller turns it on for
+the training batches only:
+
+    pre_train = DevicePreprocessor(True, 3, augment=True, seed=1234 + rank)     # data-parallel ranks need distinct seeds
+    pre_valid = DevicePreprocessor(False, 3)                                   # inference / validation batches are never augmented
+    X, target = pre_train(images_u8, masks_u8)                                 # [B,101,101] uint8 on the GPU
+
+``augment=AugmentConfig(...)`` changes probabilities / ranges or switches single ops off; every call draws fresh parameters from
+(seed, call counter, image index), and ``record_params=True`` keeps the drawn record for ``last_params()``.
 """
 import ctypes
+import dataclasses
 
+import numpy as np
 import torch
 
 from ._abi import OP_FUNCS, SaltError, check, fill
@@ -28,21 +39,105 @@ def pad_split(size, divisor=64):
     return int(pad / 2), pad - int(pad / 2)
 
 
+AUG_OPS = ('fliplr', 'sharpen', 'emboss', 'affine', 'piecewise', 'perspective', 'invert', 'contrast', 'add', 'add_elementwise',
+           'multiply', 'multiply_elementwise')          # the SALT_AUG_* enable bits, in bit order
+N_PARAMS = 64                                          # SALT_AUG_PARAMS
+STAGE_ORDERS = ('ABC', 'ACB', 'BAC', 'BCA', 'CAB', 'CBA')
+INTENSITY_OPS = ('noop', 'add', 'add_elementwise', 'multiply', 'multiply_elementwise')
+
+
+@dataclasses.dataclass
+class AugmentConfig:
+    """The reference's augmentation sequences (augmentation.py:34-65) as numbers; defaults are the reference's.  ``enable``: the ops that
+    may be drawn (SomeOf draws among the enabled children of stage A only; OneOf among the enabled intensity ops)."""
+    enable: tuple = AUG_OPS
+    p_fliplr: float = 0.5
+    sharpen_alpha: float = 0.5
+    sharpen_lightness: float = 1.0
+    emboss_alpha: float = 0.5
+    emboss_strength: float = 1.0
+    rotate: tuple = (-10.0, 10.0)
+    shift: tuple = (-0.05, 0.05)
+    p_piecewise: float = 0.3
+    piecewise_scale: tuple = (0.04, 0.08)
+    p_perspective: float = 0.3
+    perspective_scale: tuple = (0.05, 0.1)
+    p_invert: float = 0.3
+    p_contrast: float = 0.3
+    contrast: tuple = (0.5, 1.5)
+    p_intensity_noop: float = 0.5
+    add: tuple = (-10, 10)
+    multiply: tuple = (0.95, 1.05)
+
+    @classmethod
+    def none(cls, **kw):
+        """every op switched off (the identity): ``AugmentConfig.none(enable=('fliplr',))`` enables one"""
+        kw.setdefault('enable', ())
+        return cls(**kw)
+
+    def enable_mask(self):
+        bad = [o for o in self.enable if o not in AUG_OPS]
+        if bad:
+            raise SaltError('AugmentConfig: unknown ops %s (known: %s)' % (bad, ', '.join(AUG_OPS)))
+        return sum(1 << AUG_OPS.index(o) for o in set(self.enable))
+
+    def fill(self, cfg):
+        """set a ctypes salt_augment_config"""
+        fill(cfg, enable=self.enable_mask(), p_fliplr=self.p_fliplr, sharpen_alpha=self.sharpen_alpha, sharpen_lightness=self.sharpen_lightness,
+             emboss_alpha=self.emboss_alpha, emboss_strength=self.emboss_strength, rotate_min=self.rotate[0], rotate_max=self.rotate[1],
+             shift_min=self.shift[0], shift_max=self.shift[1], p_piecewise=self.p_piecewise, piecewise_scale_min=self.piecewise_scale[0],
+             piecewise_scale_max=self.piecewise_scale[1], p_perspective=self.p_perspective, perspective_scale_min=self.perspective_scale[0],
+             perspective_scale_max=self.perspective_scale[1], p_invert=self.p_invert, p_contrast=self.p_contrast,
+             contrast_min=self.contrast[0], contrast_max=self.contrast[1], p_intensity_noop=self.p_intensity_noop,
+             add_min=int(self.add[0]), add_max=int(self.add[1]), mul_min=self.multiply[0], mul_max=self.multiply[1])
+
+
+def decode_params(params):
+    """[B, 64] params record (saltnet.h SALT_AUG_PARAMS layout) -> dict of numpy arrays, one entry per image"""
+    p = np.asarray(params.detach().cpu() if torch.is_tensor(params) else params, dtype=np.float32).reshape(-1, N_PARAMS)
+    return {'order': p[:, 0].astype(np.int64), 'n': p[:, 1].astype(np.int64), 'chosen': p[:, 2:6] != 0, 'flip': p[:, 6] != 0,
+            'angle': p[:, 7], 'shift': p[:, 8], 'piecewise': p[:, 9] != 0, 'piecewise_scale': p[:, 10],
+            'piecewise_jitter': p[:, 11:43].reshape(-1, 4, 4, 2), 'perspective': p[:, 43] != 0, 'perspective_scale': p[:, 44],
+            'perspective_corners': p[:, 45:53].reshape(-1, 4, 2), 'invert': p[:, 53] != 0, 'contrast': p[:, 54] != 0,
+            'contrast_alpha': p[:, 55], 'intensity_op': p[:, 56].astype(np.int64), 'value': p[:, 57]}
+
+
 class DevicePreprocessor:
     """Callable: (images [B,h,w] uint8|float, masks [B,h,w] or None) on the GPU -> (X [B,C,H,W], target [B,2,H,W] | None)."""
 
-    def __init__(self, train, channels=3, resize=102, pad=13, divisor=64, mean=MEAN, std=STD, interpolation='cubic'):
+    def __init__(self, train, channels=3, resize=102, pad=13, divisor=64, mean=MEAN, std=STD, interpolation='cubic', augment=False, seed=1234,
+                 record_params=False):
         """``interpolation`` of the train-branch resize: 'cubic' (default) is what the reference executes - augmentation.py:79-85 calls
         ``iaa.Scale({...})`` without an interpolation argument and imgaug 0.2.5 (environment.yml:15) defaults to 'cubic' =
         cv2.INTER_CUBIC, applied to the uint8 tile AND the uint8 {0,1} mask.  uint8 tiles take cv2's own evaluation of that filter
         (11-bit fixed-point coefficients, integer sums, saturating shift: opencv_python 3.4.0.12, environment.yml:16); float tiles -
         and 'cubic_float' for uint8 ones - the float form of the same filter (differs by 1 LSB on a few percent of the pixels);
-        'bilinear' is rounds 1-2 of this build."""
+        'bilinear' is rounds 1-2 of this build.
+
+        ``augment``: False (default: the tiles as they are), True (the reference's affine_seq + intensity_seq) or an AugmentConfig;
+        training batches of uint8 tiles up to 128x128 with the 'cubic' resize only.  ``seed``: the draws of image b of the k-th call are a
+        pure function of (seed, k, b) - give every data-parallel rank its own seed.  ``record_params``: keep the drawn parameters of the
+        last call for ``last_params()``."""
         if interpolation not in ('cubic', 'cubic_float', 'bilinear'):
             raise SaltError('DevicePreprocessor: interpolation %r (cubic | cubic_float | bilinear)' % (interpolation,))
         self.interpolation = interpolation
         self.train, self.channels, self.resize, self.pad, self.divisor = bool(train), int(channels), resize, pad, divisor
         self.mean, self.std = tuple(mean), tuple(std)
+        if augment is True:
+            augment = AugmentConfig()
+        elif augment is False or augment is None:
+            augment = None
+        elif not isinstance(augment, AugmentConfig):
+            raise SaltError('DevicePreprocessor: augment must be True, False or an AugmentConfig')
+        if augment is not None and not self.train:
+            raise SaltError('DevicePreprocessor: augmentation is for training batches (the reference never augments inference batches)')
+        if augment is not None and interpolation != 'cubic':
+            raise SaltError("DevicePreprocessor: augmentation runs with the 'cubic' resize of uint8 tiles")
+        if augment is not None:
+            augment.enable_mask()
+        self.augment, self.seed, self.record_params = augment, int(seed), bool(record_params)
+        self.counter = 0                       # calls so far: the `counter` of the next augmented call
+        self._params = None
 
     def geometry(self, h, w):
         """(resize_h, resize_w, top, left, H, W)"""
@@ -53,11 +148,17 @@ class DevicePreprocessor:
         right, left = pad_split(w, self.divisor)          # horizontal: int(pad/2) goes to the right
         return 0, 0, top, left, h + top + bottom, w + left + right
 
-    def __call__(self, images, masks=None):
-        if not images.is_cuda or (masks is not None and not masks.is_cuda):
+    def __call__(self, images, masks=None, params=None, debug=False):
+        """``params`` ([B, 64] fp32 on the GPU, augmentation only): replay that record instead of drawing.  ``debug``: also return a dict
+        with the geometric-stage tiles 'geo_img' / 'geo_mask' [B,h,w] and the padded intensity-stage tile 'gray' [B,H,W] (uint8)."""
+        if not images.is_cuda or (masks is not None and not masks.is_cuda) or (params is not None and not params.is_cuda):
             raise SaltError('DevicePreprocessor: tensors must live on the GPU (there is no CPU path)')
         if images.dtype not in (torch.uint8, torch.float32):
             raise SaltError('DevicePreprocessor: images must be uint8 or float32 in [0, 1]')
+        if self.augment is not None:
+            return self._augment(images, masks, params, debug)
+        if params is not None or debug:
+            raise SaltError('DevicePreprocessor: params / debug need augment')
         images = images.contiguous()
         B, h, w = images.shape
         rh, rw, top, left, H, W = self.geometry(h, w)
@@ -75,3 +176,52 @@ class DevicePreprocessor:
              interpolation=0 if self.interpolation == 'bilinear' else (2 if self.interpolation == 'cubic' and images.dtype == torch.uint8 else 1))
         check(fn(ctypes.byref(s), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), 'preprocess')
         return x, target
+
+    def _augment(self, images, masks, params, debug):
+        if images.dtype != torch.uint8:
+            raise SaltError('DevicePreprocessor: augmentation takes uint8 tiles (the reference augments uint8 arrays)')
+        images = images.contiguous()
+        B, h, w = images.shape
+        if h > 128 or w > 128:
+            raise SaltError('DevicePreprocessor: augmentation takes tiles up to 128x128 (got %dx%d)' % (h, w))
+        rh, rw, top, left, H, W = self.geometry(h, w)
+        dev = images.device
+        x = torch.empty((B, self.channels, H, W), dtype=torch.float32, device=dev)
+        target, mptr = None, None
+        if masks is not None:
+            masks = masks.contiguous().to(torch.uint8)
+            if tuple(masks.shape) != (B, h, w):
+                raise SaltError('DevicePreprocessor: masks must be [B,h,w] like the images')
+            target = torch.empty((B, 2, H, W), dtype=torch.float32, device=dev)
+            mptr = masks.data_ptr()
+        if params is not None:
+            params = params.contiguous()
+            if params.dtype != torch.float32 or tuple(params.shape) != (B, N_PARAMS):
+                raise SaltError('DevicePreprocessor: params must be fp32 [B, %d]' % N_PARAMS)
+            rec = params
+        else:
+            rec = torch.empty((B, N_PARAMS), dtype=torch.float32, device=dev) if self.record_params else None
+        dbg = {}
+        if debug:
+            dbg = {'geo_img': torch.empty((B, h, w), dtype=torch.uint8, device=dev), 'geo_mask': torch.empty((B, h, w), dtype=torch.uint8, device=dev),
+                   'gray': torch.empty((B, H, W), dtype=torch.uint8, device=dev)}
+        fn, S = OP_FUNCS['salt_augment_preprocess']
+        s = S()
+        self.augment.fill(s.cfg)
+        fill(s, img=images.data_ptr(), mask=mptr, B=B, h=h, w=w, resize_h=rh, resize_w=rw, top=top, left=left, H=H, W=W,
+             channels=self.channels, mean=list(self.mean), std=list(self.std), x=x.data_ptr(),
+             target=target.data_ptr() if target is not None else None, seed=self.seed & (2 ** 64 - 1), counter=self.counter,
+             params=rec.data_ptr() if rec is not None else None, params_given=int(params is not None),
+             geo_img=dbg['geo_img'].data_ptr() if debug else None, geo_mask=dbg['geo_mask'].data_ptr() if debug else None,
+             gray=dbg['gray'].data_ptr() if debug else None)
+        check(fn(ctypes.byref(s), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), 'augment_preprocess')
+        self.counter += 1
+        self._params = rec
+        return (x, target, dbg) if debug else (x, target)
+
+    def last_params(self, raw=False):
+        """the parameters of the last augmented call: decoded (dict of per-image numpy arrays) or ``raw`` ([B, 64] fp32 on the GPU);
+        needs record_params=True (or a replayed record)"""
+        if self._params is None:
+            raise SaltError('DevicePreprocessor: no params recorded (construct with augment and record_params=True)')
+        return self._params if raw else decode_params(self._params)
