@@ -234,19 +234,6 @@ typedef struct {
 } salt_wgrad_reduce_args;
 int salt_wgrad_reduce(const salt_wgrad_reduce_args*, void* stream);
 
-/* round 6: the slab reductions of SEVERAL layers in one launch (the 53 reductions of the ResNet34 U-Net's backward pass were 53 launches
- * of 4 - 25 us on the weight-gradient queue).  `jobs` = DEVICE array of njobs salt_wgrad_reduce_args (each with its own slab),
- * `job_block0` = DEVICE prefix sums [njobs + 1] of salt_wgrad_reduce_job_blocks over the jobs; per element the same loads and the same
- * summation order as salt_wgrad_reduce: bit-identical.  salt_wgrad_reduce_job_blocks validates a job (< 0: bad arguments). */
-typedef struct {
-    const void* jobs;
-    const int* job_block0;
-    int njobs;
-    int total_blocks;
-} salt_wgrad_reduce_batched_args;
-int salt_wgrad_reduce_batched(const salt_wgrad_reduce_batched_args*, void* stream);
-int salt_wgrad_reduce_job_blocks(const salt_wgrad_reduce_args*);
-
 /* fp32 master weight (reference layout) -> packed compute layout.
  * transpose=0: Wp[chunk][t][n=d0][c=d1]  from W[d0][d1][kh][kw]   (conv forward; convT dgrad)
  * transpose=1: Wp[chunk][t][n=d1][c=d0]                           (conv dgrad;   convT forward) */
@@ -586,20 +573,6 @@ typedef struct {              /* bilinear xR (nn.Upsample / F.upsample(mode='bil
                                * evaluated the same call: use it for checkpoints trained in the reference's own environment */
 } salt_bilinear_args;
 int salt_bilinear(const salt_bilinear_args*, void* stream);
-
-/* Hypercolumn rows (architectures/unet.py:101-107: torch.cat of the decoder maps up-sampled x2 / x4 / x8 / x16): ONE pass writes the
- * nlev up-sampled levels of every output pixel next to each other - channels [c0 + k*C, c0 + (k+1)*C) of y's pixel row from x[k] at
- * factor R[k] - instead of one salt_bilinear launch per level into a channel slice (128-byte pieces at the row pitch; at the C4 size
- * that streams a 2.7 GB buffer four times at 0.6 TB/s).  Same arithmetic per value as salt_bilinear: bit-identical. */
-typedef struct {
-    int dtype;
-    int nlev;                 /* 1..4 */
-    salt_view x[4];           /* [B, H / R[k], W / R[k], C] */
-    int R[4];
-    salt_view y;              /* [B, H, W, *] view whose channels [c0, c0 + nlev*C) are written (y.C = nlev*C, y.p at channel c0) */
-    int align_corners;
-} salt_hyper_rows_args;
-int salt_hyper_rows(const salt_hyper_rows_args*, void* stream);
 
 /* Factored hypercolumn (architectures/unet.py:101-109 + architectures/base.py:21-37).  The reference builds
  *   hyper = cat([dec1, up2(dec2), up4(dec3), up8(dec4), up16(dec5)])  and runs  Conv2dBnRelu(5 C, C): replicate pad (top 2, right 2), 3x3.
@@ -1069,8 +1042,7 @@ typedef struct {
     salt_op_fn fn;
     const void* args;
     int stream;               /* 0 = main, 1 = side, 2 = main after joining side work of this range, 3 = main after joining the side
-                                 stream unconditionally (work enqueued there before the call) - salt_program_run_streams;
-                                 4, 5 = auxiliary stream (salt_set_aux_stream), side stream without one */
+                                 stream unconditionally (work enqueued there before the call) - salt_program_run_streams */
     int reserved;
 } salt_program_entry;
 int salt_program_run(const salt_program_entry* entries, int n, void* stream);
@@ -1091,10 +1063,6 @@ int salt_program_run_streams_ex(const salt_program_entry* entries, int begin, in
  * one call per bucket (each cut cost a flush of the pending side-stream entries and the completion-signal fork hand-off). */
 int salt_program_run_streams_marks(const salt_program_entry* entries, int begin, int end, void* main_stream, void* side_stream, int join_at_end,
                                    const int* marks, int nmarks, void* const* ev_main, void* const* ev_side);
-/* stream-tag 4 entries (the weight-gradient slab reductions; behind the side entry in front of them, two alternating slab buffers) and
- * stream-tag 5 entries (optimizer updates of parameter ranges whose gradients are final; behind both queues) run on this stream in the
- * plain eager two-stream run, joined into the main stream at the end of the range; NULL (default): on the side stream.  Per host thread. */
-int salt_set_aux_stream(void* stream);
 int salt_event_create(void** event_out);            /* a hipEvent_t without timing */
 int salt_event_destroy(void* event);
 int salt_stream_wait_event(void* stream, void* event);

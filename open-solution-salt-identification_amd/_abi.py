@@ -9,13 +9,15 @@ import ctypes
 import os
 import re
 
+from . import switches
+
 import torch  # noqa: F401  FIRST: libsaltnet_hip.so must bind to the HIP runtime torch ships (its libamdhip64), not load a second
 #                      copy from /opt/rocm - two runtimes in one process leave the later one without a device (hipErrorNoDevice)
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_PKG)
 HEADER = os.path.join(_ROOT, 'include', 'saltnet.h')
-LIB_PATH = os.environ.get('SALT_LIB') or os.path.join(_PKG, 'libsaltnet_hip.so')      # SALT_LIB: A/B a build variant (tools/build_variant.sh)
+LIB_PATH = switches.get('SALT_LIB') or os.path.join(_PKG, 'libsaltnet_hip.so')      # SALT_LIB: A/B a build variant (tools/build_variant.sh)
 
 _SCALARS = {
     'int': ctypes.c_int, 'float': ctypes.c_float, 'int64_t': ctypes.c_int64, 'uint32_t': ctypes.c_uint32, 'uint64_t': ctypes.c_uint64,
@@ -118,7 +120,6 @@ lib.salt_program_run_streams_marks.argtypes = [ctypes.c_void_p, ctypes.c_int, ct
                                                ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p)]
 lib.salt_event_create.argtypes = [ctypes.POINTER(ctypes.c_void_p)]
 lib.salt_event_destroy.argtypes = [ctypes.c_void_p]
-lib.salt_set_aux_stream.argtypes = [ctypes.c_void_p]
 lib.salt_stream_wait_event.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
 
 DECLARED_SYMBOLS = [p[0] for p in _PROTOS] + ['salt_last_error']

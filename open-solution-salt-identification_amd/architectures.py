@@ -16,11 +16,11 @@ Reference classes mirrored (paths relative to the reference's common_blocks/):
   torchvision 0.2.0 models/resnet.py (un-vendored dependency): ResNet / BasicBlock / Bottleneck layout
 """
 import math
-import os
 
 import torch
 from torch import nn
 
+from . import switches
 from ._abi import SaltError
 from .runtime import Engine
 
@@ -175,7 +175,7 @@ def _shortcut_gradient_first(g, n0, downsample):
     makes that convolution's data gradient - a full-coverage launch - the last writer, which can then carry the BatchNorm-backward
     sums of x's producer (Graph._bn_train_bwd) and saves that layer's reduction pass.  ``n0`` = tape length BEFORE the main branch was
     emitted; the shortcut's closure sits at n0 - 1."""
-    if downsample is None or not g.train or os.environ.get('SALT_NO_SHORTCUT_FIRST') or n0 < 1 or len(g.tape) < n0 + 2:
+    if downsample is None or not g.train or switches.get('SALT_NO_SHORTCUT_FIRST') or n0 < 1 or len(g.tape) < n0 + 2:
         return
     g.tape.insert(n0, g.tape.pop(n0 - 1))        # [.., down, conv1, ..] -> [.., conv1, down, ..]: backward runs .., down, conv1
 
@@ -282,7 +282,7 @@ class ResNetEncoders(EmitOnly):
 class HipNetwork(nn.Module):
     """Base of the callable networks: owns the Engine, dispatches forward to the compiled HIP program."""
 
-    compute_dtype = os.environ.get('SALT_DTYPE', 'f32')
+    compute_dtype = switches.get('SALT_DTYPE')
     # nn.Upsample / F.upsample(mode='bilinear') (base.py:70, unet.py:103-106).  False: torch >= 0.4 semantics, what the oracle and the
     # goldens executed (torch 2.10).  True: how torch 0.3.1 - the version the reference pins, environment.yml:17 - evaluated the very
     # same calls; a checkpoint TRAINED in the reference's environment saw these features, so evaluate / fine-tune it with True
@@ -403,18 +403,14 @@ class UNetResNet(HipNetwork):
         e5 = emit_blocks(g, enc.layer4, e4, out=cat5.slice(b // 2, 512 * exp))
         c = self.center[1].emit(g, self.center[0].emit(g, e5))
         c = g.avgpool2(c, name='center.pool')
-        # SALT_HYPER_ROWS (default 0; 1: eval, 2: train too): ONE salt_hyper_rows pass writes the four up-sampled levels of every pixel row
-        # instead of four launches into channel slices - measured SLOWER on both streams, kept selectable
-        rows_mode = int(os.environ.get('SALT_HYPER_ROWS', '0'))
-        fused_rows = self.use_hypercolumn and (rows_mode == 2 or (rows_mode == 1 and not g.train))
         # FACTORED hypercolumn (round 5; DESIGN 4, saltnet.h salt_hyper_stencil): the levels up-sampled by R >= SALT_HYPER_FACTOR (default 4;
         # 0 = off) are never up-sampled, stored or convolved at full resolution.  A 1x1 contraction commutes with the bilinear
         # interpolation and the tap shift, so each such level enters the final convolution as z_k = [W_tap] dec_k - ONE 1x1 launch at the
         # level's own resolution - plus a separable stencil that adds sum_tap shift_tap(up(z_k[tap])) to the convolution over the
         # remaining full-resolution channels [dec1 | up2(dec2)]
-        fmin = int(os.environ.get('SALT_HYPER_FACTOR', '4'))
+        fmin = switches.get('SALT_HYPER_FACTOR')
         levels = [(16, 4), (8, 3), (4, 2), (2, 1)]          # (R, channel block of the hypercolumn)
-        fact = [(R, k) for R, k in levels if fmin and R >= fmin] if (self.use_hypercolumn and not fused_rows) else []
+        fact = [(R, k) for R, k in levels if fmin and R >= fmin] if self.use_hypercolumn else []
         if fact and not g.hyper_factor_ok(B, H, W, d, [R for R, _ in fact]):
             fact = []
         nfull = 5 - len(fact)                               # channel blocks that stay at full resolution (contiguous from block 0)
@@ -426,7 +422,7 @@ class UNetResNet(HipNetwork):
             # 320-channel rows.  Every producer (dec1's scSE, the four up-samplings) and every gradient consumer then streams ONE dense
             # tensor instead of 128-byte pieces at a 640-byte pitch (0.6 TB/s at the C4 size); the final convolution, its data gradient
             # and its weight gradient address the planes themselves (salt_conv_args.x_plane / y_plane, salt_conv_wgrad_args.q_plane)
-            planes = d if (not fused_rows and nfull > 1 and g.planar_ok(B, H, W, nfull * d, d, self.final[0].conv)) else 0
+            planes = d if (nfull > 1 and g.planar_ok(B, H, W, nfull * d, d, self.final[0].conv)) else 0
             hyper = g.new_act(B, H, W, nfull * d, 'hypercolumn', planes=planes)
         # the hypercolumn up-samplings only feed the final convolution: each one goes to the side stream as soon as its decoder
         # level exists and overlaps the remaining decoder levels; the final convolution joins
@@ -434,7 +430,7 @@ class UNetResNet(HipNetwork):
             if (R, k) in fact:
                 with g.side():
                     zs[k] = g.hyper_level(x, self.final[0].conv, k * d, name='hyper.z%d' % k)
-            elif self.use_hypercolumn and not fused_rows:
+            elif self.use_hypercolumn:
                 with g.side():
                     g.upsample(x, R, out=hyper.slice(k * d, d))
         d5 = self.dec5.emit(g, c, e5, cat=cat5)
@@ -445,15 +441,12 @@ class UNetResNet(HipNetwork):
         hyper_up(d3, 4, 2)
         d2 = self.dec2.emit(g, d3, e2, cat=cat2)
         hyper_up(d2, 2, 1)
-        if fused_rows:
-            with g.side():
-                g.hyper_rows([d2, d3, d4, d5], [2, 4, 8, 16], hyper.slice(d, 4 * d))
         if self.use_hypercolumn:
             d1 = self.dec1.emit(g, d2, None, out=hyper.slice(0, d))
             g.join()
             if fact:
                 ks = sorted(zs)
-                # eval: the 1x1 logit head is the block's only consumer - the stencil's epilogue applies it (SALT_HYPER_HEAD=0: separate launch)
+                # eval: the 1x1 logit head is the block's only consumer - the stencil's epilogue applies it
                 fuse_head = g.head_bn_ok(d, self.final[1]) if g.train else g.hyper_head_ok(d, self.final[1])
                 f = g.conv_hyper(hyper, [zs[k] for k in ks], [dict((k_, R_) for R_, k_ in fact)[k] for k in ks], self.final[0].conv,
                                  self.final[0].batch_norm, relu=self.final[0].use_relu, head=(self.final[1], logits) if fuse_head else None)

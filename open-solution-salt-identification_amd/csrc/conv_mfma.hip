@@ -1471,8 +1471,7 @@ int make_plan(const salt_conv_args* a, Plan* pl) {
     const int64_t pixels = (int64_t)a->x.B * a->OH * a->OW * (a->nphase > 1 ? a->nphase : 1);
     // 1x1 stride-1 convolution with Cin a multiple of 4 chunks: 4 channel chunks per barrier round (virtual taps, see the kernel)
     const int KCE_ = a->dtype == SALT_F32 ? 16 : 32;
-    static const bool vt_off = getenv("SALT_CONV_NO_VT") != nullptr;
-    const int vt = (!vt_off && a->ntaps == 1 && a->in_step == 1 && a->x.C % (4 * KCE_) == 0) ? 4 : 1;
+    const int vt = (a->ntaps == 1 && a->in_step == 1 && a->x.C % (4 * KCE_) == 0) ? 4 : 1;
     // ---- conv_glds_kernel (one 512-thread workgroup per CU, LDS-DMA ring): bf16, unit input step, 9 or 4 real taps, whole aligned
     // 64-byte channel chunks.  Decided from the geometry only (salt_conv_stats_parts plans with the same rule before the epilogue
     // fields are known).
@@ -1505,8 +1504,7 @@ int make_plan(const salt_conv_args* a, Plan* pl) {
         // few pixels, many channels (ResNet stages 3-4, the 8x8 / 16x16 decoder levels): 128x32 tiles double the workgroup count and
         // run at 3 workgroups per CU - measured 8-15 % faster than 128x64 / 64x64 there (tools/cfg_sweep.sh)
         const int64_t wgs = ((pixels + 127) / 128) * cdiv(Cout, 64);
-        static const int small_cfg = getenv("SALT_CONV_SMALL_CFG") ? atoi(getenv("SALT_CONV_SMALL_CFG")) : 4;
-        if (id == 1 && wgs < 512) id = (small_cfg == 5 && wgs >= 256) ? 1 : small_cfg;
+        if (id == 1 && wgs < 512) id = 4;
     }
     const TileCfg* cfg = nullptr;
     for (const auto& c : kCfgs) if (c.id == id) cfg = &c;
@@ -1523,8 +1521,7 @@ int make_plan(const salt_conv_args* a, Plan* pl) {
         // General tiles for the fused-fold data gradients (the extended grids are 2^n + 2 wide: 16-wide tiles of the 10 / 18 / 34-wide
         // grids are 40 - 60 % empty): full-width strips of th rows, or whole images when one fits.  Taken when they save >= 15 % of the
         // tile slots and their halo fits the loader.
-        static const bool gen_off = getenv("SALT_CONV_GEN_TILES") && atoi(getenv("SALT_CONV_GEN_TILES")) == 0;
-        if (fold_fused && !gen_off && a->in_step == 1 && vt == 1 && a->OW * (a->fold_top + 1) <= BM) {
+        if (fold_fused && a->in_step == 1 && vt == 1 && a->OW * (a->fold_top + 1) <= BM) {
             const int gtw = a->OW;
             int gth = BM / gtw, gnb = 1;
             if (gth >= a->OH) { gth = a->OH; gnb = BM / (a->OH * a->OW); }
@@ -2001,16 +1998,12 @@ struct WgradKP {
     int a_blocks, b_blocks;
     int bmp;                        // pixels per K tile (64 | 128)
     long long q_plane;              // salt_conv_wgrad_args.q_plane: b-block bb reads the dense plane Q + bb * q_plane (0: channel-interleaved rows)
-    int atomic;                     // SALT_WGRAD_ATOMIC=1 (A/B): every split ADDS into slab 0 with global_atomic_add_f32 instead of writing its own slab
     int ksplit;                     // conv_wgrad_kernel<float>: 0 off; 4: Ca, Cb <= 32 - the four waves share block (0, 0) and a quarter of the k-steps each;
                                     // 2: Ca <= 32 - waves (wa, wb) work on block (0, wb), k-step pairs of parity wa; 3: Cb <= 32 - block (wa, 0), parity wb
 };
 
 template <typename T> struct WRow { static constexpr int BYTES = 64 * (int)sizeof(T); };
-__device__ __forceinline__ void slab_put4(float* dst, const f32x4& v, bool atomic) {
-    if (atomic) { unsafeAtomicAdd(dst, v.x); unsafeAtomicAdd(dst + 1, v.y); unsafeAtomicAdd(dst + 2, v.z); unsafeAtomicAdd(dst + 3, v.w); }
-    else *reinterpret_cast<f32x4*>(dst) = v;
-}   // 64 channels per pixel row
+__device__ __forceinline__ void slab_put4(float* dst, const f32x4& v) { *reinterpret_cast<f32x4*>(dst) = v; }   // 64 channels per pixel row
 
 template <typename T, int NT>
 __global__ __launch_bounds__(256) void conv_wgrad_kernel(WgradKP p) {
@@ -2270,8 +2263,8 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(WgradKP p) {
                 const int a = a0 + wa_o * 32 + (r & 3) + 8 * (r >> 2) + 4 * khalf;
                 const int b = c0 + wb_o * 32 + l31;
                 if (a < p.Ca && b < p.Cb) {
-                    float* d = p.partials + (((int64_t)(p.atomic ? 0 : split) * p.ntaps + t) * p.Ca + a) * p.Cb + b;
-                    if (p.atomic) unsafeAtomicAdd(d, acc[t][r]); else *d = acc[t][r];
+                    float* d = p.partials + (((int64_t)split * p.ntaps + t) * p.Ca + a) * p.Cb + b;
+                    *d = acc[t][r];
                 }
             }
         }
@@ -2494,11 +2487,11 @@ __global__ __launch_bounds__(256) void conv_wgrad_fast_kernel(WgradKP p) {
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
         if (t < p.ntaps && a < p.Ca) {
-            float* row = p.partials + (((int64_t)(p.atomic ? 0 : split) * p.ntaps + t) * p.Ca + a) * p.Cb;
+            float* row = p.partials + (((int64_t)split * p.ntaps + t) * p.Ca + a) * p.Cb;
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 const int b = c0 + wb * 32 + 8 * g + 4 * khalf;
-                if (b < p.Cb) slab_put4(row + b, f32x4{acc[t][4 * g], acc[t][4 * g + 1], acc[t][4 * g + 2], acc[t][4 * g + 3]}, p.atomic != 0);
+                if (b < p.Cb) slab_put4(row + b, f32x4{acc[t][4 * g], acc[t][4 * g + 1], acc[t][4 * g + 2], acc[t][4 * g + 3]});
             }
         }
     }
@@ -2686,11 +2679,11 @@ __global__ __launch_bounds__(512) void conv_wgrad_fast8_kernel(WgradKP p) {
 #pragma unroll
     for (int tl = 0; tl < NTA; ++tl) {
         if (tl < cnt && a < p.Ca) {
-            float* row = p.partials + (((int64_t)(p.atomic ? 0 : split) * p.ntaps + grp * 5 + tl) * p.Ca + a) * p.Cb;
+            float* row = p.partials + (((int64_t)split * p.ntaps + grp * 5 + tl) * p.Ca + a) * p.Cb;
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 const int b = c0 + wb * 32 + 8 * g + 4 * khalf;
-                if (b < p.Cb) slab_put4(row + b, f32x4{acc[tl][4 * g], acc[tl][4 * g + 1], acc[tl][4 * g + 2], acc[tl][4 * g + 3]}, p.atomic != 0);
+                if (b < p.Cb) slab_put4(row + b, f32x4{acc[tl][4 * g], acc[tl][4 * g + 1], acc[tl][4 * g + 2], acc[tl][4 * g + 3]});
             }
         }
     }
@@ -2889,11 +2882,11 @@ __global__ __launch_bounds__(256) void conv_wgrad_fast32_kernel(WgradKP p) {
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
         if (t < p.ntaps && a < p.Ca) {
-            float* row = p.partials + (((int64_t)(p.atomic ? 0 : split) * p.ntaps + t) * p.Ca + a) * p.Cb;
+            float* row = p.partials + (((int64_t)split * p.ntaps + t) * p.Ca + a) * p.Cb;
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 const int b = c0 + wb * 32 + 8 * g + 4 * khalf;
-                if (b < p.Cb) slab_put4(row + b, f32x4{acc[t][4 * g], acc[t][4 * g + 1], acc[t][4 * g + 2], acc[t][4 * g + 3]}, p.atomic != 0);
+                if (b < p.Cb) slab_put4(row + b, f32x4{acc[t][4 * g], acc[t][4 * g + 1], acc[t][4 * g + 2], acc[t][4 * g + 3]});
             }
         }
     }
@@ -2931,7 +2924,7 @@ int wgrad_plan(const salt_conv_wgrad_args* a, WgradKP* k, int* nsplit_out) {
         if ((size_t)(bmp + k->nb * k->hh * k->hw) * rowb <= 80 * 1024) break;     // keep >= 2 workgroups per CU
     }
     k->P = a->p.p; k->Q = a->q.p; k->partials = a->partials;
-    k->q_plane = a->q_plane; k->ksplit = 0; k->atomic = 0;
+    k->q_plane = a->q_plane; k->ksplit = 0;
     k->B = a->p.B; k->PH = a->p.H; k->PW = a->p.W; k->Ca = a->p.C; k->p_cs = a->p.cs;
     k->QH = a->q.H; k->QW = a->q.W; k->Cb = a->q.C; k->q_cs = a->q.cs;
     k->ntaps = a->ntaps; k->q_step = a->q_step; k->pad_mode = a->pad_mode; k->min_dy = min_dy; k->min_dx = min_dx;
@@ -2942,7 +2935,6 @@ int wgrad_plan(const salt_conv_wgrad_args* a, WgradKP* k, int* nsplit_out) {
     k->a_blocks = cdiv(a->p.C, 64); k->b_blocks = cdiv(a->q.C, 64);
     // every split costs a partial slab (written here, read again by the reduce): bound the workgroup count and give each
     // workgroup enough pixel tiles to amortise its slab
-    static const int target_wgs = getenv("SALT_WGRAD_WGS") ? atoi(getenv("SALT_WGRAD_WGS")) : 512;
     // bf16: >= 8 pixel tiles per split (every split costs a 147 KB slab round trip).  fp32: 2 - the exact-f32 MFMA is 16x slower, so a
     // workgroup's 1024 pixels were ~200 us of matrix work on 32 workgroups (vanilla U-Net fp32: 7.47 -> 6.13 ms per step)
     static const int min_tiles_env = getenv("SALT_WGRAD_TPW") ? atoi(getenv("SALT_WGRAD_TPW")) : 0;
@@ -2952,14 +2944,11 @@ int wgrad_plan(const salt_conv_wgrad_args* a, WgradKP* k, int* nsplit_out) {
     // 16x16 levels run on the generic kernel, whose time is the length of a workgroup's tile chain, while more than ~256 workgroups take
     // CUs from the data-gradient chain
     const int min_tiles = min_tiles_env > 0 ? min_tiles_env : (a->dtype == SALT_F32 ? 2 : 8);
-    static const bool wgs_env = getenv("SALT_WGRAD_WGS") != nullptr;
     // bf16 (round 6): 128 workgroups per launch instead of 512.  Backward is bound by the kernel time of its two queues together
     // (DESIGN 7): a weight-gradient launch that holds every CU slows the data-gradient chain beside it by more than its own shorter
     // run is worth, and every split less is a 147 KB slab less to write and reduce.  Same box, C2 step: 512 5.05 - 5.08 ms, 256 5.00,
     // 160 5.00, 128 4.97 - 4.99, 96 5.03, 64 5.13, 32 5.97 (profiles/r06_wgrad_wgs_ab.txt)
-    static const int wgs_big = getenv("SALT_WGRAD_WGS_BIG") ? atoi(getenv("SALT_WGRAD_WGS_BIG")) : 0;      // A/B: the 128 x 128 maps (>= 2048 pixel tiles)
-    int ns = (wgs_env ? target_wgs : (a->dtype == SALT_F32 && !min_tiles_env) ? 256 : a->dtype == SALT_F32 ? target_wgs : 128) / blocks_;
-    if (wgs_big > 0 && k->ntiles >= 2048) ns = wgs_big / blocks_;
+    int ns = (a->dtype == SALT_F32 ? (min_tiles_env ? 512 : 256) : 128) / blocks_;
     // the stem (64 x 16 channels, launched on the MAIN stream at the very end of backward, nothing left to overlap with): finer
     // split.  NOT for the other single-block layers: their launches share the chip with the data-gradient chain, and 256 instead
     // of 128 weight-gradient workgroups cost 6.17 -> 6.24 ms per step (and halving the tiles per split wherever a launch has fewer than
@@ -3023,96 +3012,7 @@ __global__ __launch_bounds__(256) void wgrad_reduce8_kernel(ReduceKP p) {
     *dst = p.accumulate ? (*dst + s) : s;
 }
 
-// (VERDICT r4 #3a, built and measured in round 5: no gain - kept opt-in behind SALT_WGRAD_REDUCE9=1.)
-// nsplit <= 8 AND the nine taps of a 3x3 weight in raster order: one thread per (a, b) pair sums its nine taps (9 x nsplit coalesced
-// loads in flight) and stores them as the 36 contiguous bytes they are in the reference layout - a wave writes 2304 contiguous bytes.
-// wgrad_reduce8_kernel's thread-per-element form stores 4 bytes at a 36-byte stride (every 128-byte line of a 512 x 512 layer's
-// 9.4 MB gradient is written nine times, a ninth each).  Same summation order per element: bit-identical results.
-__global__ __launch_bounds__(256) void wgrad_reduce9_kernel(ReduceKP p) {
-    const int64_t ab = (int64_t)blockIdx.x * 256 + threadIdx.x, nab = (int64_t)p.Ca * p.Cb;
-    if (ab >= nab) return;
-    const int a = (int)(ab / p.Cb), b = (int)(ab - (int64_t)a * p.Cb);
-    const int64_t slab = 9 * nab;
-    float s[9];
-#pragma unroll
-    for (int t = 0; t < 9; ++t) {
-        float v[8];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) v[k] = k < p.nsplit ? p.partials[k * slab + t * nab + ab] : 0.f;
-        s[t] = (((v[0] + v[4]) + (v[1] + v[5])) + (v[2] + v[6])) + (v[3] + v[7]);
-    }
-    float* dst = p.grad + ((int64_t)a * p.ldb + b) * 9;
-#pragma unroll
-    for (int t = 0; t < 9; ++t) dst[t] = p.accumulate ? dst[t] + s[t] : s[t];
-}
-
-// salt_wgrad_reduce_batched: one launch over the reductions of several layers.  A block finds its job in the block-prefix table and
-// runs wgrad_reduce8_kernel's (nsplit <= 8: a thread per element, 256 elements per block) or wgrad_reduce_kernel's (4 split rows x 64
-// elements) body on it - the same loads, the same summation order, the same stores.
-__global__ __launch_bounds__(256) void wgrad_reduce_batched_kernel(const salt_wgrad_reduce_args* jobs, const int* block0, int njobs) {
-    __shared__ float sm[4][64];
-    int lo = 0, hi = njobs;                                     // block0[lo] <= blockIdx.x < block0[hi]
-    while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if ((int)blockIdx.x >= block0[mid]) lo = mid; else hi = mid; }
-    const salt_wgrad_reduce_args& a = jobs[lo];
-    const int blk = (int)blockIdx.x - block0[lo];
-    const int64_t slab = (int64_t)a.ntaps * a.Ca * a.Cb;
-    const int ldb = a.ldb > 0 ? a.ldb : a.Cb;
-    int64_t i; float s; bool writer;
-    if (a.nsplit <= 8) {
-        i = (int64_t)blk * 256 + threadIdx.x;
-        writer = i < slab;
-        float v[8];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) v[k] = (writer && k < a.nsplit) ? a.partials[k * slab + i] : 0.f;
-        s = (((v[0] + v[4]) + (v[1] + v[5])) + (v[2] + v[6])) + (v[3] + v[7]);
-    } else {
-        const int e = threadIdx.x & 63, row = threadIdx.x >> 6;
-        i = (int64_t)blk * 64 + e;
-        float s0 = 0.f, s1 = 0.f;
-        if (i < slab) {
-            int k = row;
-            for (; k + 4 < a.nsplit; k += 8) { s0 += a.partials[k * slab + i]; s1 += a.partials[(k + 4) * slab + i]; }
-            for (; k < a.nsplit; k += 4) s0 += a.partials[k * slab + i];
-        }
-        sm[row][e] = s0 + s1;
-        __syncthreads();
-        writer = row == 0 && i < slab;
-        s = sm[0][e] + sm[1][e] + sm[2][e] + sm[3][e];
-    }
-    if (!writer) return;
-    const int b = (int)(i % a.Cb);
-    int64_t r = i / a.Cb;
-    int ar = (int)(r % a.Ca);
-    int t = (int)(r / a.Ca);
-    if (a.a_mod) { t = ar / a.a_mod; ar -= t * a.a_mod; }
-    float* dst = a.grad + (((int64_t)ar * ldb + b) * a.KH + a.tap_kh[t]) * a.KW + a.tap_kw[t];
-    *dst = a.accumulate ? (*dst + s) : s;
-}
-
 }  // namespace
-
-extern "C" int salt_wgrad_reduce_job_blocks(const salt_wgrad_reduce_args* a) {
-    if (!a || a->ntaps < 1 || a->ntaps > SALT_MAX_TAPS || a->nsplit < 1 || a->Ca < 1 || a->Cb < 1 || a->KH < 1 || a->KW < 1) return -1;
-    int nt_tab = a->ntaps;
-    if (a->a_mod) {
-        if (a->a_mod < 0 || a->ntaps != 1 || a->Ca % a->a_mod || a->Ca / a->a_mod > SALT_MAX_TAPS) return -1;
-        nt_tab = a->Ca / a->a_mod;
-    }
-    if (a->ldb && a->ldb < a->Cb) return -1;
-    for (int t = 0; t < nt_tab; ++t)
-        if (a->tap_kh[t] < 0 || a->tap_kh[t] >= a->KH || a->tap_kw[t] < 0 || a->tap_kw[t] >= a->KW) return -1;
-    const int64_t slab = (int64_t)a->ntaps * a->Ca * a->Cb;
-    const int64_t blocks = a->nsplit <= 8 ? (slab + 255) / 256 : (slab + 63) / 64;
-    return blocks > 0x3fffffff ? -1 : (int)blocks;
-}
-
-extern "C" int salt_wgrad_reduce_batched(const salt_wgrad_reduce_batched_args* a, void* stream) {
-    if (!a || !a->jobs || !a->job_block0 || a->njobs < 1 || a->total_blocks < 1) SALT_FAIL(SALT_E_BADARG, "wgrad_reduce_batched: bad args");
-    hipLaunchKernelGGL(wgrad_reduce_batched_kernel, dim3((unsigned)a->total_blocks), dim3(256), 0, (hipStream_t)stream,
-                       static_cast<const salt_wgrad_reduce_args*>(a->jobs), a->job_block0, a->njobs);
-    SALT_CHECK_LAUNCH();
-    return SALT_OK;
-}
 
 extern "C" int salt_conv(const salt_conv_args* a, void* stream) {
     Plan pl;
@@ -3260,18 +3160,16 @@ static int launch_wgrad(const WgradKP& k, hipStream_t st) {
     const dim3 grid((unsigned)(k.a_blocks * k.b_blocks * k.nsplit));
     if constexpr (sizeof(T) == 2) {
         // fast path: whole aligned 16-byte pieces, 3x3, 128-pixel K tiles (conv_wgrad_fast_kernel)
-        static const bool generic = getenv("SALT_WGRAD_GENERIC") != nullptr;
         // (5..8 taps - the two 8-tap halves of the 4x4 space-to-depth stem - run the 9-tap instance: the padding tap re-reads tap 0's rows
         //  and is never stored)
-        const bool fast = !generic && k.ntaps >= 5 && k.ntaps <= 9 && k.bmp == 128 && k.p_cs % 8 == 0 && k.q_cs % 8 == 0 && k.Ca % 8 == 0 && k.Cb % 8 == 0 &&
+        const bool fast = k.ntaps >= 5 && k.ntaps <= 9 && k.bmp == 128 && k.p_cs % 8 == 0 && k.q_cs % 8 == 0 && k.Ca % 8 == 0 && k.Cb % 8 == 0 &&
                           ((reinterpret_cast<uintptr_t>(k.P) | reinterpret_cast<uintptr_t>(k.Q) | reinterpret_cast<uintptr_t>(k.partials)) & 15) == 0 &&
                           k.nb * k.hh * k.hw * 8 <= 10 * 256;
         if (fast) {
             SALT_WGRAD_PROBE(3)
             bool row16 = k.ntaps == 9 && k.tw_log2 == 4 && k.th_log2 == 3 && k.nb == 1 && k.q_step == 1 && k.hw == 18;
             for (int t = 0; t < 9; ++t) row16 = row16 && k.tap_off[t] == (t / 3) * 18 + t % 3;       // raster tap order
-            static const bool four_waves = getenv("SALT_WGRAD_W4") != nullptr;
-            if (row16 && !four_waves) {
+            if (row16) {
                 auto kern8 = k.pad_mode ? conv_wgrad_fast8_kernel<true> : conv_wgrad_fast8_kernel<false>;
                 if (lds > 64 * 1024) { hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern8), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
                     if (e != hipSuccess) SALT_FAIL((int)e, "hipFuncSetAttribute: %s", hipGetErrorString(e)); }
@@ -3279,8 +3177,7 @@ static int launch_wgrad(const WgradKP& k, hipStream_t st) {
                 SALT_CHECK_LAUNCH();
                 return SALT_OK;
             }
-            auto kern = k.pad_mode ? (row16 ? conv_wgrad_fast_kernel<9, 8, true, true> : conv_wgrad_fast_kernel<9, 8, true, false>)
-                                   : (row16 ? conv_wgrad_fast_kernel<9, 8, false, true> : conv_wgrad_fast_kernel<9, 8, false, false>);
+            auto kern = k.pad_mode ? conv_wgrad_fast_kernel<9, 8, true, false> : conv_wgrad_fast_kernel<9, 8, false, false>;
             if (lds > 64 * 1024) { hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
                 if (e != hipSuccess) SALT_FAIL((int)e, "hipFuncSetAttribute: %s", hipGetErrorString(e)); }
             hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, k);
@@ -3289,12 +3186,11 @@ static int launch_wgrad(const WgradKP& k, hipStream_t st) {
         }
         // round 3: the stride-2 3x3 layers (ResNet layer2-4 conv1): their halo (17 x 17 pixels for an 8 x 8 tile) only leaves room for
         // 64-pixel K tiles, which used to send them to the generic kernel (51 us at 94 TFLOP/s); the fast kernel with 4 k-steps per tile
-        static const bool no_fast64 = getenv("SALT_WGRAD_NO_FAST64") != nullptr;
-        const bool fast64 = !generic && !no_fast64 && k.ntaps == 9 && k.bmp == 64 && k.p_cs % 8 == 0 && k.q_cs % 8 == 0 && k.Ca % 8 == 0 && k.Cb % 8 == 0 &&
+        const bool fast64 = k.ntaps == 9 && k.bmp == 64 && k.p_cs % 8 == 0 && k.q_cs % 8 == 0 && k.Ca % 8 == 0 && k.Cb % 8 == 0 &&
                             ((reinterpret_cast<uintptr_t>(k.P) | reinterpret_cast<uintptr_t>(k.Q) | reinterpret_cast<uintptr_t>(k.partials)) & 15) == 0 &&
                             k.nb * k.hh * k.hw * 8 <= 10 * 256;
         // ... and the 1x1 stride-2 projection shortcuts (one tap; 33 us at 16 TFLOP/s on the generic kernel)
-        const bool fast1 = !generic && !no_fast64 && k.ntaps == 1 && !k.pad_mode && (k.bmp == 64 || k.bmp == 128) && k.p_cs % 8 == 0 && k.q_cs % 8 == 0 &&
+        const bool fast1 = k.ntaps == 1 && !k.pad_mode && (k.bmp == 64 || k.bmp == 128) && k.p_cs % 8 == 0 && k.q_cs % 8 == 0 &&
                            k.Ca % 8 == 0 && k.Cb % 8 == 0 &&
                            ((reinterpret_cast<uintptr_t>(k.P) | reinterpret_cast<uintptr_t>(k.Q) | reinterpret_cast<uintptr_t>(k.partials)) & 15) == 0 &&
                            k.nb * k.hh * k.hw * 8 <= 10 * 256;
@@ -3318,15 +3214,13 @@ static int launch_wgrad(const WgradKP& k, hipStream_t st) {
         }
     }
     if constexpr (sizeof(T) == 4) {
-        static const bool generic = getenv("SALT_WGRAD_GENERIC") != nullptr;
-        bool fast = !generic && k.ntaps == 9 && k.bmp == 128 && k.p_cs % 4 == 0 && k.q_cs % 4 == 0 && k.Ca % 4 == 0 && k.Cb % 4 == 0 &&
+        bool fast = k.ntaps == 9 && k.bmp == 128 && k.p_cs % 4 == 0 && k.q_cs % 4 == 0 && k.Ca % 4 == 0 && k.Cb % 4 == 0 &&
                     ((reinterpret_cast<uintptr_t>(k.P) | reinterpret_cast<uintptr_t>(k.Q) | reinterpret_cast<uintptr_t>(k.partials)) & 15) == 0 &&
                     k.tw_log2 == 4 && k.th_log2 == 3 && k.nb == 1 && k.q_step == 1 && k.hw == 18 && k.hh == 10;
         for (int t = 0; t < 9 && fast; ++t) fast = k.tap_off[t] == (t / 3) * 18 + t % 3;
         if (fast) {
             SALT_WGRAD_PROBE(4)
-            static const bool nosplit = getenv("SALT_WGRAD32_NOSPLIT") != nullptr;
-            const bool a32 = !nosplit && k.Ca <= 32, b32 = !nosplit && k.Cb <= 32;
+            const bool a32 = k.Ca <= 32, b32 = k.Cb <= 32;
             auto kern = k.pad_mode ? conv_wgrad_fast32_kernel<true> : conv_wgrad_fast32_kernel<false>;
             if (a32 && b32) kern = k.pad_mode ? conv_wgrad_fast32_kernel<true, 4, 0> : conv_wgrad_fast32_kernel<false, 4, 0>;
             else if (a32) kern = k.pad_mode ? conv_wgrad_fast32_kernel<true, 2, 0> : conv_wgrad_fast32_kernel<false, 2, 0>;
@@ -3341,8 +3235,7 @@ static int launch_wgrad(const WgradKP& k, hipStream_t st) {
     SALT_WGRAD_PROBE(5)
     WgradKP kg = k;
     if constexpr (sizeof(T) == 4) {
-        static const bool no_ks = getenv("SALT_WGRAD32_NOSPLIT") != nullptr;
-        if (!no_ks && !k.atomic && lds >= 4 * 16 * 64 * sizeof(float)) {
+        if (lds >= 4 * 16 * 64 * sizeof(float)) {
             const bool a32 = k.Ca <= 32, b32 = k.Cb <= 32;
             kg.ksplit = (a32 && b32) ? 4 : (a32 ? 2 : (b32 ? 3 : 0));
         }
@@ -3380,14 +3273,6 @@ extern "C" int salt_conv_wgrad(const salt_conv_wgrad_args* a, void* stream) {
     { int lrc = SALT_OK; if (conv_wgrad_thin(a, true, (hipStream_t)stream, &lrc) > 0) return lrc; }
     { int lrc = SALT_OK; if (conv_wgrad_ls(a, true, (hipStream_t)stream, &lrc) > 0) return lrc; }
     if (a->nsplit != ns) SALT_FAIL(SALT_E_BADARG, "wgrad: nsplit %d, expected %d", a->nsplit, ns);
-    // A/B switch: the splits add into ONE slab with global_atomic_add_f32 (zeroed here, in stream order) instead of
-    // writing nsplit slabs that salt_wgrad_reduce sums.  Not bit-reproducible; off by default.
-    static const bool atomic = getenv("SALT_WGRAD_ATOMIC") != nullptr;
-    k.atomic = atomic && ns > 1;
-    if (k.atomic) {
-        hipError_t e = hipMemsetAsync(a->partials, 0, (size_t)a->ntaps * k.Ca * k.Cb * sizeof(float), (hipStream_t)stream);
-        if (e != hipSuccess) SALT_FAIL((int)e, "hipMemsetAsync: %s", hipGetErrorString(e));
-    }
     if (a->dtype == SALT_F32) return launch_wgrad<float>(k, (hipStream_t)stream);
     if (a->dtype == SALT_BF16) return launch_wgrad<bf16_t>(k, (hipStream_t)stream);
     SALT_FAIL(SALT_E_BADARG, "wgrad: dtype");
@@ -3410,18 +3295,7 @@ extern "C" int salt_wgrad_reduce(const salt_wgrad_reduce_args* a, void* stream) 
         p.tap_kh[t] = a->tap_kh[t]; p.tap_kw[t] = a->tap_kw[t];
     }
     const int64_t slab = (int64_t)a->ntaps * a->Ca * a->Cb;
-    static const bool atomic = getenv("SALT_WGRAD_ATOMIC") != nullptr;
-    if (atomic && p.nsplit > 1) p.nsplit = 1;                      // salt_conv_wgrad added every split into slab 0
-    static const bool rows_reduce = getenv("SALT_WGRAD_REDUCE_ROWS") != nullptr;
-    bool raster9 = a->ntaps == 9 && a->KH == 3 && a->KW == 3 && !a->a_mod && a->nsplit <= 8;
-    for (int t = 0; t < 9 && raster9; ++t) raster9 = a->tap_kh[t] * 3 + a->tap_kw[t] == t;
-    // opt-in (SALT_WGRAD_REDUCE9=1; per call, the parity test switches it): measured NOT faster than the thread-per-element kernel (the
-    // 512 x 512 layers 14.0 against 12.8 us, the class 0.56 against 0.55 ms per step - the 36-byte-stride stores are merged in L2)
-    const char* r9_env = getenv("SALT_WGRAD_REDUCE9");
-    const bool use_r9 = r9_env && atoi(r9_env) == 1;
-    if (!rows_reduce && raster9 && use_r9)
-        hipLaunchKernelGGL(wgrad_reduce9_kernel, dim3((unsigned)(((int64_t)a->Ca * a->Cb + 255) / 256)), dim3(256), 0, (hipStream_t)stream, p);
-    else if (!rows_reduce && a->nsplit <= 8) hipLaunchKernelGGL(wgrad_reduce8_kernel, dim3((unsigned)((slab + 255) / 256)), dim3(256), 0, (hipStream_t)stream, p);
+    if (a->nsplit <= 8) hipLaunchKernelGGL(wgrad_reduce8_kernel, dim3((unsigned)((slab + 255) / 256)), dim3(256), 0, (hipStream_t)stream, p);
     else hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)((slab + 63) / 64)), dim3(256), 0, (hipStream_t)stream, p);
     SALT_CHECK_LAUNCH();
     return SALT_OK;

@@ -649,8 +649,7 @@ extern "C" int salt_conv_first_wgrad(const salt_conv_first_wgrad_args* a, void* 
     if (p.per > MAXKK) SALT_FAIL(SALT_E_UNSUPPORTED, "conv_first_wgrad: %d taps per thread > %d", p.per, MAXKK);
     const int nparts = a->B * p.tiles_y * p.tiles_x;
     if (a->nparts != nparts) SALT_FAIL(SALT_E_BADARG, "conv_first_wgrad: nparts %d, expected %d", a->nparts, nparts);
-    static const bool mfma_off = getenv("SALT_FIRST_WGRAD_MFMA") && atoi(getenv("SALT_FIRST_WGRAD_MFMA")) == 0;
-    p.mfma = (!mfma_off && Cout % 16 == 0 && KKC <= 16) ? 1 : 0;
+    p.mfma = (Cout % 16 == 0 && KKC <= 16) ? 1 : 0;
     const size_t lds = sizeof(float) * ((size_t)p.Cin * p.halo * p.halo + (size_t)256 * Cout + (p.mfma ? 1024 : 0));
     if (lds > 160 * 1024) SALT_FAIL(SALT_E_LDS, "conv_first_wgrad: needs %zu bytes of LDS", lds);
     SALT_DISPATCH_DTYPE(a->dtype, T, {

@@ -402,7 +402,7 @@ int thin_launch_mode(const ThKP& k, hipStream_t st) {
         attr_set = true;
     }
     int per_cu = (160 * 1024) / LDS;
-    static const int cap_env = getenv("SALT_THIN_WGS_PER_CU") ? atoi(getenv("SALT_THIN_WGS_PER_CU")) : 2;
+    constexpr int cap_env = 2;
     if (per_cu > cap_env) per_cu = cap_env;
     if (per_cu < 1) per_cu = 1;
     int wgs = thin_cus() * per_cu;

@@ -546,8 +546,7 @@ extern "C" int salt_debug_wl_clk(unsigned long long* host_out, int n) {
 int conv_wgrad_ls(const salt_conv_wgrad_args* a, bool launch, hipStream_t st, int* rc) {
     static const bool off = getenv("SALT_WGRAD_LS") && atoi(getenv("SALT_WGRAD_LS")) == 0;
     if (off || a->dtype != SALT_BF16 || a->ntaps != 9 || (a->q_step != 1 && a->q_step != 2)) return 0;
-    static const bool no_s2 = getenv("SALT_WGRAD_LS_S2") && atoi(getenv("SALT_WGRAD_LS_S2")) == 0;       // A/B: stride-2 layers on the previous kernels
-    if (a->q_step == 2 && (no_s2 || a->pad_mode != 0)) return 0;
+    if (a->q_step == 2 && a->pad_mode != 0) return 0;
     for (int t = 0; t < 9; ++t)
         if (a->tap_dy[t] != a->tap_dy[0] + t / 3 || a->tap_dx[t] != a->tap_dx[0] + t % 3) return 0;     // raster 3 x 3 window
     if (a->p.cs % 8 || a->q.cs % 8 || a->p.C % 8 || a->q.C % 8 || a->p.B != a->q.B) return 0;
@@ -575,12 +574,11 @@ int conv_wgrad_ls(const salt_conv_wgrad_args* a, bool launch, hipStream_t st, in
     // split rule of wgrad_plan: a workgroup budget per launch and a minimum of pixels per split (every split costs a slab round trip)
     // round 6: 128 workgroups per launch instead of 512 (wgrad_plan in conv_mfma.hip has the measurements: backward is bound by the
     // kernel time of both queues together, a weight-gradient launch on every CU slows the data-gradient chain beside it)
-    static const int target_wgs = getenv("SALT_WGRAD_WGS") ? atoi(getenv("SALT_WGRAD_WGS")) : 128;
-    static const int wgs_big = getenv("SALT_WGRAD_WGS_BIG") ? atoi(getenv("SALT_WGRAD_WGS_BIG")) : 0;      // A/B: the 128 x 128 maps
+    constexpr int target_wgs = 128;
     static const int tpw = getenv("SALT_WGRAD_TPW") ? atoi(getenv("SALT_WGRAD_TPW")) : 8;          // in 128-pixel tiles, as before
     const int blocks = k.a_blocks * k.b_blocks;
     int upw_min = tpw * 8 / KU; if (upw_min < 1) upw_min = 1;
-    int ns = ((wgs_big > 0 && (long long)k.total * KU >= 16384) ? wgs_big : target_wgs) / blocks;
+    int ns = target_wgs / blocks;
     if (ns > k.total / upw_min) ns = k.total / upw_min;
     if (ns < 1) ns = 1;
     k.upw = cdiv(k.total, ns);

@@ -1718,18 +1718,15 @@ int conv_ls_launch(const salt_conv_args* a, hipStream_t st) {
     // two-tile items (MT = 2): plain epilogue, 64-channel blocks, >= 4 chunks of input channels and >= 16 tiles per workgroup (>= 4 from 24 chunks).  Same-box
     // per-layer A/B on the ResNet152 pass: every layer of the class 2 - 12 % faster, the class 17.7 -> 16.0 ms.  (The first
     // version kept the 18 tap addresses in registers beside 128 accumulators: they were spilled and reloaded INSIDE the chunk loop and
-    // the layers with few chunks ran 12 - 20 % slower.)  SALT_CONV_LS_MT=1: off; SALT_CONV_LS_MT_MINCHUNK; cfg bit 20 asks, bit 21 forbids
-    static const int mt_env = getenv("SALT_CONV_LS_MT") ? atoi(getenv("SALT_CONV_LS_MT")) : 2;
-    static const int mt_minchunk = getenv("SALT_CONV_LS_MT_MINCHUNK") ? atoi(getenv("SALT_CONV_LS_MT_MINCHUNK")) : 4;
+    // the layers with few chunks ran 12 - 20 % slower.)  cfg bit 20 asks, bit 21 forbids
+    constexpr int mt_minchunk = 4, mt_mintiles = 16;
     // (a bias / folded-BatchNorm / ReLU / residual epilogue marks the forward layers of an eval-mode network: the plain data gradients of a B = 32 training step have 4 - 8 tiles per
-    //  workgroup and came out 0.25 % slower per step with two-tile items; SALT_CONV_LS_MT_TRAIN=1 lifts the restriction)
-    static const bool mt_train = getenv("SALT_CONV_LS_MT_TRAIN") != nullptr;
-    static const int mt_mintiles = getenv("SALT_CONV_LS_MT_MINTILES") ? atoi(getenv("SALT_CONV_LS_MT_MINTILES")) : 16;
+    //  workgroup and came out 0.25 % slower per step with two-tile items)
     const bool asked = (a->cfg & 0xff) == 10;
     int mt = 1;
     if (ni == 2 && !k.fin_acc && !k.bnb_acc) {
         if (asked && ((a->cfg >> 20) & 1)) mt = 2;
-        else if (!(asked && ((a->cfg >> 21) & 1)) && mt_env == 2 && k.nchunk >= mt_minchunk && (a->scale || a->bias || a->relu || a->res.p || mt_train) &&
+        else if (!(asked && ((a->cfg >> 21) & 1)) && k.nchunk >= mt_minchunk && (a->scale || a->bias || a->relu || a->res.p) &&
                  (k.per_xcd >= mt_mintiles * k.slots || (k.per_xcd >= 4 * k.slots && k.nchunk >= 24))) mt = 2;       // (8 tiles per workgroup x 4 chunks - the training step's 128 -> 64 over the two full-resolution hypercolumn planes - came out 50 % slower)
     }
     return ni == 2 ? ls_launch<2>(k, wgs, st, mt) : ls_launch<1>(k, wgs, st);

@@ -27,10 +27,7 @@ inline bool vec_ok(const salt_view& v, int ve) {
 }
 inline int ew_blocks(int64_t units) {
     static const int64_t cap = getenv("SALT_EW_BLOCKS") ? atoi(getenv("SALT_EW_BLOCKS")) : 512;      // round 6: 512 = two workgroups per CU (same box: 1024 5.27, 768 5.27, 512 5.20, 384 5.21, 256 5.23, 192 5.34 ms; round 3: 768 - since then every workgroup of the consumer-side finalize kernels pays the statistics prologue)
-    // SALT_EW_MIN_UNITS (A/B, round 5): at least this many 16-byte units per thread - fewer workgroups on the small tensors, where every
-    // workgroup's statistics prologue (8 shards x 2 C + 1 doubles from L2, fp64 division + square root per channel) outweighs its stream
-    static const int64_t min_units = getenv("SALT_EW_MIN_UNITS") ? atoi(getenv("SALT_EW_MIN_UNITS")) : 1;
-    int64_t b = (units + 256 * min_units - 1) / (256 * min_units); return (int)(b < 1 ? 1 : (b > cap ? cap : b));
+    int64_t b = (units + 255) / 256; return (int)(b < 1 ? 1 : (b > cap ? cap : b));
 }
 
 #ifndef SALT_BNB_UNITS
@@ -216,9 +213,8 @@ __global__ __launch_bounds__(256) void bn_finalize_kernel(salt_bn_finalize_args 
 // 64 part-rows x 4 channels for every layer: these kernels are pure latency (a few hundred KB), and the widest split - most
 // workgroups, fewest loads per thread - measured fastest on the whole step (7.50 vs 7.72 ms against the size-dependent choice).
 inline int bn_rows_for(int nparts) {
-    static const int force = getenv("SALT_BN_ROWS") ? atoi(getenv("SALT_BN_ROWS")) : 64;
     (void)nparts;
-    return force;
+    return 64;
 }
 
 __global__ void bn_fold_kernel(salt_bn_fold_args a) {
@@ -728,7 +724,7 @@ __global__ void avgpool2_kernel(salt_view x, salt_view y, int backward, int accu
 
 // U output units per thread in flight: the 4 U gathers of an iteration are issued before any of them is used.  (One unit per
 // iteration was a chain of ~16 dependent memory round trips per thread: 33 us for a 67 MB level, whatever the write pitch - round 3.)
-// the interpolation itself, with the contractions pinned (bilinear_fwd_kernel and hyper_rows_kernel must agree bit for bit)
+// the interpolation itself, with the contractions pinned (every forward kernel agrees bit for bit)
 __device__ __forceinline__ float bil_mix(float ly, float lx, float a, float b, float c, float d) {
     const float top = __fmaf_rn(lx, b, __fmul_rn(1.f - lx, a));
     const float bot = __fmaf_rn(lx, d, __fmul_rn(1.f - lx, c));
@@ -777,35 +773,6 @@ __global__ __launch_bounds__(256) void bilinear_fwd_kernel(salt_view x, salt_vie
                 o[j] = bil_mix(ly[i], lx[i], a[i][j], bq[i][j], c[i][j], d[i][j]);
             if (i == 0 || u0 + i * stride < units) Unit<T, VEC>::st((T*)y.p + dsto[i], o);
         }
-    }
-}
-
-// all levels of the hypercolumn in one pass: unit = (pixel, level, channel piece), so consecutive lanes write consecutive bytes of a pixel row
-struct HyperKP { salt_view x[4]; int R[4]; salt_view y; int nlev, ac; };
-template <typename T, bool VEC>
-__global__ void hyper_rows_kernel(HyperKP p) {
-    constexpr int N = Unit<T, VEC>::N;
-    const int cpl = p.x[0].C / N, upp = cpl * p.nlev;
-    const int64_t units = (int64_t)p.y.B * p.y.H * p.y.W * upp;
-    for (int64_t u = blockIdx.x * 256LL + threadIdx.x; u < units; u += gridDim.x * 256LL) {
-        int64_t pix = u / upp; const int r_ = (int)(u - pix * upp);
-        const int lev = r_ / cpl, c0 = (r_ - lev * cpl) * N;
-        const salt_view& x = p.x[lev];
-        const int R = p.R[lev];
-        const int ox = (int)(pix % p.y.W); int64_t r = pix / p.y.W; const int oy = (int)(r % p.y.H); const int b = (int)(r / p.y.H);
-        int y0, y1, x0, x1; float ly, lx;
-        bil_src(oy, R, x.H, p.ac, y0, y1, ly);
-        bil_src(ox, R, x.W, p.ac, x0, x1, lx);
-        const T* base = (const T*)x.p + (int64_t)b * x.H * x.W * x.cs + c0;
-        float a[N], bq[N], c[N], d[N], o[N];
-        Unit<T, VEC>::ld(base + ((int64_t)y0 * x.W + x0) * x.cs, a);
-        Unit<T, VEC>::ld(base + ((int64_t)y0 * x.W + x1) * x.cs, bq);
-        Unit<T, VEC>::ld(base + ((int64_t)y1 * x.W + x0) * x.cs, c);
-        Unit<T, VEC>::ld(base + ((int64_t)y1 * x.W + x1) * x.cs, d);
-#pragma unroll
-        for (int j = 0; j < N; ++j)
-            o[j] = bil_mix(ly, lx, a[j], bq[j], c[j], d[j]);
-        Unit<T, VEC>::st((T*)p.y.p + pix * p.y.cs + lev * x.C + c0, o);
     }
 }
 
@@ -1278,7 +1245,7 @@ extern "C" int salt_bn_fold(const salt_bn_fold_args* a, void* stream) {
 
 static int bn_bwd_nparts(const salt_bn_bwd_args* a, int64_t* ppb) {
     const int64_t npix = view_pixels(a->y);
-    static const int64_t max_parts = getenv("SALT_BNB_PARTS") ? atoi(getenv("SALT_BNB_PARTS")) : 512;
+    constexpr int64_t max_parts = 512;
     int64_t parts = (npix + 31) / 32;                       // >= 32 pixels per block (small maps need the blocks), <= 512 blocks
     if (parts > max_parts) parts = max_parts;
     if (parts < 1) parts = 1;
@@ -1459,8 +1426,7 @@ extern "C" int salt_bilinear(const salt_bilinear_args* a, void* stream) {
         const bool rows_ok = !rows_off && v && !a->align_corners && cpv >= 1 && cpv <= 256 && 256 % cpv == 0 &&
                              (int64_t)a->y.W * a->y.cs < (1ll << 30) && (int64_t)a->y.H * a->y.W * a->y.cs < (1ll << 31) && view_pixels(a->y) / a->y.W < (1ll << 31);
         auto row_grid = [](int64_t rows) { const int64_t g = (rows + 7) / 8 * 8; return dim3((unsigned)(g < 16384 ? g : 16384)); };      // a multiple of 8: one row range per XCD
-        static const bool cells_off = getenv("SALT_BILINEAR_CELLS") && atoi(getenv("SALT_BILINEAR_CELLS")) == 0;
-        const bool cells_ok = rows_ok && !cells_off && !a->backward && view_pixels(a->x) < (1ll << 31) && (a->R == 2 || a->R == 4 || a->R == 8 || a->R == 16);
+        const bool cells_ok = rows_ok && !a->backward && view_pixels(a->x) < (1ll << 31) && (a->R == 2 || a->R == 4 || a->R == 8 || a->R == 16);
         if (cells_ok) {
             const int64_t units = view_pixels(a->x) * cpv;
             const dim3 grid((unsigned)((units + 255) / 256 < 65536 ? (units + 255) / 256 : 65536));
@@ -1500,28 +1466,6 @@ extern "C" int salt_bilinear(const salt_bilinear_args* a, void* stream) {
                 else hipLaunchKernelGGL((bilinear_bwd_kernel<T, false, 0>), dim3(ew_blocks(units)), dim3(256), 0, (hipStream_t)stream, a->x, a->y, a->R, a->accumulate, a->align_corners);
             }
         }
-    })
-    SALT_CHECK_LAUNCH();
-    return SALT_OK;
-}
-
-extern "C" int salt_hyper_rows(const salt_hyper_rows_args* a, void* stream) {
-    if (!a || a->nlev < 1 || a->nlev > 4 || !view_ok(a->y)) SALT_FAIL(SALT_E_BADARG, "hyper_rows: bad args");
-    HyperKP k;
-    k.y = a->y; k.nlev = a->nlev; k.ac = a->align_corners;
-    for (int i = 0; i < 4; ++i) { k.x[i] = a->x[i < a->nlev ? i : 0]; k.R[i] = a->R[i < a->nlev ? i : 0]; }
-    for (int i = 0; i < a->nlev; ++i) {
-        const salt_view& x = a->x[i];
-        if (!view_ok(x) || a->R[i] < 1 || a->y.H != x.H * a->R[i] || a->y.W != x.W * a->R[i] || x.B != a->y.B || x.C != a->x[0].C)
-            SALT_FAIL(SALT_E_BADARG, "hyper_rows: level %d does not match the output grid", i);
-    }
-    if (a->y.C != a->nlev * a->x[0].C) SALT_FAIL(SALT_E_BADARG, "hyper_rows: y.C must be nlev * C");
-    SALT_DISPATCH_DTYPE(a->dtype, T, {
-        const int ve = Elem<T>::VE;
-        bool v = vec_ok(a->y, ve) && a->x[0].C % ve == 0;
-        for (int i = 0; i < a->nlev; ++i) v = v && vec_ok(a->x[i], ve);
-        const int64_t units = view_pixels(a->y) * (a->y.C / (v ? ve : 1));
-        EW_LAUNCH(hyper_rows_kernel, T, v, units, (hipStream_t)stream, k);
     })
     SALT_CHECK_LAUNCH();
     return SALT_OK;

@@ -314,7 +314,7 @@ int head_bn_parts(const salt_view& x, int64_t* per) {
 }
 
 inline int head_bn_blocks(int64_t units) {
-    static const int64_t cap = getenv("SALT_HEAD_BLOCKS") ? atoi(getenv("SALT_HEAD_BLOCKS")) : 1024;
+    constexpr int64_t cap = 1024;
     int64_t b = (units + 255) / 256;
     return (int)(b < 1 ? 1 : (b > cap ? cap : b));
 }

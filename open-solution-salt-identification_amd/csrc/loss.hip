@@ -727,9 +727,8 @@ extern "C" int salt_lovasz_hinge(const salt_lovasz_args* a, void* stream) {
     if (!a || !a->logits || !a->target || a->B < 1 || a->P < 0 || !a->ws_keys || !a->ws_vals || !a->loss_per_image || !a->loss)
         SALT_FAIL(SALT_E_BADARG, "lovasz: bad args");
     static const bool plain = getenv("SALT_LOVASZ_PLAIN") != nullptr;       // A/B switch: the non-prefetching kernel
-    static const bool nosplit = getenv("SALT_LOVASZ_NOSPLIT") != nullptr;   // A/B switch: one workgroup per image
     const int S = (a->P + SL - 1) / SL;
-    if (a->ws_split && !plain && !nosplit && a->P >= 2 * SL && S <= SMAXSEG) {
+    if (a->ws_split && !plain && a->P >= 2 * SL && S <= SMAXSEG) {
         hipStream_t st = (hipStream_t)stream;
         LovaszSplit sp{S, a->ws_split, a->ws_split + (int64_t)3 * a->B * S * 256, reinterpret_cast<float*>(a->ws_split + (int64_t)3 * a->B * S * 256 + (int64_t)a->B * S)};
         const dim3 grid(a->B * S);

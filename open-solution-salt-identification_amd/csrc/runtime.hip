@@ -71,35 +71,27 @@ extern "C" int salt_program_run_timed(const salt_program_entry* e, int begin, in
 }
 
 namespace {
-// The fork / join events only order two streams of ONE device: a device-scope release is all they need.  The default event does a
-// system-scope fence (L2 write-back + invalidate for host visibility) when it transitions to recorded.  SALT_EVENT_FLAGS: 0 default
-// events, 1 hipEventDisableSystemFence, 2 hipEventReleaseToDevice.
-unsigned fork_event_flags() {
-    static const int mode = getenv("SALT_EVENT_FLAGS") ? atoi(getenv("SALT_EVENT_FLAGS")) : 0;
-    return mode == 1 ? hipEventDisableSystemFence : (mode == 2 ? hipEventReleaseToDevice : 0u);
-}
+// The fork / join events only order two streams of ONE device.  Default events: creating them with hipEventDisableSystemFence or
+// hipEventReleaseToDevice (device-scope release instead of the system-scope fence) had no measurable effect on the step.
+constexpr unsigned kForkEventFlags = hipEventDisableTiming;
 struct EventPool {
     hipEvent_t ev[2] = {nullptr, nullptr};
-    hipEvent_t ax[4] = {nullptr, nullptr, nullptr, nullptr};   // auxiliary stream: [0] side -> aux hand-over, [1], [2] "slab free again" ring, [3] main -> aux
     int ensure() {
         for (int i = 0; i < 2; ++i)
-            if (!ev[i] && hipEventCreateWithFlags(&ev[i], hipEventDisableTiming | fork_event_flags()) != hipSuccess) return -1;
-        for (int i = 0; i < 4; ++i)
-            if (!ax[i] && hipEventCreateWithFlags(&ax[i], hipEventDisableTiming | fork_event_flags()) != hipSuccess) return -1;
+            if (!ev[i] && hipEventCreateWithFlags(&ev[i], kForkEventFlags) != hipSuccess) return -1;
         return 0;
     }
 };
 thread_local EventPool g_events;
-thread_local hipStream_t g_aux_stream = nullptr;   // salt_set_aux_stream: where stream-tag-4 entries run (NULL: on the side stream)
 thread_local hipEvent_t g_fork_event = nullptr;
-const bool g_fork_handoff_env = !getenv("SALT_NO_FORK_HANDOFF");
 thread_local bool g_capturing = false;         // hipExtLaunchKernelGGL stop events are not capturable: plain event forks while a graph records
-#define g_fork_handoff (g_fork_handoff_env && !g_capturing)
+// Side-stream entries are issued behind one fork per this many groups.  Eager run: 1, a fork per layer that rides on the producing
+// kernel's completion signal (6.18 ms per step; explicit event record 6.25, one fork per two layers 6.30).  While a hipGraph is captured: 8 (a
+// cross-stream edge of a replayed graph stalls the main branch ~10 us, a live event does not).
+constexpr int kForkEveryEager = 1, kForkEveryGraph = 8;
 }  // namespace
 
 hipEvent_t salt_take_fork_event() { hipEvent_t e = g_fork_event; g_fork_event = nullptr; return e; }
-
-extern "C" int salt_set_aux_stream(void* stream) { g_aux_stream = (hipStream_t)stream; return SALT_OK; }
 
 extern "C" int salt_program_run_streams(const salt_program_entry* e, int begin, int end, void* main_stream, void* side_stream) {
     return salt_program_run_streams_ex(e, begin, end, main_stream, side_stream, 1);
@@ -112,7 +104,7 @@ extern "C" int salt_program_run_streams_ex(const salt_program_entry* e, int begi
 extern "C" int salt_event_create(void** out) {
     if (!out) SALT_FAIL(SALT_E_BADARG, "event_create: null");
     hipEvent_t ev = nullptr;
-    const hipError_t err = hipEventCreateWithFlags(&ev, hipEventDisableTiming | fork_event_flags());
+    const hipError_t err = hipEventCreateWithFlags(&ev, kForkEventFlags);
     if (err != hipSuccess) SALT_FAIL((int)err, "hipEventCreate: %s", hipGetErrorString(err));
     *out = ev;
     return SALT_OK;
@@ -135,37 +127,11 @@ extern "C" int salt_program_run_streams_marks(const salt_program_entry* e, int b
     if (!e || begin < 0 || end < begin) SALT_FAIL(SALT_E_BADARG, "program: bad range");
     if (g_events.ensure()) SALT_FAIL(SALT_E_BADARG, "hipEventCreate failed");
     hipStream_t ms = (hipStream_t)main_stream, ss = (hipStream_t)side_stream;
-    static const bool one_stream = getenv("SALT_ONE_STREAM") != nullptr;      // A/B: every entry on the main stream, in program order
-    if (one_stream) {
-        (void)hipEventRecord(g_events.ev[1], ss);                 // whatever the caller enqueued on the side stream before (weight packs)
-        (void)hipStreamWaitEvent(ms, g_events.ev[1], 0);
-        int b0 = begin;
-        for (int m = 0; m < nmarks; ++m) {
-            const int pos = marks[m] < b0 ? b0 : (marks[m] > end ? end : marks[m]);
-            const int rc = salt_program_run_range(e, b0, pos, main_stream);
-            if (rc) return rc;
-            (void)hipEventRecord((hipEvent_t)ev_main[m], ms);
-            (void)hipEventRecord((hipEvent_t)ev_side[m], ss);
-            b0 = pos;
-        }
-        return salt_program_run_range(e, b0, end, main_stream);
-    }
     bool main_dirty = true, side_used = false;       // main_dirty: main has work the side stream has not been ordered after
-    // Fork coalescing (SALT_FORK_EVERY = K > 1): side-stream entries are held back until K groups of them are pending, then issued
+    // Fork coalescing (fork_every = K > 1): side-stream entries are held back until K groups of them are pending, then issued
     // behind ONE fork.  A held entry only ever runs later than its program position, so its inputs are complete; every cross-queue
     // dependency costs the main queue ~10 us of dispatch stall (rocprofv3 timeline), a held entry costs the side stream its head start.
-    static const int fork_eager = getenv("SALT_FORK_EVERY") ? atoi(getenv("SALT_FORK_EVERY")) : 1;
-    static const int fork_graph = getenv("SALT_FORK_EVERY_GRAPH") ? atoi(getenv("SALT_FORK_EVERY_GRAPH")) : 8;
-    const int fork_every = g_capturing ? fork_graph : fork_eager;   // a cross-stream edge of a replayed graph stalls the main branch ~10 us, a live event does not
-    // SALT_FORK_PLAN="a,b,c": group counts of the first flushes of a range (then fork_every): A/B of the flush pattern
-    static int plan[16], nplan = -1;
-    if (nplan < 0) {
-        nplan = 0;
-        if (const char* e = getenv("SALT_FORK_PLAN")) {
-            while (*e && nplan < 16) { plan[nplan++] = atoi(e); while (*e && *e != ',') ++e; if (*e == ',') ++e; }
-        }
-    }
-    int nflush = 0;
+    const int fork_every = g_capturing ? kForkEveryGraph : kForkEveryEager;
     int pending[64], npending = 0, groups = 0;
     bool prev_side = false;
     auto flush = [&]() -> int {
@@ -180,19 +146,9 @@ extern "C" int salt_program_run_streams_marks(const salt_program_entry* e, int b
             const int rc = e[j].fn(e[j].args, side_stream);
             if (rc) { char prev[400]; strncpy(prev, g_err, sizeof(prev) - 1); prev[sizeof(prev) - 1] = 0; salt_set_error("program entry %d failed (%d): %s", j, rc, prev); return rc; }
         }
-        npending = 0; groups = 0; side_used = true; ++nflush;
+        npending = 0; groups = 0; side_used = true;
         return 0;
     };
-    // Auxiliary stream (round 6).  Entries tagged 4 - the weight-gradient slab reductions - run on a THIRD stream, each behind the side
-    // entry in front of it (its conv_wgrad) and beside the NEXT conv_wgrad, which writes the other of two alternating slab buffers; the
-    // side entry that reuses a slab waits for the reduction that read it two reductions ago.  Entries tagged 5 - the optimizer's update
-    // of a parameter range whose gradients are final at that position (FusedAdam.backward_program) - run there behind everything both
-    // queues were given so far.  Only in the plain eager two-stream run (no marks, no capture, join at the end, a fork per group);
-    // otherwise tags 4 and 5 are the side stream (same order guarantees, no concurrency).
-    hipStream_t as = g_aux_stream;
-    const bool use_aux = as && as != ms && as != ss && !g_capturing && nmarks == 0 && join_at_end && fork_every <= 1;
-    int naux = 0;
-    bool aux_used = false;
     int mk = 0;
     auto do_marks = [&](int i) -> int {          // every mark at position i: both queues' events, behind everything issued so far
         while (mk < nmarks && marks[mk] <= i) {
@@ -205,26 +161,7 @@ extern "C" int salt_program_run_streams_marks(const salt_program_entry* e, int b
     };
     for (int i = begin; i < end; ++i) {
         if (mk < nmarks) { const int rc = do_marks(i); if (rc) return rc; }
-        if (use_aux && e[i].stream == 4) {
-            (void)hipEventRecord(g_events.ax[0], ss);            // behind the conv_wgrad that filled the slab
-            (void)hipStreamWaitEvent(as, g_events.ax[0], 0);
-            const int rc = e[i].fn(e[i].args, as);
-            if (rc) { char prev[400]; strncpy(prev, g_err, sizeof(prev) - 1); prev[sizeof(prev) - 1] = 0; salt_set_error("program entry %d failed (%d): %s", i, rc, prev); return rc; }
-            (void)hipEventRecord(g_events.ax[1 + (naux & 1)], as);
-            ++naux; aux_used = true;
-            continue;
-        }
-        if (use_aux && e[i].stream == 5) {                       // behind BOTH queues (an optimizer update of parameters whose gradients are final here)
-            (void)hipEventRecord(g_events.ax[3], ms); (void)hipStreamWaitEvent(as, g_events.ax[3], 0);
-            (void)hipEventRecord(g_events.ax[0], ss); (void)hipStreamWaitEvent(as, g_events.ax[0], 0);
-            const int rc = e[i].fn(e[i].args, as);
-            if (rc) { char prev[400]; strncpy(prev, g_err, sizeof(prev) - 1); prev[sizeof(prev) - 1] = 0; salt_set_error("program entry %d failed (%d): %s", i, rc, prev); return rc; }
-            aux_used = true;
-            continue;
-        }
-        const bool side = e[i].stream == 1 || e[i].stream == 4 || e[i].stream == 5;
-        if (use_aux && side && i + 1 < end && e[i + 1].stream == 4 && naux >= 2)
-            (void)hipStreamWaitEvent(ss, g_events.ax[1 + (naux & 1)], 0);      // the slab this launch writes was read by the reduction two back
+        const bool side = e[i].stream == 1;
         if (fork_every > 1) {
             if (side) {
                 if (npending == 64) { const int rc = flush(); if (rc) return rc; }
@@ -232,12 +169,11 @@ extern "C" int salt_program_run_streams_marks(const salt_program_entry* e, int b
                 continue;
             }
             if (prev_side) { ++groups; prev_side = false; }
-            if (groups >= (nflush < nplan ? plan[nflush] : fork_every) || e[i].stream == 2 || e[i].stream == 3) { const int rc = flush(); if (rc) return rc; }
+            if (groups >= fork_every || e[i].stream == 2 || e[i].stream == 3) { const int rc = flush(); if (rc) return rc; }
         }
         if ((e[i].stream == 2 && side_used) || e[i].stream == 3) {   // a main-stream entry that consumes side-stream results:
             (void)hipEventRecord(g_events.ev[1], ss);                 // 2 = produced inside this range, 3 = enqueued on the side
             (void)hipStreamWaitEvent(ms, g_events.ev[1], 0);          // stream before the call (data-gradient weight packs)
-            if (aux_used) { (void)hipEventRecord(g_events.ax[0], as); (void)hipStreamWaitEvent(ms, g_events.ax[0], 0); }
             side_used = false;
         }
         if (side && main_dirty) {
@@ -245,7 +181,7 @@ extern "C" int salt_program_run_streams_marks(const salt_program_entry* e, int b
             (void)hipStreamWaitEvent(ss, g_events.ev[0], 0);
             main_dirty = false;
         }
-        const bool handoff = g_fork_handoff && fork_every <= 1 && !side && i + 1 < end && e[i + 1].stream == 1;
+        const bool handoff = !g_capturing && fork_every <= 1 && !side && i + 1 < end && e[i + 1].stream == 1;
         if (handoff) g_fork_event = g_events.ev[0];        // the entry may attach it to its last launch as the stop event
         const int rc = e[i].fn(e[i].args, side ? side_stream : main_stream);
         const bool taken = handoff && g_fork_event == nullptr;
@@ -265,11 +201,6 @@ extern "C" int salt_program_run_streams_marks(const salt_program_entry* e, int b
     if (side_used && join_at_end) {
         (void)hipEventRecord(g_events.ev[1], ss);
         (void)hipStreamWaitEvent(ms, g_events.ev[1], 0);
-    }
-    if (aux_used) {                                              // (use_aux implies join_at_end)
-        (void)hipEventRecord(g_events.ax[0], as);
-        (void)hipStreamWaitEvent(ms, g_events.ax[0], 0);
-        (void)hipStreamWaitEvent(ss, g_events.ax[0], 0);          // the next range's first slab writers
     }
     return SALT_OK;
 }
@@ -353,7 +284,6 @@ extern "C" int salt_abi_struct_sizes(int* out, int n) {
     (int)sizeof(salt_conv_args),
     (int)sizeof(salt_conv_wgrad_args),
     (int)sizeof(salt_wgrad_reduce_args),
-    (int)sizeof(salt_wgrad_reduce_batched_args),
     (int)sizeof(salt_pack_conv_weight_args),
     (int)sizeof(salt_pack_batched_args),
     (int)sizeof(salt_conv_first_args),
@@ -374,7 +304,6 @@ extern "C" int salt_abi_struct_sizes(int* out, int n) {
     (int)sizeof(salt_maxpool2_bwd_args),
     (int)sizeof(salt_avgpool2_args),
     (int)sizeof(salt_bilinear_args),
-    (int)sizeof(salt_hyper_rows_args),
     (int)sizeof(salt_hyper_stencil_args),
     (int)sizeof(salt_pad_fold_args),
     (int)sizeof(salt_pad_fold_strip_args),

@@ -12,11 +12,11 @@ buffers that their producers write in place, so ``torch.cat`` never copies anyth
 PyTorch is used for device memory (tensors), streams and nothing else on this path.
 """
 import ctypes
-import os
 
 import numpy as np
 import torch
 
+from . import switches
 from ._abi import OP_FUNCS, STRUCTS, SaltError, check, fill, lib
 
 DT_CODE = {'f32': 0, 'bf16': 1}
@@ -29,7 +29,7 @@ def fwd_bn_fold():
     only reader is ONE 3x3 convolution runs in that convolution's loader (salt_conv_args.in_*; forward values bit-identical, tested).
     The weight-gradient kernels cannot re-derive the activation, so such a graph is FORWARD-ONLY: its backward closure raises instead
     of computing a wrong gradient."""
-    return os.environ.get('SALT_FWD_BN_FOLD', '0') not in ('', '0')
+    return switches.get('SALT_FWD_BN_FOLD')
 
 
 def _round_up(v, m):
@@ -41,17 +41,6 @@ class Scratch:
 
     def __init__(self, name, nbytes):
         self.name, self.nbytes = name, int(nbytes)
-
-
-_AUX_STREAMS = {}
-
-
-def _aux_stream(side):
-    """The auxiliary stream that goes with a side stream (salt_set_aux_stream): one per side stream, created on first use."""
-    a = _AUX_STREAMS.get(side.cuda_stream)
-    if a is None:
-        a = _AUX_STREAMS[side.cuda_stream] = torch.cuda.Stream(device=side.device)
-    return a
 
 
 class Program:
@@ -66,7 +55,6 @@ class Program:
         self.patches = []      # (struct, path, Scratch)
         self._entries = None
         self.marks = {}
-        self._has_aux = None           # any stream-tag-4 entry (slab reductions on the auxiliary stream)?
         self._pre_run = None           # callable(stream, begin) run before the entries are issued (Graph.finalize: shard hygiene)
         self._post_run = None          # callable(begin, end) after they were issued
 
@@ -141,10 +129,6 @@ class Program:
             rc = lib.salt_program_run_streams_marks(ctypes.cast(self._entries, ctypes.c_void_p), begin, end, st, ctypes.c_void_p(side.cuda_stream),
                                                     1 if join else 0, marks[0], marks[1], marks[2], marks[3])
         elif side is not None:
-            if self._has_aux is None:
-                self._has_aux = 4 in self.streams or 5 in self.streams
-            if self._has_aux:
-                lib.salt_set_aux_stream(None if os.environ.get('SALT_NO_AUX_STREAM') else ctypes.c_void_p(_aux_stream(side).cuda_stream))
             rc = lib.salt_program_run_streams_ex(ctypes.cast(self._entries, ctypes.c_void_p), begin, end, st, ctypes.c_void_p(side.cuda_stream),
                                                  1 if join else 0)
         else:
@@ -347,8 +331,6 @@ class Graph:
         self._scratch_sfx = ''
         # fp64 statistics shards of the train-mode BatchNorm layers (SALT_BN_FIN=2): slices of one arena per program, cleared by ONE
         # salt_zero at the head of the program
-        self._pending_reduces, self._deferred_params, self._pending_bytes, self._reduce_batches = [], [], 0, []
-        self._n_slab = 0
         self._fin_bytes = {'fwd': 0, 'bwd': 0}
         self._fin_patches = []                   # (struct, field, 'fwd' | 'bwd', byte offset)
         self._fin_zero = {}
@@ -404,18 +386,10 @@ class Graph:
                     obj = getattr(obj, a)
                 setattr(obj, path[-1], self.scratch[sc.name].data_ptr())
             prog.finalize()
-        # device tables of the batched slab reductions (the jobs' slab pointers were patched just above)
-        import numpy as np
-        for op, jobs, blocks in self._reduce_batches:
-            table = torch.frombuffer(bytearray(b''.join(bytes(j) for j in jobs)), dtype=torch.uint8).to(self.device)
-            pref = torch.from_numpy(np.concatenate([[0], np.cumsum(blocks)]).astype(np.int32)).to(self.device)
-            self.keep += [table, pref]
-            fill(op, jobs=table.data_ptr(), job_block0=pref.data_ptr())
         # ONE arena for the fp64 statistics shards of both programs, cleared by ONE salt_zero at the head of the FORWARD program (a
         # training step runs forward -> loss -> backward exactly once each; the backward program's own clear - a 6 us launch at the
         # head of the critical queue - is dropped: its salt_zero entry stays in the program with 0 bytes, which launches nothing).
-        # SALT_SPLIT_ZERO=1: each program clears its own half (for callers that replay a backward program on its own).
-        split = bool(os.environ.get('SALT_SPLIT_ZERO')) or 'fwd' not in self._fin_zero
+        split = 'fwd' not in self._fin_zero
         nbf, nbb = self._fin_bytes['fwd'], self._fin_bytes['bwd']
         if self._fin_zero:
             arena = self.alloc((max((nbf + nbb) // 8, 1),), torch.float64)
@@ -459,51 +433,10 @@ class Graph:
             self._fin_patches.append((st, field, which, off))
         return off
 
-    def _gp(self, param, deferred=False):
-        """Gradient pointer of a parameter; remembers that the current backward closure finalises it (``deferred``: the NEXT batched
-        slab reduction does - Graph._flush_reduces records the position)."""
-        (self._deferred_params if deferred else self._touched).append(param)
+    def _gp(self, param):
+        """Gradient pointer of a parameter; remembers that the current backward closure finalises it."""
+        self._touched.append(param)
         return self.engine.grad_ptr(param)
-
-    # ------------------------------------------------------------------ batched weight-gradient slab reductions (round 6)
-    def _reduce_batching(self):
-        """SALT_WGRAD_BATCH_MB=<n> (OPT-IN; default 0 = one salt_wgrad_reduce launch per layer): the slab reductions of consecutive layers
-        are collected - every layer then needs its OWN slab region (0.9 GB for the ResNet34 U-Net instead of one shared 25 MB workspace) -
-        and issued as ONE salt_wgrad_reduce_batched launch whenever the collected gradients reach n megabytes or 16 layers.  Built for
-        VERDICT r5 #3 and measured SLOWER on the step (same box: 5.06 ms per layer / 5.13 with per-layer slabs but a launch per layer /
-        5.16 at 4 MB / 5.19 at 40 MB, profiles/r06_wgrad_batch2_ab.txt): the shared 25 MB workspace is written and read back out of the
-        256 MB Infinity Cache, per-layer regions go to HBM - the slab round trip the counters show is cache traffic, not HBM time."""
-        return float(os.environ.get('SALT_WGRAD_BATCH_MB', '0')) if self.train else 0.0
-
-    def _queue_reduce(self, fields, weight, nbytes):
-        """one layer's reduction: argument struct now, launch with the next batch"""
-        S = STRUCTS['salt_wgrad_reduce_args']()
-        self._n_slab = getattr(self, '_n_slab', 0) + 1
-        sc = Scratch('wgrad#%d' % self._n_slab, nbytes)
-        plain = dict(fields)
-        plain['grad'] = self._gp(weight, deferred=True) + plain.pop('grad_off', 0)
-        fill(S, **plain)
-        self.bwd.patches.append((S, ('partials',), sc))
-        self.keep.append(S)
-        self._pending_reduces.append(S)
-        self._pending_bytes += plain['ntaps'] * plain['Ca'] * plain['Cb'] * 4                      # bytes of gradient this job finishes
-        if self._pending_bytes >= self._reduce_batching() * 1e6 or len(self._pending_reduces) >= 16:
-            self._flush_reduces()
-        return sc
-
-    def _flush_reduces(self):
-        if not getattr(self, '_pending_reduces', None):
-            return
-        jobs = self._pending_reduces
-        blocks = [lib.salt_wgrad_reduce_job_blocks(ctypes.byref(j)) for j in jobs]
-        if min(blocks) < 0:
-            raise SaltError('wgrad_reduce_batched: bad job')
-        op = self.bwd.add('wgrad_reduce_batched', stream=1, jobs=1, job_block0=1, njobs=len(jobs), total_blocks=int(sum(blocks)))
-        self._reduce_batches.append((op, jobs, blocks))
-        for p in self._deferred_params:
-            off, n = self.engine.grad_range(p)
-            self.grad_ready.append((off, n, len(self.bwd.ops)))
-        self._pending_reduces, self._deferred_params, self._pending_bytes = [], [], 0
 
     def build_backward(self):
         """Emit the backward program (reverse tape order).  Also records, per parameter, the program position
@@ -518,7 +451,6 @@ class Graph:
             for p in self._touched:
                 off, n = self.engine.grad_range(p)
                 self.grad_ready.append((off, n, len(self.bwd.ops)))
-        self._flush_reduces()
         self.tape = []
         for b in getattr(self, '_bias_bufs', []):        # every folded channel-SE term must have met its bn_bwd, or x.grad is incomplete
             if getattr(b, 'grad_bias', None) is not None:
@@ -538,7 +470,7 @@ class Graph:
         """Can a [B,H,W,C] buffer that feeds ONE replicate-padded 3x3 convolution (the hypercolumn -> final Conv2dBnRelu,
         architectures/unet.py:101-109) be stored as C / pc dense planes?  Yes iff the library runs the forward launch on conv_ls_kernel
         (x_plane) and, in train mode, the data gradient on conv_ws_kernel (y_plane) and accepts q_plane for the weight gradient."""
-        if self.dtype != 'bf16' or os.environ.get('SALT_NO_PLANAR') or C % pc or pc % self.ve:
+        if self.dtype != 'bf16' or switches.get('SALT_NO_PLANAR') or C % pc or pc % self.ve:
             return False
         if self.train and self._fin_mode() != 2:
             return False                               # the per-tile partials protocols run on conv_mfma_kernel only
@@ -597,10 +529,6 @@ class Graph:
         stream = fold.pop('stream', None)
         kw.update(fold)
         kw.update(self._plane_args(x_view, y_view))
-        if prog is self.bwd and not (cfg >> 8) and os.environ.get('SALT_CONV_WPX_BWD'):
-            # A/B: workgroups per XCD of the whole-CU kernels (conv_ws / conv_ls) in BACKWARD, where they share the chip with the
-            # weight-gradient stream (a whole-CU workgroup waits for a CU the other stream has left completely)
-            kw['cfg'] = cfg | (int(os.environ['SALT_CONV_WPX_BWD']) << 8)
         return prog.add('conv', stream=stream, **kw)
 
     @staticmethod
@@ -629,7 +557,7 @@ class Graph:
         """SALT_BN_FIN: how the train-mode BatchNorm sums travel.  2 (default): fp64 shard atomics in the producing launch, finalized
         by the consumer (salt_affine_act / the apply pass of salt_bn_bwd); 1: the same shards, finalized in the producing launch by the
         workgroup that draws the last ticket; 0: per-tile partials + separate finalize launches."""
-        return int(os.environ.get('SALT_BN_FIN', '2'))
+        return switches.get('SALT_BN_FIN')
 
     @classmethod
     def _fin_on(cls):
@@ -711,9 +639,9 @@ class Graph:
         partials, ready = Scratch('bn_bwd', nparts * 2 * C * 4), 0
         wr = out.buf.grad_writers
         # (round 6: only the LAST writer has to cover exactly this slice - earlier writers of the same buffer, e.g. the decoder's data
-        #  gradient over the whole concat buffer an encoder output lives in, are complete before it runs.  SALT_BNB_STRICT=1: round 5's rule)
+        #  gradient over the whole concat buffer an encoder output lives in, are complete before it runs)
         same = (lambda w_: (w_[0], w_[1]) == (out.c0, out.C))
-        ok_wr = bool(wr) and same(wr[-1]) and (all(same(w_) for w_ in wr) or not os.environ.get('SALT_BNB_STRICT'))
+        ok_wr = bool(wr) and same(wr[-1])
         sec = wr[-1][2] if (ok_wr and isinstance(wr[-1][2], tuple) and wr[-1][2][0] == 'sec') else None
         if sec is not None and not relu and res is None and self._fin_mode() == 2:
             # round 6: dL/d(out) is the dres the main branch's bn_bwd wrote (this is a projection shortcut's BatchNorm): that apply pass
@@ -722,8 +650,7 @@ class Graph:
             self.bwd.set_fields(producer, sec_y=y.view(), sec_mean=w['mean'].data_ptr(), sec_invstd=w['invstd'].data_ptr())
         elif sec is not None:
             pass                                   # (a shape the secondary sums do not cover: this layer keeps its reduction pass)
-        elif (ok_wr and wr[-1][2] is not None and C % self.ve == 0
-                and (res is None or not os.environ.get('SALT_NO_BNB_RES')) and not os.environ.get('SALT_NO_BNB_FUSE')):
+        elif ok_wr and wr[-1][2] is not None and C % self.ve == 0:
             # the LAST writer of dL/d(out) is a plain data-gradient launch (it completes the gradient: earlier writers of the same
             # slice were accumulated): its epilogue also reduces this layer's BatchNorm-backward sums over its pixel tiles
             # (salt_conv_args.bnb_*), and bn_bwd skips its own pass over da and y.  With a residual the mask comes from `out`.
@@ -765,7 +692,7 @@ class Graph:
             out.buf.grad_bias = None
         if res is not None and acc_res == 0 and ready == 3 and self._fin_mode() == 2 and C % self.ve == 0 and 256 % (C // self.ve) == 0 \
                 and getattr(res.buf, 'bn_train_out', None) == (res.c0, res.C) and bias is None and not res.plane_stride() \
-                and os.environ.get('SALT_BNB_SEC', '1') != '0':
+                and switches.get('SALT_BNB_SEC'):
             res.buf.grad_writers[-1][2] = ('sec', s2)          # the residual's own BatchNorm (a projection shortcut) may ask this pass for its sums
         if sec is not None and ready == 3 and producer is sec[1]:
             self._fin_slot('bwd', 8 * 2 * C, (producer, 'sec_acc'), (s2, 'fin_acc'))
@@ -842,7 +769,7 @@ class Graph:
             if res is None:
                 self._conv_launch(self.fwd, x.view(), pk.data_ptr(), td, stride, pad_mode, out.view(), OH, OW, bias=bias,
                                   scale=w['scale'].data_ptr(), shift=w['shift'].data_ptr(), relu=int(relu))
-            elif Cout % self.ve == 0 and not os.environ.get('SALT_NO_RES_FOLD'):
+            elif Cout % self.ve == 0 and not switches.get('SALT_NO_RES_FOLD'):
                 # eval-mode residual block: folded BN + identity add + ReLU all in the convolution's epilogue (salt_conv_args.res) - the
                 # same values as the separate affine_act pass below, bit for bit, without its launch and its trip over `out`
                 if getattr(res, 'on_side', False):
@@ -896,7 +823,7 @@ class Graph:
 
     def hyper_head_ok(self, C, hconv):
         """Can salt_hyper_stencil's epilogue apply the logit head ``hconv`` (eval; saltnet.h: 1..2 classes, 1 / 2 / 4 / 8 channel blocks)?"""
-        if self.train or os.environ.get('SALT_HYPER_HEAD', '1') == '0':
+        if self.train:
             return False
         co, ci, kh, kw = hconv.weight.shape
         return (kh, kw) == (1, 1) and ci == C and 1 <= co <= 2 and C in ((64, 128, 256) if self.dtype == 'f32' else (64, 128, 256, 512))
@@ -905,7 +832,7 @@ class Graph:
         """TRAIN mode: can the final block's BatchNorm apply + ReLU and the logit head ``hconv`` run as one pass over the raw convolution
         output (salt_head_bn / salt_head_bn_bwd; saltnet.h: <= 4 classes, C a power-of-two number of 16-byte pieces <= 64, consumer-side
         statistics shards)?  SALT_HEAD_BN=0 keeps the separate launches (A/B)."""
-        if not self.train or self._fin_mode() != 2 or os.environ.get('SALT_HEAD_BN', '1') == '0':
+        if not self.train or self._fin_mode() != 2 or not switches.get('SALT_HEAD_BN'):
             return False
         co, ci, kh, kw = hconv.weight.shape
         cpv = C // self.ve
@@ -1051,21 +978,16 @@ class Graph:
         """dW = sum_p P[p,:]^T Q[p*q_step + tap, :] -> weight.grad (reference layout [Ca][Cb][KH][KW]).
         ``b_slice`` = (first, row stride): Q covers only channels [first, first + Cb) of the weight's second axis (salt_wgrad_reduce_args.ldb).
         ``tapgemm`` = (rows, [(kh, kw)]): a 1x1 launch whose P channels are t * rows + a (salt_wgrad_reduce_args.a_mod) - Graph.hyper_level."""
-        batching = self._reduce_batching() > 0
-        aux = not batching and os.environ.get('SALT_REDUCE_AUX', '0') != '0'
-        gw = self.engine.grad_ptr(weight) if batching else self._gp(weight)
-        goff = 0
+        gw = self._gp(weight)
         Ca, Cb = p_view.C, q_view.C
         extra = {}
         if b_slice is not None:
-            goff = 4 * b_slice[0] * KH * KW
-            gw += goff
+            gw += 4 * b_slice[0] * KH * KW
             extra['ldb'] = b_slice[1]
         if tapgemm is not None:
             assert len(taps_dydx) == 1 and Ca == tapgemm[0] * len(tapgemm[1])
             extra['a_mod'] = tapgemm[0]
             taps_khkw = list(tapgemm[1])
-        first = True
         for i in range(0, len(taps_dydx), 9 if len(taps_dydx) != 16 else 4):
             chunk = list(range(i, min(i + (9 if len(taps_dydx) != 16 else 4), len(taps_dydx))))
             S = STRUCTS['salt_conv_wgrad_args']()
@@ -1076,24 +998,13 @@ class Graph:
             if ns < 0:
                 raise SaltError('wgrad plan failed: ' + lib.salt_last_error().decode())
             nbytes = ns * len(chunk) * Ca * Cb * 4
-            # two alternating slab workspaces: the reduction of pair k runs on the auxiliary stream beside conv_wgrad k + 1 (stream tag 4,
-            # runtime.hip); both stay in the Infinity Cache (2 x <= 25 MB)
-            slab = 'wgrad'
-            if aux:
-                slab = 'wgrad_' + 'ab'[self._n_slab & 1]
-                self._n_slab += 1
-            wg_op = self.bwd.add('conv_wgrad', stream=1, dtype=self.dt, p=p_view, q=q_view, ntaps=len(chunk), tap_dy=[taps_dydx[j][0] for j in chunk],
+            self.bwd.add('conv_wgrad', stream=1, dtype=self.dt, p=p_view, q=q_view, ntaps=len(chunk), tap_dy=[taps_dydx[j][0] for j in chunk],
                                  tap_dx=[taps_dydx[j][1] for j in chunk], q_step=q_step, pad_mode=pad_mode,
-                                 partials=None if batching else Scratch(slab, nbytes), nsplit=ns, q_plane=qp)
+                         partials=Scratch('wgrad', nbytes), nsplit=ns, q_plane=qp)
             rt = range(len(taps_khkw)) if tapgemm is not None else chunk
             rfields = dict(nsplit=ns, ntaps=len(chunk), Ca=Ca, Cb=Cb, KH=KH, KW=KW, tap_kh=[taps_khkw[j][0] for j in rt],
                            tap_kw=[taps_khkw[j][1] for j in rt], accumulate=0, **extra)
-            if batching:
-                sc = self._queue_reduce(dict(rfields, grad_off=goff), weight, nbytes)
-                self.bwd.set_fields(wg_op, partials=sc)
-            else:
-                self.bwd.add('wgrad_reduce', stream=4 if aux else 1, partials=Scratch(slab, nbytes), grad=gw, **rfields)
-            first = False
+            self.bwd.add('wgrad_reduce', stream=1, partials=Scratch('wgrad', nbytes), grad=gw, **rfields)
 
     def _bwd_pack_tag(self):
         """Stream tag of a data-gradient convolution: the first one of the backward program joins the side stream, where the
@@ -1111,14 +1022,7 @@ class Graph:
             Hp, Wp = x.H + top, x.W + right
             td = [(-(t[2]) - top, -(t[3])) for t in taps]
             acc = x.grad_state()
-            if os.environ.get('SALT_FOLD_FULL'):            # A/B: gradient on the extended grid in scratch, then a full fold pass
-                ext = shaped_view(0, x.B, Hp, Wp, x.C, _round_up(x.C, self.ve))
-                nbytes = x.B * Hp * Wp * ext.cs * self._es()
-                self._conv_launch(self.bwd, dy.gview(), pk.data_ptr(), td, 1, 0, (ext, Scratch('dgrad_ext', nbytes)), Hp, Wp, stream=self._bwd_pack_tag())
-                self.bwd.add('pad_fold', dtype=self.dt, xp=(ext, Scratch('dgrad_ext', nbytes)), top=top, bottom=0, left=0, right=right,
-                             x=x.gview(), accumulate=acc)
-                return
-            if x.C % self.ve == 0 and not os.environ.get('SALT_FOLD_STRIP'):
+            if x.C % self.ve == 0:
                 # fused fold: the launch tiles the extended grid so that every pad-ring pixel shares a tile with the edge pixel it folds
                 # onto; the epilogue sums them from the staged tile - no strip, no second pass, and (a plain store of the complete
                 # gradient) the launch can carry the BatchNorm-backward sums of x's producer
@@ -1155,7 +1059,7 @@ class Graph:
             pk_t, elems = eng.packed_phases(conv, phase_taps, transposed=True, bwd=True)
             s = self._conv_launch(self.bwd, dy.gview(), pk_t.data_ptr(), td_u, 1, 0, x.gview(), x.H // 2, x.W // 2, out_step=2, accumulate=acc,
                                   nphase=4, w_phase_elems=elems, stream=self._bwd_pack_tag())
-            if not x.plane_stride() and not os.environ.get('SALT_NO_BNB_PHASE'):
+            if not x.plane_stride():
                 x.buf.grad_writers[-1][2] = s      # all four parities of an even grid: every pixel once - can carry the BatchNorm-backward sums (round 6)
             return
         if any(not sel for _, _, sel in phases) and not acc:
@@ -1174,7 +1078,7 @@ class Graph:
         """per_phase: for each of the 4 output-parity phases a list of ((dy, dx), (kh, kw)).  -> (unified tap offsets, per-phase
         (kh, kw) | None lists) when the phases can share one launch (even grid, <= 9 distinct offsets, at least two non-empty
         phases), else None."""
-        if os.environ.get('SALT_NO_PHASE_FUSE') or H % 2 or W % 2:
+        if H % 2 or W % 2:
             return None
         offs = sorted({o for ph in per_phase for o, _ in ph})
         if not offs or len(offs) > 9 or sum(1 for ph in per_phase if ph) < 2:
@@ -1492,22 +1396,6 @@ class Graph:
             self.tape.append(backward)
         return out
 
-    def hyper_rows(self, xs, Rs, out):
-        """All up-sampled hypercolumn levels in ONE pass: out (a slice of len(xs) * C channels) <- [up(x_k, R_k)] (salt_hyper_rows); the
-        adjoints stay one salt_bilinear launch per level."""
-        ac = int(bool(getattr(getattr(self.engine, 'module', None), 'align_corners', False)))
-        assert out.C == len(xs) * xs[0].C and all(x.C == xs[0].C for x in xs)
-        self.fwd.add('hyper_rows', dtype=self.dt, nlev=len(xs), x=[x.view() for x in xs], R=list(Rs), y=out.view(), align_corners=ac)
-        if self.train:
-            def backward():
-                for k in reversed(range(len(xs))):
-                    x, R, o = xs[k], Rs[k], out.slice(k * xs[0].C, xs[0].C)
-                    acc = x.grad_state()
-                    tmp = Scratch('bilinear', x.B * o.H * x.W * _round_up(x.C, self.ve) * self._es()) if R >= 4 else None
-                    self.bwd.add('bilinear', dtype=self.dt, x=x.gview(), y=o.gview(), R=R, backward=1, accumulate=acc, tmp=tmp, align_corners=ac)
-            self.tape.append(backward)
-        return out
-
     def add(self, a, b, out=None, name=''):
         if out is None:
             out = self.new_act(a.B, a.H, a.W, a.C, name)
@@ -1555,11 +1443,11 @@ class Graph:
             out = self.new_act(x.B, x.H, x.W, x.C, name)
         l1, l2, cs = cse.fc[0], cse.fc[2], sse.fc
         R, C, B = l1.weight.shape[0], x.C, x.B
-        shards = self.train and self._fin_mode() == 2 and os.environ.get('SALT_SE_SHARDS', '1') != '0'   # per-image sums through the zeroed fp64 arena (see _fin_slot)
+        shards = self.train and self._fin_mode() == 2 and switches.get('SALT_SE_SHARDS')   # per-image sums through the zeroed fp64 arena (see _fin_slot)
         # round 6: x = relu(bn(conv)) whose ONLY reader is this operator (base.DecoderBlock: conv2 -> scSE, architectures/base.py:60-85) -
         # the affine_act that would store it is taken back out of the program and the scSE kernels apply BatchNorm + ReLU to the raw
         # convolution output on the way in (salt_scse_args.in_fin); backward reads the raw output through the same transform
-        taken = self._take_act_op(x) if (shards and os.environ.get('SALT_SE_IN_BN', '1') != '0') else None
+        taken = self._take_act_op(x) if (shards and switches.get('SALT_SE_IN_BN')) else None
         if taken is not None:
             sa, Fbn = taken
             xv_ = sa.y                                   # the raw convolution output; never x.view(): the activation has no storage reader
@@ -1588,7 +1476,7 @@ class Graph:
                 gp = self._gp
                 # round 6: the FC parameter gradients (one workgroup over the whole batch: 18 - 24 us) are nobody's input before the optimizer -
                 # they run as their own operator on the weight-gradient queue; the critical queue keeps the per-image dgap kernel
-                defer = shards and os.environ.get('SALT_SE_FC_SIDE', '1') != '0'
+                defer = shards and switches.get('SALT_SE_FC_SIDE')
                 kw = dict(dtype=self.dt, x=xview(), y=out.view(), dy=out.gview(), w1=l1.weight.data_ptr(), w2=l2.weight.data_ptr(),
                           R=R, ws=cs.weight.data_ptr(), gap=gap.data_ptr(), hidden=hid.data_ptr(), gate_c=gc.data_ptr(), gate_s=gs.data_ptr(),
                           partials=Scratch('se', B * nparts * (2 * C + 1) * 4), nparts=nparts, g_w1=gp(l1.weight), g_b1=gp(l1.bias),
@@ -1599,13 +1487,12 @@ class Graph:
                 # round 6: with the input transform the kernel holds everything the producer layer's BatchNorm backward sums over - it takes
                 # them too and that layer's bn_bwd loses its reduction pass (saltnet.h salt_scse_bwd_args.bnb_acc; SALT_SE_BNB=0: off)
                 carry = (taken is not None and shards and getattr(x.buf, 'bn_train_out', None) == (x.c0, x.C) and acc == 0
-                         and x.B * x.H * x.W < (1 << 31) and os.environ.get('SALT_SE_BIAS_FOLD', '1') != '0' and os.environ.get('SALT_SE_BNB', '1') != '0')
+                         and x.B * x.H * x.W < (1 << 31) and switches.get('SALT_SE_BNB'))
                 if shards:
                     self._fin_slot('bwd', B * ((6 if carry else 2) * C + 1), (sb, 'acc'), *([(sg, 'acc')] if sg is not None else []))
                 # x = relu(bn(conv)): its only gradient consumer is that layer's bn_bwd, which can add the channel-SE term dgap[b][c]
                 # wherever it reads dL/dx - the broadcast-add pass over dx (read + write of the whole tensor) disappears
-                if (getattr(x.buf, 'bn_train_out', None) == (x.c0, x.C) and acc == 0 and x.B * x.H * x.W < (1 << 31)
-                        and os.environ.get('SALT_SE_BIAS_FOLD', '1') != '0'):
+                if (getattr(x.buf, 'bn_train_out', None) == (x.c0, x.C) and acc == 0 and x.B * x.H * x.W < (1 << 31)):
                     if getattr(x.buf, 'grad_bias', None) is not None:
                         raise SaltError('two pending gradient biases on %s' % x.buf.name)
                     self.bwd.set_fields(sb, skip_bcast=1)

@@ -11,13 +11,13 @@ parameter buffers), the optimizer is one fused Adam kernel, ``_fit_loop`` runs f
 -> (bucketed RCCL all-reduce overlapped with backward) -> Adam without touching torch autograd, and
 ``nn.DataParallel`` (models.py:81-85) is replaced by one process per GPU (parallel.py).
 """
-import os
 
 import numpy as np
 import torch
 
 from . import architectures as A
 from . import parallel
+from . import switches
 from ._abi import SaltError
 from .losses import lovasz_loss, mixed_dice_bce_loss
 from .optim import FusedAdam, weight_regularization
@@ -106,7 +106,8 @@ class SegmentationModel(Model):
         self.dp = parallel.DataParallel.from_env()
         # opt-in: one-GPU training replays the whole step as a hipGraph (training_config['step_graph'] / SALT_STEP_GRAPH=1);
         # the eager two-stream step is faster
-        self.step_graph = bool(int(os.environ.get('SALT_STEP_GRAPH', '1' if (training_config or {}).get('step_graph', False) else '0')))
+        sg = switches.get('SALT_STEP_GRAPH')
+        self.step_graph = bool((training_config or {}).get('step_graph', False)) if sg is None else sg
 
     # ------------------------------------------------------------------ reference surface
     def set_model(self):
@@ -169,7 +170,7 @@ class SegmentationModel(Model):
         (name, loss_function, weight), target = self.loss_function[0], targets[0]
         kind = getattr(loss_function, 'native_kind', None)
         if kind is not None:
-            batch_loss = self._fused_step(X, target, kind, weight, adam_in_backward=True)     # (optimizer.step() follows below)
+            batch_loss = self._fused_step(X, target, kind, weight)     # (optimizer.step() follows below)
         else:                                   # any torch-differentiable loss: through the autograd bridge
             outputs_batch = self.model(X)
             batch_loss = loss_function(outputs_batch, target) * weight
@@ -181,7 +182,7 @@ class SegmentationModel(Model):
             self.optimizer.step()
         return {'sum': batch_loss}
 
-    def _fused_step(self, X, target, kind, weight, adam_in_backward=False):
+    def _fused_step(self, X, target, kind, weight):
         eng = self.model.engine(X.device)
         # 'first step of a shape ran eagerly' is remembered ON the engine (a rebuilt engine starts empty - no recycled id() can skip it)
         if self.step_graph and not self.dp._active() and (tuple(X.shape), kind) in eng.eager_done:
@@ -200,29 +201,20 @@ class SegmentationModel(Model):
         net = eng.net(tuple(X.shape), True)
         K = net.logits.shape[1]
         loss_prog = net.loss_program(kind, weight)
-        zero_copy = os.environ.get('SALT_STEP_ZERO_COPY', '1') != '0'
-        bx = zero_copy and net.bindable(X, net.x)
-        bt = zero_copy and net.bindable(target, net.target)
-        loss_t = torch.empty((1,), dtype=torch.float32, device=X.device) if zero_copy else None
+        bx = net.bindable(X, net.x)
+        bt = net.bindable(target, net.target)
+        loss_t = torch.empty((1,), dtype=torch.float32, device=X.device)
         try:
             net.bind(x=X if bx else None, target=target if bt else None, loss=loss_t)
             eng.forward(X if bx else X.contiguous().float(), True, bound=bx)
             if not bt:
                 net.target.copy_(target[:, :K])
             loss_prog.run()
-            bwd = None
-            if adam_in_backward and not self.dp._active() and getattr(self.optimizer, 'model', None) is self.model and hasattr(self.optimizer, 'begin_step'):
-                # one rank: the optimizer updates each parameter range as soon as its gradients are final, beside the rest of backward
-                self.optimizer.grad_scale = 1.0
-                bwd = self.optimizer.begin_step(net)
-            if bwd is not None:
-                bwd.run(side=eng.side_stream)
-            else:
-                self.dp.backward(eng, net, self.optimizer)
+            self.dp.backward(eng, net, self.optimizer)
         finally:
             net.bind()                           # back to the static buffers (tools / tests that run the programs on their own)
         eng.eager_done.add((tuple(X.shape), kind))
-        return loss_t[0] if zero_copy else net.loss[0].clone()
+        return loss_t[0]
 
     def transform(self, datagen, validation_datagen=None, *args, **kwargs):
         outputs = self._transform(datagen, validation_datagen)

@@ -24,6 +24,8 @@ import weakref
 import torch
 import torch.distributed as dist
 
+from . import switches
+
 DEFAULT_BUCKET_BYTES = 32 << 20
 DEFAULT_TAIL_BYTES = 4 << 20
 # RCCL's device kernels take ONE workgroup (= one CU) per channel.  The convolution kernels of this build are whole-CU workgroups
@@ -44,7 +46,7 @@ def configure_rccl_env():
     is created - RCCL reads it when the communicator comes up.  -> the value in effect, or None when RCCL's default is left alone."""
     if 'NCCL_MAX_NCHANNELS' in os.environ:
         return int(os.environ['NCCL_MAX_NCHANNELS'])
-    n = int(os.environ.get('SALT_RCCL_MAX_NCHANNELS', str(DEFAULT_RCCL_MAX_NCHANNELS)))
+    n = switches.get('SALT_RCCL_MAX_NCHANNELS')
     if n > 0:
         os.environ['NCCL_MAX_NCHANNELS'] = str(n)
         return n
@@ -78,7 +80,7 @@ def pin_rank_threads(local_rank=0, local_world=1):
     between the ranks whose GPUs share it (the reference's nn.DataParallel ran ONE process with a thread per replica, models.py:81-85,
     and num_workers loader processes, loaders.py:477-490).  SALT_NO_PIN=1: leave the affinity alone.
     -> {'numa_node', 'cpus' (count), 'mask' (cpulist string), 'ranks_on_node'} or None when nothing was changed."""
-    if os.environ.get('SALT_NO_PIN') or not hasattr(os, 'sched_setaffinity'):
+    if switches.get('SALT_NO_PIN') or not hasattr(os, 'sched_setaffinity'):
         return None
     try:
         allowed = sorted(os.sched_getaffinity(0))
@@ -221,7 +223,7 @@ class DataParallel:
                 w.wait()
 
     def _active(self):
-        return self.world > 1 or bool(os.environ.get('SALT_FORCE_DP_PATH') and dist.is_initialized())
+        return self.world > 1 or bool(switches.get('SALT_FORCE_DP_PATH') and dist.is_initialized())
 
     def _all_reduce(self, t):
         """SUM all-reduce of one contiguous gradient range on the current stream (async work handle).  Tests substitute the
@@ -293,10 +295,10 @@ class DataParallel:
             return
         key = net
         if key not in self._plans:
-            frac = float(os.environ.get('SALT_DP_FIRST_FRACTION', str(DEFAULT_FIRST_FRACTION)))
+            frac = DEFAULT_FIRST_FRACTION
             self._plans[key] = plan_buckets(net.g.grad_ready, eng.n_live, self.bucket_bytes,
                                             first_pos=int(frac * len(net.bwd)) if frac > 0 else None)
-        if self.timeline or os.environ.get('SALT_DP_SEGMENTS'):
+        if self.timeline:
             if key not in self._events:
                 # ONE event per bucket and queue, created once (round 4 allocated two torch.cuda.Event objects per bucket per step)
                 self._events[key] = [(torch.cuda.Event(), torch.cuda.Event()) for _ in self._plans[key]]
@@ -358,7 +360,7 @@ class DataParallel:
 
     def _backward_segments(self, eng, net, key):
         """round 4's form - the backward program cut into one executor call per bucket - kept for the per-bucket timing timeline
-        (timeline=True needs timing events recorded from Python) and as an A/B (SALT_DP_SEGMENTS=1)"""
+        (timeline=True needs timing events recorded from Python)"""
         if self._comm_stream is None:
             self._comm_stream = torch.cuda.Stream()
         cur = torch.cuda.current_stream()

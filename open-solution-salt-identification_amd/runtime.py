@@ -12,7 +12,6 @@ Design notes (MI355X-first):
     stream) -> fused Adam; each is one call into the native executor.
 """
 import ctypes
-import os
 
 import torch
 
@@ -87,10 +86,15 @@ class CompiledNet:
         return self._slots[which][1]
 
     def bind(self, **tensors):
-        """bind(x=t, target=t2, loss=t3): point the programs at these device tensors (None / omitted: the static buffer).  The caller
-        keeps the tensors alive until the step's launches are enqueued on the stream it later frees / overwrites them on."""
-        for which in ('x', 'target', 'loss'):
-            t = tensors.get(which)
+        """bind(x=t, target=t2, loss=t3): point the programs at these device tensors.  ``key=None`` points that key back at its static
+        buffer, a key that is not given is left as it is, and a bare ``bind()`` resets all three.  The caller keeps the tensors alive
+        until the step's launches are enqueued on the stream it later frees / overwrites them on."""
+        if not tensors:
+            tensors = dict(x=None, target=None, loss=None)
+        for which in tensors:
+            if which not in ('x', 'target', 'loss'):
+                raise SaltError('bind(): unknown key %r' % which)
+            t = tensors[which]
             buf = {'x': self.x, 'target': getattr(self, 'target', None), 'loss': getattr(self, 'loss', None)}[which]
             if buf is None:
                 continue
@@ -158,8 +162,7 @@ class Engine:
         self._packed_version = -1
         self._folded_version = None
         self.world = 1
-        pr = os.environ.get('SALT_SIDE_PRIORITY')                # (A/B: HIP stream priority of the weight-gradient queue; lower number = served first)
-        self.side_stream = torch.cuda.Stream(device=device, priority=int(pr)) if pr else torch.cuda.Stream(device=device)     # weight-gradient kernels overlap the data-gradient chain
+        self.side_stream = torch.cuda.Stream(device=device)     # weight-gradient kernels overlap the data-gradient chain
         self.eager_done = set()          # (shape, loss kind) whose first training step already ran eagerly (models.SegmentationModel._fused_step)
 
     # ------------------------------------------------------------------ flat parameter storage
@@ -368,10 +371,8 @@ class Engine:
         # recaptures an executable of an older one instead of replaying it against freed tables
         self._pack_generation = getattr(self, '_pack_generation', 0) + 1
 
-    def refresh(self, train, defer_bwd=False):
-        """Bring the packed weight copies (and, in eval mode, the folded BN constants) up to date.  ``defer_bwd``: leave the
-        data-gradient packs to a later ``refresh(True)`` (Engine.forward issues them after the forward program, so that they run under
-        the loss kernel - 32 workgroups on an otherwise idle GPU - instead of competing with the first forward layers)."""
+    def refresh(self, train):
+        """Bring the packed weight copies (and, in eval mode, the folded BN constants) up to date."""
         if getattr(self, '_pack_batched_n', -1) != len(self._pack_ops):
             self._build_pack_batch()
             self._packed_version = self._packed_bwd_version = -1
@@ -379,13 +380,10 @@ class Engine:
             # the optimizer step that produced this weight version wrote the vector-path forward packs itself (FusedAdam -> salt_adam_pack)
             (self._pack_batched_rest if getattr(self, '_adam_packed_version', None) == self.wver else self._pack_batched).run()
             self._packed_version = self.wver
-        if train and not defer_bwd and self._packed_bwd_version != self.wver and len(self._pack_batched_bwd):
+        if train and self._packed_bwd_version != self.wver and len(self._pack_batched_bwd):
             # ordered after the optimizer step on the main stream; the backward program's first data-gradient joins (engine.py)
-            if os.environ.get('SALT_PACK_BWD_MAIN'):                 # A/B: everything on the main stream
-                self._pack_batched_bwd.run()
-            else:
-                self.side_stream.wait_stream(torch.cuda.current_stream())
-                self._pack_batched_bwd.run(stream=self.side_stream)
+            self.side_stream.wait_stream(torch.cuda.current_stream())
+            self._pack_batched_bwd.run(stream=self.side_stream)
             self._packed_bwd_version = self.wver
         if not train and self._folded_version != (self.wver, self.sver):
             self._fold_ops.run()
@@ -476,11 +474,8 @@ class Engine:
         if not bound:
             net.bind(x=None)
             net.x.copy_(x)
-        late = train and bool(os.environ.get('SALT_PACK_BWD_LATE'))   # round 2: the loss is ~65 us now, too short to hide the packs
-        self.refresh(train, defer_bwd=late)
-        net.fwd.run(side=None if os.environ.get('SALT_NO_FWD_SIDE') else self.side_stream)
-        if late:
-            self.refresh(True)                               # data-gradient packs behind the forward pass (A/B: SALT_PACK_BWD_LATE)
+        self.refresh(train)
+        net.fwd.run(side=self.side_stream)
         if train:
             self.touch(weights=False, stats=True)            # BN running statistics moved
         return net

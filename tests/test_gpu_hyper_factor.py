@@ -370,12 +370,10 @@ def test_tapgemm_pack_and_sliced_reduce_layouts():
 
 
 @pytest.mark.parametrize('shape', [(64, 64, 3), (512, 512, 2), (96, 40, 8), (64, 320, 1)])
-def test_wgrad_reduce9_is_bit_identical_to_the_per_element_kernel(shape, monkeypatch):
-    """wgrad_reduce9_kernel (a thread per (a, b) pair writes its nine taps as 36 contiguous bytes) against wgrad_reduce8_kernel (a thread per
-    slab element): the SAME slabs presented with the taps in reverse order take the per-element kernel (the launch is routed by the raster
-    order of tap_kh / tap_kw) and must produce the same bits, plain and accumulating, full tensor and channel slice (ldb)."""
+def test_wgrad_reduce_does_not_depend_on_the_tap_order(shape):
+    """salt_wgrad_reduce: the SAME slabs presented with the taps in raster and in reverse order (tap_kh / tap_kw name where each tap
+    goes) must produce the same bits, plain and accumulating, on a channel slice (ldb), and both equal the sum over the splits."""
     abi = _abi()
-    monkeypatch.setenv('SALT_WGRAD_REDUCE9', '1')          # opt-in kernel (measured no faster: DESIGN 10)
     Ca, Cb, ns = shape
     g = torch.Generator().manual_seed(Ca + Cb)
     slab = torch.randn(ns, 9, Ca, Cb, generator=g)
@@ -395,4 +393,5 @@ def test_wgrad_reduce9_is_bit_identical_to_the_per_element_kernel(shape, monkeyp
     assert torch.equal(res['raster'], res['reverse'])
     want = torch.full((Ca, ldb, 3, 3), 0.5)
     want[:, 8:8 + Cb] = 2 * slab.sum(0).permute(1, 2, 0).reshape(Ca, Cb, 3, 3)
-    assert_close(res['raster'], want, 1e-6, 'reduce9 vs torch')
+    assert_close(res['raster'], want, 1e-6, 'reduce vs torch')
+    assert_close(res['reverse'], want, 1e-6, 'reduce (reverse tap order) vs torch')

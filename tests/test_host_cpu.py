@@ -413,3 +413,37 @@ def test_no_wrong_result_switches_in_the_shipped_engine():
     assert not re.search(r'SALT_EXP_|SALT_TIMING_ONLY|timing_experiment', src)
     assert 'forward-only' in src and 'SALT_FWD_BN_FOLD' in src
 
+
+def test_switch_table_names_exactly_the_switches_the_code_reads():
+    """One table of switches: the SALT_* names the library reads (`getenv("...")` in csrc/*.hip) plus the names of the package's table
+    (switches.SWITCHES) are exactly the rows of DESIGN.md's switch table, the accessor module is the only package file that reads a SALT_*
+    variable, and an unknown name raises.  (Error codes and macros - SALT_E_*, SALT_OK - are not switches: matched by context.)"""
+    import glob
+    from salt_amd import switches
+    c_names = set()
+    for fn in glob.glob(os.path.join(PKG, 'csrc', '*.hip')) + glob.glob(os.path.join(PKG, 'csrc', '*.h')):
+        with open(fn) as f:
+            c_names |= set(re.findall(r'getenv\("(SALT_[A-Z0-9_]+)"\)', f.read()))
+    assert c_names and not (c_names & set(switches.SWITCHES))
+    with open(os.path.join(ROOT, 'DESIGN.md')) as f:
+        design = f.read()
+    table = design[design.index('## 8. Switches'):design.index('## 9.')]
+    table = table[:table.index('Build-time variants')]
+    rows = [l for l in table.split('\n') if l.startswith('| `')]
+    doc_names = [re.match(r'\| `(SALT_[A-Z0-9_]+)` \|', l).group(1) for l in rows]
+    assert len(doc_names) == len(set(doc_names))
+    assert set(doc_names) == c_names | set(switches.SWITCHES), (sorted(set(doc_names) ^ (c_names | set(switches.SWITCHES))))
+    for l in rows:                                           # every survivor says who sets it
+        assert len(l.split('|')) == 7 and l.split('|')[5].strip(), l
+    for fn in glob.glob(os.path.join(PKG, '*.py')):
+        if os.path.basename(fn) == 'switches.py':
+            continue
+        with open(fn) as f:
+            src = f.read()
+        assert not re.search(r"os\.environ(\.get\(|\[)\s*['\"]SALT_", src), fn
+        assert not re.search(r"getenv\(\s*['\"]SALT_", src), fn
+    with pytest.raises(KeyError):
+        switches.get('SALT_NOT_A_SWITCH')
+    for name, (default, parse, meaning) in switches.SWITCHES.items():
+        assert callable(parse) and meaning
+
