@@ -731,6 +731,45 @@ typedef struct {
 int salt_scse_bwd(const salt_scse_bwd_args*, void* stream);
 int salt_scse_fc_grads(const salt_scse_bwd_args*, void* stream);
 
+/* ------------------------------------------------------------------ depth-conditioned channel gate (architectures/base.py:120-131,
+ * models_with_depth.py:56-76): s[b][j] = sigmoid(w[j] D[b] + bias[j]) (nn.Linear(1, C) + Sigmoid), hyper * s[:, :, None, None].
+ * A per-image, per-channel scale commutes with bilinear up-sampling, so every hypercolumn level is gated at its OWN resolution by
+ * salt_channel_gate over channels [c0, c0 + C) of the gate; no full-resolution 5d-channel tensor is ever formed. */
+typedef struct {
+    const float* d;           /* [B][1] fp32 depth of every image */
+    const float* w;           /* [C] (nn.Linear(1, C).weight is [C][1]) */
+    const float* bias;        /* [C] */
+    int B;
+    int C;
+    float* s;                 /* [B][C] gate: written by forward, read by backward */
+    int backward;             /* 0: s from d, w, bias.  1: gw[j] = sum_b ds s (1 - s) D[b], gb[j] = sum_b ds s (1 - s), b ascending */
+    const float* ds;          /* backward: [B][C] fp32 dL/ds (the fixed-order path of salt_channel_gate), or NULL */
+    const double* ds_acc;     /* backward: [B][C] fp64 sums salt_channel_gate added to (atomics path), used when ds == NULL */
+    float* gw;                /* backward out [C] */
+    float* gb;                /* backward out [C] */
+    int accumulate;           /* 1: gw / gb += */
+} salt_depth_gate_args;
+int salt_depth_gate(const salt_depth_gate_args*, void* stream);
+
+typedef struct {
+    int dtype;
+    salt_view x;              /* forward input.  backward: the forward input, or with inplace = 1 the forward OUTPUT (the input is gone) */
+    salt_view y;              /* forward: output, y = x s[b][c0 + c] (may be x itself).  backward: dL/dy */
+    salt_view dx;             /* backward: dL/dx = dL/dy s (may be y itself) */
+    const float* s;           /* [B][sC] */
+    int sC;
+    int c0;
+    int backward;
+    int accumulate;           /* backward: dx += */
+    int inplace;              /* backward: x holds y = x s, s > 0: sum dy x = (sum dy y) / s */
+    float* ds;                /* backward, fixed-order path: [B][sC] fp32, columns [c0, c0 + C) are WRITTEN from the partials (second launch) */
+    float* partials;          /* backward, fixed-order path: [B][nparts][C] workspace */
+    int nparts;               /* as returned by salt_channel_gate_parts */
+    double* ds_acc;           /* backward, atomics path (ds == NULL): [B][sC] fp64 ZEROED by the caller; every (image, part) adds its sums */
+} salt_channel_gate_args;
+int salt_channel_gate(const salt_channel_gate_args*, void* stream);
+int salt_channel_gate_parts(const salt_channel_gate_args*);
+
 /* ------------------------------------------------------------------ losses
  * Lovasz hinge, per image, both channels flattened together, F.elu variant
  * (lovasz_losses.py:81-115,21-33; models.py:326-328).  One workgroup per image: LSD radix sort of

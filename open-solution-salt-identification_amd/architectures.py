@@ -340,7 +340,19 @@ class HipNetwork(nn.Module):
         return []
 
     # -- execution -----------------------------------------------------------------------------------
-    def forward(self, x):
+    uses_depth = False          # True: forward(x, d) with the tiles' depths d [B,1] (UNetResNetWithDepth)
+
+    def _check_depth(self, x, d):
+        if not self.uses_depth:
+            if d is not None:
+                raise SaltError('%s takes no depth input' % type(self).__name__)
+            return None
+        if not isinstance(d, torch.Tensor) or tuple(d.shape) != (x.shape[0], 1):
+            raise SaltError('%s needs the depth input d of shape [%d, 1] (got %s)'
+                            % (type(self).__name__, x.shape[0], 'none' if d is None else tuple(getattr(d, 'shape', ()))))
+        return d.to(x.device).contiguous().float()
+
+    def forward(self, x, d=None):
         if not isinstance(x, torch.Tensor) or x.dim() != 4:
             raise SaltError('expected a [B,C,H,W] tensor')
         if x.device.type != 'cuda':
@@ -348,10 +360,11 @@ class HipNetwork(nn.Module):
                             % (type(self).__name__, x.device.type))
         eng = self.engine(x.device)
         x = x.contiguous().float()
+        d = self._check_depth(x, d)
         if self.training and torch.is_grad_enabled():
             from .autograd import HipNetFunction
-            return HipNetFunction.apply(self, x, *eng.live_params)
-        net = eng.forward(x, self.training)
+            return HipNetFunction.apply(self, x, d, *eng.live_params)
+        net = eng.forward(x, self.training, d=d)
         return net.logits.clone()
 
 
@@ -382,6 +395,11 @@ class UNetResNet(HipNetwork):
         B, _, H, W = shape
         s = 2 if self.encoders.pool0 else 1
         return (B, self.num_classes, H // s, W // s)
+
+    def _hyper_in(self, g, x, c0, last=False):
+        """Hook: ``x`` is about to enter the final block as channels [c0, c0 + x.C) of the (possibly factored) hypercolumn, at its own
+        resolution.  ``last``: dec1, whose only consumer is the final block.  UNetResNetWithDepth gates here."""
+        return x
 
     def emit(self, g, x_nchw, logits):
         enc = self.encoders.encoder
@@ -429,10 +447,10 @@ class UNetResNet(HipNetwork):
         def hyper_up(x, R, k):
             if (R, k) in fact:
                 with g.side():
-                    zs[k] = g.hyper_level(x, self.final[0].conv, k * d, name='hyper.z%d' % k)
+                    zs[k] = g.hyper_level(self._hyper_in(g, x, k * d), self.final[0].conv, k * d, name='hyper.z%d' % k)
             elif self.use_hypercolumn:
                 with g.side():
-                    g.upsample(x, R, out=hyper.slice(k * d, d))
+                    g.upsample(self._hyper_in(g, x, k * d), R, out=hyper.slice(k * d, d))
         d5 = self.dec5.emit(g, c, e5, cat=cat5)
         hyper_up(d5, 16, 4)
         d4 = self.dec4.emit(g, d5, e4, cat=cat4)
@@ -442,7 +460,7 @@ class UNetResNet(HipNetwork):
         d2 = self.dec2.emit(g, d3, e2, cat=cat2)
         hyper_up(d2, 2, 1)
         if self.use_hypercolumn:
-            d1 = self.dec1.emit(g, d2, None, out=hyper.slice(0, d))
+            d1 = self._hyper_in(g, self.dec1.emit(g, d2, None, out=hyper.slice(0, d)), 0, last=True)
             g.join()
             if fact:
                 ks = sorted(zs)
@@ -455,9 +473,44 @@ class UNetResNet(HipNetwork):
             else:
                 f = self.final[0].emit(g, hyper)
         else:
-            d1 = self.dec1.emit(g, d2, None)
+            d1 = self._hyper_in(g, self.dec1.emit(g, d2, None), 0, last=True)
             f = self.final[0].emit(g, d1)
         g.head(f, self.final[1], logits)
+
+
+class DepthChannelExcitation(EmitOnly):
+    """architectures/base.py:120-131: x * sigmoid(Linear(1, C)(d))[:, :, None, None]."""
+
+    def __init__(self, channels):
+        super().__init__()
+        self.fc = nn.Sequential(nn.Linear(1, channels), nn.Sigmoid())
+
+
+class UNetResNetWithDepth(UNetResNet):
+    """architectures.models_with_depth.UNetResNetWithDepth: UNetResNet whose hypercolumn (or dec1 alone) is scaled per image and
+    channel by a gate computed from the tile's depth ``d`` [B,1] before the final block.  The scale commutes with the bilinear
+    up-sampling, so every level is gated at its own resolution (Graph.channel_gate) and the factored / planar hypercolumn paths of
+    UNetResNet.emit are used as they are: dec5 .. dec2 also feed the next decoder and get a gated copy, dec1 is gated in place (the
+    scSE backward that produced it reads its output for the ReLU mask only, and the gate is positive)."""
+
+    uses_depth = True
+
+    def __init__(self, encoder_depth, num_classes, dropout_2d=0.0, pretrained=False, use_hypercolumn=False):
+        super().__init__(encoder_depth, num_classes, dropout_2d=dropout_2d, pretrained=pretrained, use_hypercolumn=use_hypercolumn)
+        self.depth_channel_excitation = DepthChannelExcitation((5 if use_hypercolumn else 1) * self.bottom // 8)
+
+    def emit(self, g, x_nchw, logits):
+        if getattr(g, 'd', None) is None:
+            raise SaltError('UNetResNetWithDepth needs the graph\'s depth input (CompiledNet allocates it)')
+        # first operator of the main stream: the side-stream level gates and the in-place gate of dec1 are all ordered behind it
+        self._gate = g.depth_gate(g.d, self.depth_channel_excitation.fc[0])
+        try:
+            super().emit(g, x_nchw, logits)
+        finally:
+            self._gate = None
+
+    def _hyper_in(self, g, x, c0, last=False):
+        return g.channel_gate(x, self._gate, c0, out=x if last else None, name='depth_gate.c%d' % c0)
 
 
 class TernausUNetResNet(HipNetwork):

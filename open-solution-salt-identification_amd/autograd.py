@@ -8,9 +8,9 @@ from ._abi import SaltError
 
 class HipNetFunction(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, module, x, *params):
+    def forward(ctx, module, x, d, *params):
         eng = module.engine(x.device)
-        net = eng.forward(x, True)
+        net = eng.forward(x, True, d=d)          # d: the depth input of a depth-conditioned network (no gradient), else None
         ctx.net, ctx.eng = net, eng
         return net.logits.clone()
 
@@ -27,7 +27,7 @@ class HipNetFunction(torch.autograd.Function):
             view = eng.grads[off:off + n].view(p.shape)
             # gradients are already in place when p.grad still aliases the flat gradient buffer
             grads.append(None if (p.grad is not None and p.grad.data_ptr() == view.data_ptr()) else view.clone())
-        return (None, None) + tuple(grads)
+        return (None, None, None) + tuple(grads)
 
 
 class _NativeLoss(torch.autograd.Function):

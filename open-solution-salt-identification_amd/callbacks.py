@@ -24,6 +24,7 @@ import torch
 from torch.optim.lr_scheduler import ReduceLROnPlateau
 
 from . import inference
+from ._abi import SaltError
 
 logger = logging.getLogger('salt_amd')
 
@@ -198,8 +199,9 @@ class ExperimentTiming(Callback):
 
 
 class ValidationMonitor(Callback):
-    """callbacks.py:462-568.  ``data_dir`` / ``loader_mode`` / ``use_depth`` are accepted for signature compatibility; the
-    ground-truth masks come from the validation batches themselves (target channel 1), not from files on disk."""
+    """callbacks.py:462-568.  ``data_dir`` / ``loader_mode`` are accepted for signature compatibility; the ground-truth masks come
+    from the validation batches themselves (target channel 1), not from files on disk.  ``use_depth``: the validation batches are
+    ``(X, D, *targets)`` and the network is called as ``model(X, D)`` (callbacks.py:568-586)."""
 
     def __init__(self, data_dir=None, loader_mode=None, epoch_every=None, batch_every=None, use_depth=False):
         super().__init__()
@@ -210,6 +212,9 @@ class ValidationMonitor(Callback):
     def set_params(self, transformer, validation_datagen=None, meta_valid=None, *args, **kwargs):
         super().set_params(transformer, validation_datagen)
         self.meta_valid = meta_valid
+        net_depth = bool(getattr(getattr(transformer, 'model', None), 'uses_depth', False))
+        if bool(self.use_depth) != net_depth:
+            raise SaltError('ValidationMonitor(use_depth=%s) on a network that %s a depth input' % (bool(self.use_depth), 'takes' if net_depth else 'does not take'))
 
     def on_epoch_end(self, *args, **kwargs):
         if self.epoch_every and (self.epoch_id % self.epoch_every) == 0 and self.validation_datagen is not None:
@@ -287,10 +292,12 @@ class EarlyStopping(Callback):
         self.epoch_id += 1
 
 
-def score_validation(transformer, validation_datagen, target_size=(101, 101)):
+def score_validation(transformer, validation_datagen, target_size=(101, 101), use_depth=None):
     """One pass over the validation generator (callbacks.py:529-568 + 503-527): mean loss, and IoU / IOUT at the threshold the
     reference's sweep selects.  Everything but a few integers per image stays on the GPU."""
     model = transformer.model
+    if use_depth is None:
+        use_depth = bool(getattr(model, 'uses_depth', False))
     was_training = model.training
     model.eval()
     batch_gen, steps = validation_datagen
@@ -300,8 +307,13 @@ def score_validation(transformer, validation_datagen, target_size=(101, 101)):
     losses, counts = [], []
     with torch.no_grad():
         for batch_id, data in enumerate(batch_gen):
-            X, target = data[0].to(dev), data[1].to(dev)
-            logits = model(X)
+            X = data[0].to(dev)
+            if use_depth:                                    # callbacks.py:568-586: (X, D, *targets), model(X, D)
+                target = data[2].to(dev)
+                logits = model(X, data[1].to(dev).float())
+            else:
+                target = data[1].to(dev)
+                logits = model(X)
             losses.append((loss_function(logits, target) * weight).detach().reshape(1))
             prob = torch.sigmoid(logits.float())
             H, W = prob.shape[2:]

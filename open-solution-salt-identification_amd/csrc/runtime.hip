@@ -311,6 +311,8 @@ extern "C" int salt_abi_struct_sizes(int* out, int n) {
     (int)sizeof(salt_layout_args),
     (int)sizeof(salt_scse_args),
     (int)sizeof(salt_scse_bwd_args),
+    (int)sizeof(salt_depth_gate_args),
+    (int)sizeof(salt_channel_gate_args),
     (int)sizeof(salt_lovasz_args),
     (int)sizeof(salt_bce_dice_args),
     (int)sizeof(salt_adam_args),

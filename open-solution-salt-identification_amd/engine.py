@@ -1500,3 +1500,60 @@ class Graph:
                     self._bias_bufs = getattr(self, '_bias_bufs', []) + [x.buf]
             self.tape.append(backward)
         return out
+
+    # ------------------------------------------------------------------ depth-conditioned channel gate (csrc/depth.hip)
+    def _gate_shards(self):
+        """dL/ds travels like the cSE pooled sums (Graph.scse): fp64 atomics into the zeroed arena, or fixed-order partials."""
+        return bool(self.train and self._fin_mode() == 2 and switches.get('SALT_SE_SHARDS'))
+
+    def depth_gate(self, d, fc):
+        """s[B, C] = sigmoid(fc(d)) for ``fc = nn.Linear(1, C)`` and the static depth buffer ``d`` [B,1] (architectures/base.py:120-131).
+        Returns the gate record that ``channel_gate`` consumes; backward (emitted LAST: every channel_gate backward has then delivered
+        its columns of dL/ds) writes fc.weight.grad and fc.bias.grad.  ``d`` gets no gradient."""
+        B, C = int(d.shape[0]), fc.weight.shape[0]
+        s = self.f32(B * C)
+        self.fwd.add('depth_gate', d=d.data_ptr(), w=fc.weight.data_ptr(), bias=fc.bias.data_ptr(), B=B, C=C, s=s.data_ptr(), backward=0)
+        gate = dict(s=s, B=B, C=C, ds=None, users=[], covered=np.zeros(C, dtype=bool))
+        if self.train:
+            if not self._gate_shards():
+                gate['ds'] = self.f32(B * C)
+
+            def backward():
+                if not gate['covered'].all():
+                    raise SaltError('depth_gate: %d of %d gate channels never met a channel_gate' % (int((~gate['covered']).sum()), C))
+                sb = self.bwd.add('depth_gate', d=d.data_ptr(), B=B, C=C, s=s.data_ptr(), backward=1,
+                                  ds=gate['ds'].data_ptr() if gate['ds'] is not None else None, gw=self._gp(fc.weight), gb=self._gp(fc.bias),
+                                  accumulate=0)
+                if gate['ds'] is None:
+                    self._fin_slot('bwd', B * C, (sb, 'ds_acc'), *[(u, 'ds_acc') for u in gate['users']])
+            self.tape.append(backward)
+        return gate
+
+    def channel_gate(self, x, gate, c0, out=None, name='gate'):
+        """out = x * s[:, c0 : c0 + x.C] per image and channel.  ``out`` = x's own slice: in place (x has no other forward reader and the backward
+        of its producer does not need the ungated values); otherwise a gated copy.  Backward: dL/dx (+)= dL/dout * s and the columns
+        [c0, c0 + x.C) of dL/ds."""
+        inplace = out is not None and out.buf is x.buf and (out.c0, out.C) == (x.c0, x.C)
+        if out is None:
+            out = self.new_act(x.B, x.H, x.W, x.C, name)
+        if gate['covered'][c0:c0 + x.C].any() or c0 + x.C > gate['C'] or x.B != gate['B']:
+            raise SaltError('channel_gate: channels [%d, %d) of a %d-channel gate' % (c0, c0 + x.C, gate['C']))
+        gate['covered'][c0:c0 + x.C] = True
+        S = fill(STRUCTS['salt_channel_gate_args'](), dtype=self.dt, x=x.view())
+        nparts = lib.salt_channel_gate_parts(ctypes.byref(S))
+        if nparts < 1:
+            raise SaltError('channel_gate: %d channels are not supported' % x.C)
+        self.fwd.add('channel_gate', dtype=self.dt, x=x.view(), y=out.view(), s=gate['s'].data_ptr(), sC=gate['C'], c0=c0, backward=0)
+        out.on_side = self.fwd.default_stream == 1
+        if self.train:
+            def backward():
+                if not out.grad_ready():
+                    raise SaltError('channel_gate: dL/d(%s) was never written' % name)
+                acc = 0 if inplace else x.grad_state()
+                kw = dict(dtype=self.dt, x=out.view() if inplace else x.view(), y=out.gview(), dx=out.gview() if inplace else x.gview(),
+                          s=gate['s'].data_ptr(), sC=gate['C'], c0=c0, backward=1, accumulate=acc, inplace=int(inplace), nparts=nparts)
+                if gate['ds'] is not None:
+                    kw.update(ds=gate['ds'].data_ptr(), partials=Scratch('gate', x.B * nparts * x.C * 4))
+                gate['users'].append(self.bwd.add('channel_gate', **kw))
+            self.tape.append(backward)
+        return out

@@ -120,13 +120,16 @@ def _looks_like_depth_channels(X):
     return bool(ok.item())
 
 
-def predict_tta(net, X, flip_ud=False, flip_lr=True, variants_per_pass=None, depth_channels=None, method='mean'):
+def predict_tta(net, X, flip_ud=False, flip_lr=True, variants_per_pass=None, depth_channels=None, method='mean', depth=None):
     """Probabilities [B, C, H, W] of an eval-mode HipNetwork aggregated over the flip variants (reference default main.py:282-285:
     left-right only; BASELINE C4's "4-flip" is flip_ud=True, flip_lr=True).  ``depth_channels``: the input is the reference's
     3-channel [gray, depth ramp, gray*ramp] batch, whose channels 1 / 2 an up-down flip must rebuild rather than flip (see
     _flip_input); None (default) = decide from the data (channel 1 = linspace(0, 1, H) AND channel 2 = channel 0 * channel 1; one host
     sync), True raises if it is not.
     ``method``: 'mean' (default, neptune.yaml:80; one fused kernel) or 'max' / 'min' / 'gmean' (loaders.py:727-735).
+
+    ``depth``: the tiles' depths [B,1] of a depth-conditioned network (UNetResNetWithDepth); a flip does not change a tile's depth, so
+    every variant runs with the same values.
 
     The variants are forwarded ``variants_per_pass`` at a time as one larger batch (default: all of them).  For bit-faithful
     handling of the asymmetric 13/14 edge pad use :func:`predict_tta_tiles`, which flips the raw tiles like the reference."""
@@ -153,7 +156,7 @@ def predict_tta(net, X, flip_ud=False, flip_lr=True, variants_per_pass=None, dep
                     _flip_input(X, ud, lr, depth_channels, out=xb[j * B:(j + 1) * B])
             else:
                 xb = _flip_input(X, group[0][0], group[0][1], depth_channels)
-            lg = net(xb)
+            lg = net(xb) if depth is None else net(xb, depth.to(X.device).float().repeat(len(group), 1))
             if len(group) == V:
                 logits = lg.float()
             else:

@@ -26,6 +26,10 @@ ARCHITECTURES = {
     'UNetResNet': {'model': A.UNetResNet,
                    'model_config': {'encoder_depth': 34, 'use_hypercolumn': True, 'dropout_2d': 0.0, 'pretrained': False, 'pool0': False},
                    'init_weights': False},
+    # models.py:46-50: the depth-conditioned network of main.py's USE_DEPTH switch (SegmentationModelWithDepth)
+    'UNetResNetWithDepth': {'model': A.UNetResNetWithDepth,
+                            'model_config': {'encoder_depth': 34, 'use_hypercolumn': True, 'dropout_2d': 0.0, 'pretrained': False},
+                            'init_weights': False},
     # unet_models.py zoo (named by BASELINE.json's north_star; not wired into the reference's registry)
     'TernausUNetResNet': {'model': A.TernausUNetResNet,
                           'model_config': {'encoder_depth': 34, 'num_filters': 32, 'dropout_2d': 0.0, 'pretrained': False, 'is_deconv': True},
@@ -182,7 +186,8 @@ class SegmentationModel(Model):
             self.optimizer.step()
         return {'sum': batch_loss}
 
-    def _fused_step(self, X, target, kind, weight):
+    def _fused_step(self, X, target, kind, weight, D=None):
+        """``D``: the depth input [B,1] of a depth-conditioned network (SegmentationModelWithDepth), fp32 on X's device."""
         eng = self.model.engine(X.device)
         # 'first step of a shape ran eagerly' is remembered ON the engine (a rebuilt engine starts empty - no recycled id() can skip it)
         if self.step_graph and not self.dp._active() and (tuple(X.shape), kind) in eng.eager_done:
@@ -190,6 +195,10 @@ class SegmentationModel(Model):
             # a shape runs eagerly: lazy one-time work - kernel attributes, workspace allocation - must not fall into the capture)
             net = eng.net(tuple(X.shape), True)
             net.x.copy_(X)
+            if (net.d is None) != (D is None):
+                raise SaltError('depth input %s' % ('missing' if D is None else 'given to a network without one'))
+            if D is not None:
+                net.d.copy_(D)
             net.target.copy_(target[:, :net.logits.shape[1]])
             self.optimizer.grad_scale = 1.0
             eng.run_step_graph(net, kind, weight, self.optimizer)
@@ -203,10 +212,11 @@ class SegmentationModel(Model):
         loss_prog = net.loss_program(kind, weight)
         bx = net.bindable(X, net.x)
         bt = net.bindable(target, net.target)
+        bd = D is not None and net.d is not None and net.bindable(D, net.d)
         loss_t = torch.empty((1,), dtype=torch.float32, device=X.device)
         try:
-            net.bind(x=X if bx else None, target=target if bt else None, loss=loss_t)
-            eng.forward(X if bx else X.contiguous().float(), True, bound=bx)
+            net.bind(x=X if bx else None, target=target if bt else None, loss=loss_t, **({'d': D} if bd else {}))
+            eng.forward(X if bx else X.contiguous().float(), True, bound=bx, d=D, d_bound=bd)
             if not bt:
                 net.target.copy_(target[:, :K])
             loss_prog.run()
@@ -254,3 +264,60 @@ class SegmentationModel(Model):
         if torch.cuda.is_available():
             self._to_device()
         return self
+
+
+class SegmentationModelWithDepth(SegmentationModel):
+    """models.py:211-286: the trainer of main.py's USE_DEPTH switch.  Batches are ``(X, D, *targets)`` with D [B,1] the tiles' depths
+    (loaders.py:310-311: z / 1000); the network is called as ``model(X, D)``.  Native losses run through the fused step, any other
+    loss through the autograd bridge; everything else (load, persist, data-parallel buckets, FusedAdam) is SegmentationModel's - the two
+    gate parameters are ordinary live parameters of the flat buffers."""
+
+    def set_model(self):
+        super().set_model()
+        if not getattr(self.model, 'uses_depth', False):
+            raise SaltError('SegmentationModelWithDepth needs a depth-conditioned architecture (UNetResNetWithDepth), got %s'
+                            % self.architecture_config['model_params']['architecture'])
+
+    def _depth(self, D, X):
+        D = D.to(X.device, non_blocking=True)
+        if tuple(D.shape) != (X.shape[0], 1):
+            raise SaltError('depth batch must be [%d, 1], got %s' % (X.shape[0], tuple(D.shape)))
+        return D if D.dtype == torch.float32 else D.float()
+
+    def _fit_loop(self, data):
+        dev = self._to_device()
+        X = data[0].to(dev, non_blocking=True)
+        D = self._depth(data[1], X)
+        targets = [t.to(dev, non_blocking=True) for t in data[2:]]
+        self.optimizer.zero_grad()
+        if len(self.loss_function) != 1:
+            raise NotImplementedError('multi-output losses are off the reference default path')
+        (name, loss_function, weight), target = self.loss_function[0], targets[0]
+        kind = getattr(loss_function, 'native_kind', None)
+        if kind is not None:
+            batch_loss = self._fused_step(X, target, kind, weight, D=D)
+        else:
+            outputs_batch = self.model(X, D)
+            batch_loss = loss_function(outputs_batch, target) * weight
+            batch_loss.backward()
+            self.dp.allreduce_gradients(self.model.engine(), self.optimizer)
+        if getattr(self, '_graph_stepped', False):
+            self._graph_stepped = False
+        else:
+            self.optimizer.step()
+        return {'sum': batch_loss}
+
+    def _transform(self, datagen, validation_datagen=None, **kwargs):
+        dev = self._to_device()
+        self.model.eval()
+        batch_gen, steps = datagen
+        outputs = {}
+        with torch.no_grad():
+            for batch_id, data in enumerate(batch_gen):
+                X = data[0].to(dev)
+                outputs_batch = self.model(X, self._depth(data[1], X))
+                outputs.setdefault(self.output_names[0], []).append(outputs_batch.cpu().numpy())
+                if batch_id == steps:
+                    break
+        self.model.train()
+        return {'{}_prediction'.format(name): get_list_of_image_predictions(outs) for name, outs in outputs.items()}

@@ -51,6 +51,8 @@ class CompiledNet:
         self.x = g.alloc((B, C, H, W), torch.float32)
         oshape = engine.module.output_shape(shape) if hasattr(engine.module, 'output_shape') else (B, num_classes, H, W)
         self.logits = g.alloc(tuple(oshape), torch.float32)
+        # second network input of a depth-conditioned network: the tiles' depths [B,1], static like x
+        self.d = g.d = g.alloc((B, 1), torch.float32) if getattr(engine.module, 'uses_depth', False) else None
         engine.module.emit(g, self.x, self.logits)
         self.dlogits = getattr(g, 'dlogits', None)
         if train:
@@ -61,7 +63,7 @@ class CompiledNet:
         g.finalize()
         self.fwd, self.bwd = g.fwd, g.bwd
         self._loss_progs = {}
-        self._slots = {}               # 'x' | 'target' | 'loss' -> [(struct, field)] that hold the static buffer's address
+        self._slots = {}               # 'x' | 'd' | 'target' | 'loss' -> [(struct, field)] that hold the static buffer's address
         self._bound = {}
 
     # ------------------------------------------------------------------ zero-copy step inputs (round 6)
@@ -71,7 +73,7 @@ class CompiledNet:
         program is a host-side store and nothing else: the fused step (models.SegmentationModel._fused_step) points them at the
         caller's resident batch / target for the duration of its enqueue calls instead of copying 6 MB + 4 MB into the static
         buffers first, and puts them back (hipGraph captures bake pointers in - they keep the copies)."""
-        buf = {'x': self.x, 'target': getattr(self, 'target', None), 'loss': getattr(self, 'loss', None)}[which]
+        buf = self._static(which)
         progs = [self.fwd, self.bwd] + list(self._loss_progs.values())
         key = (which, tuple(id(p) for p in progs))
         if self._slots.get(which, (None,))[0] != key:
@@ -82,20 +84,25 @@ class CompiledNet:
                         _ptr_fields(st, buf.data_ptr(), out)
                         if self._bound.get(which, buf.data_ptr()) != buf.data_ptr():
                             _ptr_fields(st, self._bound[which], out)
+            if which == 'd' and buf is not None and not out:
+                raise SaltError('no operator of this instance reads the depth input')
             self._slots[which] = (key, out)
         return self._slots[which][1]
 
+    def _static(self, which):
+        return {'x': self.x, 'd': self.d, 'target': getattr(self, 'target', None), 'loss': getattr(self, 'loss', None)}[which]
+
     def bind(self, **tensors):
-        """bind(x=t, target=t2, loss=t3): point the programs at these device tensors.  ``key=None`` points that key back at its static
-        buffer, a key that is not given is left as it is, and a bare ``bind()`` resets all three.  The caller keeps the tensors alive
+        """bind(x=t, d=t1, target=t2, loss=t3): point the programs at these device tensors.  ``key=None`` points that key back at its static
+        buffer, a key that is not given is left as it is, and a bare ``bind()`` resets all of them.  The caller keeps the tensors alive
         until the step's launches are enqueued on the stream it later frees / overwrites them on."""
         if not tensors:
-            tensors = dict(x=None, target=None, loss=None)
+            tensors = dict(x=None, d=None, target=None, loss=None)
         for which in tensors:
-            if which not in ('x', 'target', 'loss'):
+            if which not in ('x', 'd', 'target', 'loss'):
                 raise SaltError('bind(): unknown key %r' % which)
             t = tensors[which]
-            buf = {'x': self.x, 'target': getattr(self, 'target', None), 'loss': getattr(self, 'loss', None)}[which]
+            buf = self._static(which)
             if buf is None:
                 continue
             ptr = buf.data_ptr() if t is None else t.data_ptr()
@@ -467,13 +474,21 @@ class Engine:
         self._packed_version = self._packed_bwd_version = self.wver      # the graph packed the weights it started from ...
         self.touch(weights=True, stats=True)                             # ... and Adam / BatchNorm moved them
 
-    def forward(self, x, train, bound=False):
-        """``bound``: the caller pointed the programs at ``x`` itself (CompiledNet.bind) - no copy into the static input buffer."""
+    def forward(self, x, train, bound=False, d=None, d_bound=False):
+        """``bound``: the caller pointed the programs at ``x`` itself (CompiledNet.bind) - no copy into the static input buffer.
+        ``d``: the depth input [B,1] of a depth-conditioned network (``d_bound``: likewise bound by the caller)."""
         _require_gpu(x.device)
         net = self.net(x.shape, train)
+        if (net.d is None) != (d is None):
+            raise SaltError('%s: depth input %s' % (type(self.module).__name__, 'missing' if d is None else 'given to a network without one'))
         if not bound:
             net.bind(x=None)
             net.x.copy_(x)
+        if d is not None and not d_bound:
+            if tuple(d.shape) != tuple(net.d.shape):
+                raise SaltError('depth input must be [%d, 1]' % net.d.shape[0])
+            net.bind(d=None)
+            net.d.copy_(d)
         self.refresh(train)
         net.fwd.run(side=self.side_stream)
         if train:
