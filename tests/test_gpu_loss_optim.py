@@ -131,6 +131,7 @@ def test_fused_adam_matches_torch_semantics():
     eng = net.engine(torch.device(DEV))
     opt = FusedAdam(weight_regularization(net, True, 1e-4), lr=1e-3, model=net)
     ps = [p.detach().cpu().clone() for p in eng.live_params]
+    p0s = [p.clone() for p in ps]
     ms = [torch.zeros_like(p) for p in ps]
     vs = [torch.zeros_like(p) for p in ps]
     gen = torch.Generator().manual_seed(1)
@@ -143,6 +144,16 @@ def test_fused_adam_matches_torch_semantics():
         OL.adam_l2_step(ps, gs, ms, vs, step, lr=1e-3, weight_decay=1e-4)
     for p, r in zip(eng.live_params, ps):
         assert_close(p.detach().cpu(), r, 1e-5, 'adam param')
+    # the moments and the summed three-step UPDATE (a parameter compared at 1e-5 of max|p| hides an update that is wrong by a percent
+    # at lr = 1e-3).  Moments: the oracle is fp32 too - three steps of about three roundings of 6e-8 on either side, 2e-6 of the max -
+    # plus the betas, which reach the kernel as fp32 words of `hyper` while torch forms 1 - beta in double: half an ulp of 0.9 / 0.999 is
+    # 2**-25 = 3.0e-8, that is 3.0e-7 of 1 - beta1 and 3.0e-5 of 1 - beta2, the factor of every term added to the moment
+    assert hasattr(opt, 'exp_avg') and hasattr(opt, 'exp_avg_sq')
+    for p, r, p0, m, v in zip(eng.live_params, ps, p0s, ms, vs):
+        off, n = eng.grad_range(p)
+        assert_close(opt.exp_avg[off:off + n].cpu().reshape(m.shape), m, 2e-6 + 3.0e-7, 'adam exp_avg')
+        assert_close(opt.exp_avg_sq[off:off + n].cpu().reshape(v.shape), v, 2e-6 + 3.0e-5, 'adam exp_avg_sq')
+        assert_close(p.detach().cpu() - p0, r - p0, 1e-4, 'adam update over three steps')
     assert opt.state_dict()['param_groups'][0]['lr'] == 1e-3
     opt.param_groups[0]['lr'] = 5e-4                                   # scheduler writes lr (callbacks.py:273-275)
     opt.step()
