@@ -1113,6 +1113,40 @@ int salt_graph_end(void* stream, void** graph_exec_out);
 int salt_graph_launch(void* graph_exec, void* stream);
 int salt_graph_destroy(void* graph_exec);
 
+/* ------------------------------------------------------------------ classifier head (architectures/misc.py:70-71,80):
+ * nn.Sequential(nn.AvgPool2d(8), nn.Conv2d(C, K, 1)) of EmptinessClassifier in one launch.  OH = H / 8, OW = W / 8 (floor; rows and
+ * columns beyond 8 OH / 8 OW belong to no window):
+ *   pooled[b,oh,ow,c] = (1/64) sum of the 8x8 window of x          (stored fp32)
+ *   logits[b,j,oh,ow] = bias[j] + sum_c w[j][c] pooled[b,oh,ow,c]   (stored fp32 NCHW)
+ * Both sums (and gw / gb of the backward call) are carried in fp64 and rounded once: a logit may cancel far below its terms.
+ * H < 8 or W < 8 is SALT_E_BADARG. */
+typedef struct {
+    int dtype;
+    salt_view x;              /* [B,H,W,C], may be a channel slice */
+    const float* w;           /* [K][C] fp32 (the module's [K,C,1,1] weight in place) */
+    const float* bias;        /* [K] or NULL */
+    int K;                    /* 1 .. 8 */
+    float* logits_nchw;       /* out fp32 [B,K,OH,OW] */
+    float* pooled;            /* out fp32 [B,OH,OW,C] kept for salt_pool_head_bwd, or NULL (eval) */
+} salt_pool_head_args;
+int salt_pool_head(const salt_pool_head_args*, void* stream);
+
+/* dx[b,h,w,c] (+)= (1/64) sum_j w[j][c] dlogits[b,j,h/8,w/8] inside the windows; outside them accumulate = 0 writes zero and
+ * accumulate = 1 leaves the pixel alone.  gw[j][c] = sum_{b,oh,ow} dlogits pooled and gb[j] = sum dlogits are OVERWRITTEN (as
+ * salt_head1x1_bwd does), summed in ascending (b, oh, ow) order: the same bits on every run.  x itself is not read. */
+typedef struct {
+    int dtype;
+    salt_view dx;             /* gradient view of the forward input [B,H,W,C]; p == NULL: no data gradient (the shape is still read) */
+    const float* w;           /* [K][C] */
+    int K;
+    const float* dlogits_nchw; /* fp32 [B,K,OH,OW] */
+    const float* pooled;      /* fp32 [B,OH,OW,C] from the forward call */
+    int accumulate;           /* dx += */
+    float* gw;                /* out [K][C] */
+    float* gb;                /* out [K] or NULL */
+} salt_pool_head_bwd_args;
+int salt_pool_head_bwd(const salt_pool_head_bwd_args*, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -13,6 +13,7 @@ Reference classes mirrored (paths relative to the reference's common_blocks/):
   architectures/base.py:7-37 Conv2dBnRelu · :40-57 DeconvConv2dBnRelu · :65-86 DecoderBlock ·
   :89-104 ChannelSELayer · :107-117 SpatialSELayer
   architectures/encoders.py:6-45 ResNetEncoders;  architectures/unet.py:22-109 UNetResNet
+  architectures/misc.py:39-81 EmptinessClassifier
   torchvision 0.2.0 models/resnet.py (un-vendored dependency): ResNet / BasicBlock / Bottleneck layout
 """
 import math
@@ -511,6 +512,46 @@ class UNetResNetWithDepth(UNetResNet):
 
     def _hyper_in(self, g, x, c0, last=False):
         return g.channel_gate(x, self._gate, c0, out=x if last else None, name='depth_gate.c%d' % c0)
+
+
+class EmptinessClassifier(HipNetwork):
+    """architectures.misc.EmptinessClassifier (misc.py:39-81), the per-tile "any salt at all" classifier empty_vs_non_empty.py trains:
+    ResNet stem without max-pool, layer1..4, then AvgPool2d(8) + 1x1 convolution on the /16 map (Graph.pool_head).  A 128x128 tile
+    gives [B, num_classes, 1, 1] logits."""
+
+    is_classifier = True        # Model.score_validation: ROC-AUC of the 1x1 output instead of the mask metrics
+
+    def __init__(self, num_classes=2, encoder_depth=18, pretrained=False):
+        super().__init__()
+        if encoder_depth not in ResNet.CFG:
+            raise NotImplementedError('only 18, 34, 50, 101, 152 version of Resnet are implemented')
+        self.num_classes = num_classes
+        self.encoder = resnet(encoder_depth, pretrained)
+        self.bottom = 512 if encoder_depth in (18, 34) else 2048
+        self.conv1 = nn.Sequential(self.encoder.conv1, self.encoder.bn1, self.encoder.relu)
+        self.encoder2 = self.encoder.layer1
+        self.encoder3 = self.encoder.layer2
+        self.encoder4 = self.encoder.layer3
+        self.encoder5 = self.encoder.layer4
+        self.classifier = nn.Sequential(nn.AvgPool2d(8), nn.Conv2d(self.bottom, num_classes, kernel_size=1, padding=0))
+
+    def dead_parameter_names(self):
+        return ['encoder.fc.weight', 'encoder.fc.bias']
+
+    def output_shape(self, shape):
+        B, _, H, W = shape
+        if H < 128 or W < 128:
+            raise SaltError('EmptinessClassifier needs tiles of at least 128x128 (got %dx%d): the layer4 map is smaller than the 8x8 pool window'
+                            % (H, W))
+        return (B, self.num_classes, H // 128, W // 128)
+
+    def emit(self, g, x_nchw, logits):
+        self.output_shape(tuple(x_nchw.shape))
+        enc = self.encoder
+        x = g.conv_first(x_nchw, enc.conv1, enc.bn1, relu=True, name='stem')
+        for layer in (enc.layer1, enc.layer2, enc.layer3, enc.layer4):
+            x = emit_blocks(g, layer, x)
+        g.pool_head(x, self.classifier[1], logits)
 
 
 class TernausUNetResNet(HipNetwork):

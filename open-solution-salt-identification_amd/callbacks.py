@@ -6,6 +6,7 @@
     ExperimentTiming                       callbacks.py:271-330
     ValidationMonitor                      callbacks.py:462-568   validation loss + the IoU / IOUT threshold sweep; the sweep runs on
                                                                   the GPU (inference.iou_counts) instead of 21 CPU pipelines
+    ValidationMonitorEmptiness             callbacks.py:618-674   validation loss + ROC-AUC of the emptiness classifier ({'sum', 'auc'})
     ReduceLROnPlateauScheduler             callbacks.py:204-241   torch ReduceLROnPlateau(mode, factor, patience, min_lr) on the fused
                                                                   Adam's param_groups (the kernel re-reads lr every step)
     ModelCheckpoint                        callbacks.py:758-792   best-metric ``state_dict`` with the reference's 'module.' key prefix
@@ -224,6 +225,17 @@ class ValidationMonitor(Callback):
         self.epoch_id += 1
 
 
+class ValidationMonitorEmptiness(ValidationMonitor):
+    """callbacks.py:618-674, the monitor empty_vs_non_empty.py trains EmptinessClassifier with: validation loss plus the ROC-AUC of the
+    "not empty" probability ({'sum', 'auc'}, score_validation_emptiness).  The labels come from the validation batches (target channel
+    1), not from ``meta_valid``, which is accepted and ignored."""
+
+    def set_params(self, transformer, validation_datagen=None, meta_valid=None, *args, **kwargs):
+        super().set_params(transformer, validation_datagen, meta_valid)
+        if not getattr(getattr(transformer, 'model', None), 'is_classifier', False):
+            raise SaltError('ValidationMonitorEmptiness needs a classifier network (EmptinessClassifier), got %s' % type(transformer.model).__name__)
+
+
 class ReduceLROnPlateauScheduler(Callback):
     def __init__(self, metric_name, minimize, reduce_factor, reduce_patience, min_lr):
         super().__init__()
@@ -333,6 +345,38 @@ def score_validation(transformer, validation_datagen, target_size=(101, 101), us
     return {'sum': mean_loss, 'iou': torch.tensor([iou], dtype=torch.float32), 'iout': torch.tensor([iout], dtype=torch.float32)}
 
 
+def score_validation_emptiness(transformer, validation_datagen):
+    """One eval pass over the validation generator (callbacks.py:662-716): mean loss and the ROC-AUC of sigmoid(logit[:, 1]) against
+    target[:, 1], as 1-element fp32 tensors {'sum', 'auc'}."""
+    model = transformer.model
+    was_training = model.training
+    model.eval()
+    batch_gen, steps = validation_datagen
+    dev = transformer._to_device()
+    (name, loss_function, weight) = transformer.loss_function[0]
+    losses, scores, labels = [], [], []
+    with torch.no_grad():
+        for batch_id, data in enumerate(batch_gen):
+            target = data[1].to(dev)
+            logits = model(data[0].to(dev))
+            if tuple(logits.shape[2:]) != (1, 1) or logits.shape[1] < 2:
+                # the reference's np.stack(y_pred)[:, 1] (callbacks.py:752-755) is one score per tile only for a [B,2,1,1] output
+                raise SaltError('emptiness validation needs [B,2,1,1] outputs (128x128 tiles), got %s' % (tuple(logits.shape),))
+            losses.append((loss_function(logits, target) * weight).detach().reshape(1))
+            scores.append(torch.sigmoid(logits.float()[:, 1, 0, 0]))
+            labels.append(target.float()[:, 1].reshape(target.shape[0], -1)[:, 0])
+            if batch_id == steps:
+                break
+    if was_training:
+        model.train()
+    if not losses:
+        raise SaltError('emptiness validation: the validation generator is empty')
+    mean_loss = torch.cat(losses).mean().reshape(1).cpu()
+    y_true = (torch.cat(labels).cpu().numpy() > 0.5).astype(np.int64)
+    auc = inference.roc_auc(y_true, torch.cat(scores).cpu().numpy())           # ValueError when only one class is present, as sklearn
+    return {'sum': mean_loss, 'auc': torch.tensor([auc], dtype=torch.float32)}
+
+
 def callbacks_network(callbacks_config):
     """models.py:300-312: build the callback list from the same config dict ('neptune_monitor' is ignored)."""
     cfg = callbacks_config or {}
@@ -342,7 +386,9 @@ def callbacks_network(callbacks_config):
     if 'training_monitor' in cfg:
         cbs.append(TrainingMonitor(**cfg['training_monitor']))
     if 'validation_monitor' in cfg:
-        cbs.append(ValidationMonitor(**cfg['validation_monitor']))
+        # the reference switches monitors by editing a comment (models.py:305-306); here the config says 'emptiness': True
+        vm = dict(cfg['validation_monitor'])
+        cbs.append((ValidationMonitorEmptiness if vm.pop('emptiness', False) else ValidationMonitor)(**vm))
     if 'model_checkpoint' in cfg:
         cbs.append(ModelCheckpoint(**cfg['model_checkpoint']))
     if 'reduce_lr_on_plateau_scheduler' in cfg:

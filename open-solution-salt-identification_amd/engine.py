@@ -1323,6 +1323,27 @@ class Graph:
                              gw=self._gp(conv.weight), gb=self._gp(conv.bias) if conv.bias is not None else None)
             self.tape.append(backward)
 
+    # ------------------------------------------------------------------ classifier head: AvgPool2d(8) + 1x1 conv to <= 8 logits, fp32 NCHW out
+    def pool_head(self, x, conv, logits_nchw, k=8):
+        """nn.Sequential(nn.AvgPool2d(k), nn.Conv2d(C, K, 1)) (architectures/misc.py:70-71) in one launch; training keeps the pooled
+        fp32 vector so that the backward launch never reads ``x`` again."""
+        if k != 8:
+            raise SaltError('pool_head: only the 8x8 window of the reference (nn.AvgPool2d(8)) is built, got %r' % (k,))
+        K = conv.weight.shape[0]
+        if tuple(conv.weight.shape[1:]) != (x.C, 1, 1) or tuple(logits_nchw.shape) != (x.B, K, x.H // k, x.W // k):
+            raise SaltError('pool_head: weight %s / logits %s do not fit the %dx%dx%d map' % (tuple(conv.weight.shape), tuple(logits_nchw.shape), x.H, x.W, x.C))
+        pooled = self.alloc((x.B, x.H // k, x.W // k, x.C), torch.float32) if self.train else None
+        self.fwd.add('pool_head', dtype=self.dt, x=x.view(), w=conv.weight.data_ptr(), bias=conv.bias.data_ptr() if conv.bias is not None else None,
+                     K=K, logits_nchw=logits_nchw.data_ptr(), pooled=pooled.data_ptr() if pooled is not None else None)
+        if self.train:
+            self.dlogits = self.alloc(tuple(logits_nchw.shape), torch.float32)
+
+            def backward():
+                acc = x.grad_state()
+                self.bwd.add('pool_head_bwd', dtype=self.dt, dx=x.gview(), w=conv.weight.data_ptr(), K=K, dlogits_nchw=self.dlogits.data_ptr(),
+                             pooled=pooled.data_ptr(), accumulate=acc, gw=self._gp(conv.weight), gb=self._gp(conv.bias) if conv.bias is not None else None)
+            self.tape.append(backward)
+
     # ------------------------------------------------------------------ layout boundary (fp32 NCHW <-> NHWC activations)
     def from_nchw(self, x_nchw, name='input'):
         B, C, H, W = x_nchw.shape

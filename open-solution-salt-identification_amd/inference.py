@@ -295,3 +295,36 @@ def select_threshold(counts_batches, thresholds=None):
     if k_best is None:                       # no threshold beat 0.0: the reference scores its default 0.5
         k_best = int(np.argmin(np.abs(thresholds - 0.5)))
     return t_best, float(iou[k_best]), float(iout[k_best])
+
+
+# ------------------------------------------------------------------ emptiness classifier (empty_vs_non_empty.py)
+def roc_auc(y_true, y_score):
+    """Area under the ROC curve of a binary problem, sklearn.metrics.roc_auc_score's value (callbacks.py:666) without the dependency:
+    the Mann-Whitney form U / (n_pos n_neg) with AVERAGE ranks for tied scores, which is the trapezoidal area of the ROC curve."""
+    y = np.asarray(y_true).reshape(-1)
+    s = np.asarray(y_score, np.float64).reshape(-1)
+    if y.shape != s.shape:
+        raise ValueError('roc_auc: %d labels for %d scores' % (y.size, s.size))
+    classes = np.unique(y)
+    if classes.size != 2:
+        raise ValueError('Only one class present in y_true. ROC AUC score is not defined in that case.')
+    pos = y == classes[1]
+    order = np.argsort(s, kind='mergesort')
+    ss = s[order]
+    start = np.flatnonzero(np.concatenate([[True], ss[1:] != ss[:-1]]))          # first index of every run of equal scores
+    end = np.concatenate([start[1:], [ss.size]])
+    avg = (start + end + 1) / 2.0                                                # mean of the 1-based ranks start + 1 .. end
+    ranks = np.empty(s.size, np.float64)
+    ranks[order] = np.repeat(avg, end - start)
+    n_pos = int(pos.sum())
+    n_neg = y.size - n_pos
+    return float((ranks[pos].sum() - n_pos * (n_pos + 1) / 2.0) / (n_pos * n_neg))
+
+
+def resize_emptiness_predictions(image, target_size):
+    """postprocessing.py:46-61: the [2,1,1] class probabilities of a tile spread over a (C x H x W) map of ``target_size``."""
+    image = np.asarray(image)
+    resized = np.zeros((image.shape[0], target_size[0], target_size[1]))
+    resized[0, :, :] = image[0]
+    resized[1, :, :] = image[1]
+    return resized

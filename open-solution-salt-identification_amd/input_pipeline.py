@@ -225,3 +225,10 @@ class DevicePreprocessor:
         if self._params is None:
             raise SaltError('DevicePreprocessor: no params recorded (construct with augment and record_params=True)')
         return self._params if raw else decode_params(self._params)
+
+
+def emptiness_target(is_not_empty):
+    """loaders.py:778-783 (preprocess_emptiness_target) for a batch: per tile the float target [2,1,1] of the emptiness classifier,
+    [1, 0] for an empty mask and [0, 1] otherwise.  ``is_not_empty``: [B] of {0, 1} (array or tensor) -> [B,2,1,1] float32."""
+    x = torch.as_tensor(np.asarray(is_not_empty.cpu() if torch.is_tensor(is_not_empty) else is_not_empty)).reshape(-1).to(torch.float32)
+    return torch.stack([(x == 0).to(torch.float32), x], 1).reshape(-1, 2, 1, 1)

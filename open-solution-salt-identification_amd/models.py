@@ -39,6 +39,10 @@ ARCHITECTURES = {
                       'init_weights': False},
     'SaltUNet': {'model': A.SaltUNet, 'model_config': {'dropout_2d': 0.0, 'pretrained': False, 'is_deconv': True}, 'init_weights': False},
     'SaltLinkNet': {'model': A.SaltLinkNet, 'model_config': {'dropout_2d': 0.0, 'pretrained': False, 'is_deconv': True}, 'init_weights': False},
+    # models.py:59-63: the per-tile "any salt at all" classifier of empty_vs_non_empty.py
+    'EmptinessClassifier': {'model': A.EmptinessClassifier,
+                            'model_config': {'encoder_depth': 18, 'pretrained': False},
+                            'init_weights': False},
     'VanillaUNet': {'model': A.VanillaUNet, 'model_config': {'in_channels': 1, 'base_filters': 16, 'levels': 4}, 'init_weights': False},
 }
 
@@ -56,7 +60,7 @@ def get_list_of_image_predictions(batch_predictions):      # utils.py:316-320
     return [img for batch in batch_predictions for img in list(batch)]
 
 
-from .callbacks import Callback, CallbackList, callbacks_network, score_validation  # noqa: E402,F401  (callbacks.py surface)
+from .callbacks import Callback, CallbackList, callbacks_network, score_validation, score_validation_emptiness  # noqa: E402,F401  (callbacks.py surface)
 
 
 class Model:
@@ -81,7 +85,10 @@ class Model:
         return self.fit(*args, **kwargs).transform(*args, **kwargs)
 
     def score_validation(self, validation_datagen):
-        """{'sum', 'iou', 'iout'} of one pass over the validation generator (callbacks.py:503-568), threshold sweep on the GPU."""
+        """{'sum', 'iou', 'iout'} of one pass over the validation generator (callbacks.py:503-568), threshold sweep on the GPU; a
+        classifier network (``is_classifier``) is scored as {'sum', 'auc'} (callbacks.py:662-674)."""
+        if getattr(self.model, 'is_classifier', False):
+            return score_validation_emptiness(self, validation_datagen)
         return score_validation(self, validation_datagen)
 
     def persist(self, filepath):
