@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <atomic>
 #include "saltnet.h"
 
 typedef unsigned short bf16_t;   // storage type of bf16 activations
@@ -121,6 +122,43 @@ int conv_wgrad_thin(const salt_conv_wgrad_args* a, bool launch, hipStream_t st, 
 
 // conv_wgrad_ls.hip: loader-specialised row-streaming weight gradient (bf16, 3x3, unit step); 0 = not one of its shapes, else nsplit
 int conv_wgrad_ls(const salt_conv_wgrad_args* a, bool launch, hipStream_t st, int* rc);
+
+// Launch `kern<<<grid, block, lds, st>>>(args...)` and run the launch check.  A launch that needs more than the default 64 KB of dynamic
+// LDS raises the kernel's limit to the CU's 160 KB first, once per kernel address: the addresses already raised fill a table from
+// the front.  Two host threads that meet on one free slot both raise their kernel; the loser of the exchange is not recorded and
+// raises its kernel once more on its next launch, which is harmless (as is a full table: every such launch raises again).
+static inline int salt_raise_lds_limit(const void* kern) {
+    static std::atomic<const void*> raised[256];
+    std::atomic<const void*>* free_slot = nullptr;
+    for (auto& slot : raised) {
+        const void* k = slot.load(std::memory_order_acquire);
+        if (k == kern) return 0;
+        if (!k) { free_slot = &slot; break; }
+    }
+    hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    if (e != hipSuccess) SALT_FAIL((int)e, "hipFuncSetAttribute: %s", hipGetErrorString(e));
+    const void* none = nullptr;
+    if (free_slot) free_slot->compare_exchange_strong(none, kern, std::memory_order_release, std::memory_order_relaxed);
+    return 0;
+}
+template <typename... Params, typename... Args>
+static inline int salt_launch(void (*kern)(Params...), dim3 grid, dim3 block, size_t lds, hipStream_t st, const Args&... args) {
+    if (lds > 64 * 1024) { const int rc = salt_raise_lds_limit(reinterpret_cast<const void*>(kern)); if (rc) return rc; }
+    hipLaunchKernelGGL(kern, grid, block, lds, st, args...);
+    SALT_CHECK_LAUNCH();
+    return 0;
+}
+
+// bounding box of a tap list
+struct TapBox { int min_dy, max_dy, min_dx, max_dx; };
+static inline TapBox tap_box(const int* dy, const int* dx, int n) {
+    TapBox b = {1 << 30, -(1 << 30), 1 << 30, -(1 << 30)};
+    for (int t = 0; t < n; ++t) {
+        b.min_dy = dy[t] < b.min_dy ? dy[t] : b.min_dy; b.max_dy = dy[t] > b.max_dy ? dy[t] : b.max_dy;
+        b.min_dx = dx[t] < b.min_dx ? dx[t] : b.min_dx; b.max_dx = dx[t] > b.max_dx ? dx[t] : b.max_dx;
+    }
+    return b;
+}
 
 static inline int ilog2_ceil(int v) { int l = 0; while ((1 << l) < v) ++l; return l; }
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }

@@ -20,12 +20,6 @@
 #include <cstdlib>
 #include <type_traits>
 #include "common.h"
-#ifndef SALT_K1_DBG
-#define SALT_K1_DBG 0
-#endif
-#ifndef SALT_K1_FAST_STORE
-#define SALT_K1_FAST_STORE 1
-#endif
 
 namespace {
 
@@ -51,7 +45,6 @@ struct ConvKP {
     int m_tiles, n_tiles;
     int vt;                          // virtual taps of a 1x1 convolution: vt channel chunks staged per barrier round (1 = off)
     int nbuf;                        // conv_glds_kernel: depth of the LDS chunk ring (2 | 3)
-    int no_perm8;                    // conv_glds_kernel: A/B - natural lane -> pixel order on the 8 x 8 tiles (SALT_GLDS_NO_PERM8)
     int y_small;                     // y / bnb_y / bnb_a hold < 2^31 elements each: the epilogue may use 32-bit offsets
     // BatchNorm-backward sums of the stored tile (saltnet.h, salt_conv_args.bnb_*); bnb_partials == nullptr: off
     const void* bnb_y; const void* bnb_a; int bnb_cs, bnb_acs, bnb_relu;
@@ -279,8 +272,8 @@ __device__ __forceinline__ void conv_epilogue(const ConvKP& p, const TileCoord& 
         // Fast path (whole tile inside the grid, whole aligned channel pieces, no fold): 32-bit offsets, no per-piece bounds / mode
         // tests, fully unrolled so that the LDS reads and (accumulate / BatchNorm-backward) loads of all pieces are in flight together.
         // The general loop below spent ~70 instructions per 16-byte piece: the epilogue of a 9.66-GFLOP layer took 4.5 us of 19 us
-        // WITHOUT its stores (round-2 variant builds: tools/build_variant.sh -DSALT_K1_DBG=n).
-        const bool fast_store = SALT_K1_FAST_STORE && full_tile && !p.fold_fused && !p.strip && y_vec && (n0 + BN <= p.Cout) && p.y_small;
+        // WITHOUT its stores.
+        const bool fast_store = full_tile && !p.fold_fused && !p.strip && y_vec && (n0 + BN <= p.Cout) && p.y_small;
         if (fast_store) {
             const int pc = tid % PPO, n = n0 + pc * VE;
             const bool accum = p.accumulate != 0;
@@ -396,11 +389,7 @@ __device__ __forceinline__ void conv_epilogue(const ConvKP& p, const TileCoord& 
                     for (int e = 0; e < VE; ++e) { f[e] += o[e]; if (p.relu) f[e] = fmaxf(f[e], 0.f); }
                     stored = pack16<T>(f);
                 }
-#if defined(SALT_K1_DBG) && (SALT_K1_DBG & 8)
-                if (stored.x == 0x12345678u && stored.y == 0x9abcdef0u) *reinterpret_cast<u32x4*>(dst) = stored;   // ablation: staging without the stores
-#else
                 *reinterpret_cast<u32x4*>(dst) = stored;
-#endif
                 if (bnb) {                                         // host: bnb implies whole aligned pieces, out_step 1, no strip
                     float g[VE], yc[VE];
                     unpack16<T>(stored, g);
@@ -564,16 +553,6 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(ConvKP p) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 
-    // compile-time ablations (round-2 variant builds: tools/build_variant.sh -DSALT_K1_DBG=n): 1 return after the prologue, 2 no chunk loop, 4 no epilogue
-    if (SALT_K1_DBG & 1) {
-        int t = 0;
-#pragma unroll
-        for (int k = 0; k < MAXA; ++k) t += a_goff[k];
-#pragma unroll
-        for (int i = 0; i < MI; ++i) t += pbase[i];
-        if (t == 0x7fffffff) reinterpret_cast<int*>(p.y)[0] = t;
-        return;
-    }
     const int nbp = p.ntaps * BN * 4;          // weight pieces per chunk
     constexpr int MAXBP = (9 * BN * 4 + 255) / 256;          // weight pieces per thread that fit the register prefetch (<= 9 taps)
 
@@ -721,7 +700,7 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(ConvKP p) {
         } else {
             load_chunk(0);
         }
-        for (int c = 0; c < ((SALT_K1_DBG & 2) ? 0 : p.nchunk); ++c) {
+        for (int c = 0; c < p.nchunk; ++c) {
             __syncthreads();                    // fragment reads of chunk c-1 are done (c == 0: the input transform table is complete)
             if constexpr (INA) {
                 const int ch0 = c * KCE + (tid & 3) * VE;
@@ -792,17 +771,6 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(ConvKP p) {
         }
     }
 
-    if (SALT_K1_DBG & 4) {
-        float tsum = 0.f;
-#pragma unroll
-        for (int i = 0; i < MI; ++i)
-#pragma unroll
-            for (int j = 0; j < NI; ++j)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) tsum += acc[i][j][r];
-        if (tsum == 123.456f) reinterpret_cast<float*>(p.y)[0] = tsum;
-        return;
-    }
     conv_epilogue<T, MI, NI, WM, WN>(p, TileCoord{m_tile, n_tile, oy0, ox0, b0, n0, out_oy, out_ox}, acc, smem);
 }
 
@@ -873,12 +841,6 @@ typedef const __attribute__((address_space(1))) void* glb_void_ptr;
 // halo rows (padded to 16) a tile may have: 128-pixel tiles <= 208 (8x16 pixels + 3x3 halo = 180, two 8x8 images = 200),
 // 256-pixel tiles <= 400 (16x16 + halo = 324, four 8x8 images = 400)
 constexpr int v2_namax(int bm) { return bm <= 128 ? 13 : 25; }
-// compile-time ablation switches of conv_glds_kernel (tools/build_variant.sh -DSALT_V2_DBG=N; 0 in the shipped library):
-// 1 no DMA, 2 no MFMA, 4 no fragment reads, 8 return after the main loop, 16 return after the prologue
-#ifndef SALT_V2_DBG
-#define SALT_V2_DBG 0
-#endif
-constexpr int DBG = SALT_V2_DBG;
 
 template <int MI, int NI, int MB, int KS, int NT>
 __global__ __launch_bounds__(512, 2) void conv_glds_kernel(ConvKP p) {
@@ -974,7 +936,6 @@ __global__ __launch_bounds__(512, 2) void conv_glds_kernel(ConvKP p) {
     }
     // issue slot i of the next chunk into ring slot `buf` (`live` false past the last chunk: zero piece -> scratch, same count)
     auto issue_slot = [&](int i, int buf, bool live) {                   // i is a constant after unrolling
-        if (DBG & 1) return;
         const bool real = live && d_off[i] >= 0;
         const int dst = real ? buf * buf_bytes + d_off[i] : dummy_off;
         const unsigned char* src = live ? d_src[i] : zp;
@@ -984,7 +945,7 @@ __global__ __launch_bounds__(512, 2) void conv_glds_kernel(ConvKP p) {
 
     // ---- fragment addressing
     // conflict-free lane -> pixel order: 16-pixel tile rows (1), 8 x 8 tiles at halo pitch 10 (2)
-    const int perm = p.gen ? 0 : p.tw_log2 == 4 ? 1 : (MI % 2 == 0 && p.tw_log2 == 3 && p.th_log2 == 3 && p.hw == 10 && !p.no_perm8) ? 2 : 0;
+    const int perm = p.gen ? 0 : p.tw_log2 == 4 ? 1 : (MI % 2 == 0 && p.tw_log2 == 3 && p.th_log2 == 3 && p.hw == 10) ? 2 : 0;
     int pbase[MI];
 #pragma unroll
     for (int i = 0; i < MI; ++i) {
@@ -1007,13 +968,6 @@ __global__ __launch_bounds__(512, 2) void conv_glds_kernel(ConvKP p) {
 
     struct Frag { u32x4 a[MI], b[NI]; };
     auto mma_frag = [&](const Frag& f) {
-        if (DBG & 2) {
-#pragma unroll
-            for (int i = 0; i < MI; ++i)
-#pragma unroll
-                for (int j = 0; j < NI; ++j) acc[i][j][0] += __uint_as_float(f.a[i].x ^ f.b[j].y);
-            return;
-        }
 #pragma unroll
         for (int i = 0; i < MI; ++i)
 #pragma unroll
@@ -1034,13 +988,6 @@ __global__ __launch_bounds__(512, 2) void conv_glds_kernel(ConvKP p) {
         auto load_frag = [&](int s, const unsigned char* base, Frag& f) {  // s is a constant after unrolling
             const int tl = (KS == 2) ? (s >> 1) : s;
             const int hx = (KS == 2) ? ((s & 1) << 5) : hx4;
-            if (DBG & 4) {
-#pragma unroll
-                for (int i = 0; i < MI; ++i) f.a[i] = u32x4{(unsigned)tl, 1u, 2u, 3u};
-#pragma unroll
-                for (int j = 0; j < NI; ++j) f.b[j] = u32x4{(unsigned)hx, 5u, 6u, 7u};
-                return;
-            }
 #pragma unroll
             for (int i = 0; i < MI; ++i) f.a[i] = *reinterpret_cast<const u32x4*>(base + (a_addr[tl][i] ^ hx));
 #pragma unroll
@@ -1057,10 +1004,8 @@ __global__ __launch_bounds__(512, 2) void conv_glds_kernel(ConvKP p) {
         for (int c = 0; c < p.nchunk; ++c) {
             // chunk c landed: this wave's share by the counted vmcnt (the nbuf - 2 younger chunks may stay in flight), everybody's
             // by the barrier; the barrier also says every wave is done reading the slot the DMA below overwrites (chunk c-1's)
-            if (!(DBG & 1)) {
-                if (nbuf == 3) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(NS) : "memory");
-                else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            }
+            if (nbuf == 3) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(NS) : "memory");
+            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             asm volatile("" ::: "memory");
             __builtin_amdgcn_s_barrier();
             asm volatile("" ::: "memory");
@@ -1080,7 +1025,7 @@ __global__ __launch_bounds__(512, 2) void conv_glds_kernel(ConvKP p) {
                 for (int u = 0; u < SPS; ++u) if (s * SPS + u < NS) issue_slot(s * SPS + u, fill, live);
                 mma_frag(f0);
                 if (s + 1 < NST) __builtin_amdgcn_sched_group_barrier(0x100, MI + NI, 0);
-                if (!(DBG & 1)) __builtin_amdgcn_sched_group_barrier(0x010, SPS, 0);
+                __builtin_amdgcn_sched_group_barrier(0x010, SPS, 0);
                 __builtin_amdgcn_sched_group_barrier(0x008, MI * NI, 0);
                 if (s + 1 < NST) {
                     if (s + 2 < NST) load_frag(s + 2, base, f0);
@@ -1088,26 +1033,14 @@ __global__ __launch_bounds__(512, 2) void conv_glds_kernel(ConvKP p) {
                     for (int u = 0; u < SPS; ++u) if ((s + 1) * SPS + u < NS) issue_slot((s + 1) * SPS + u, fill, live);
                     mma_frag(f1);
                     if (s + 2 < NST) __builtin_amdgcn_sched_group_barrier(0x100, MI + NI, 0);
-                    if (!(DBG & 1)) __builtin_amdgcn_sched_group_barrier(0x010, SPS, 0);
+                    __builtin_amdgcn_sched_group_barrier(0x010, SPS, 0);
                     __builtin_amdgcn_sched_group_barrier(0x008, MI * NI, 0);
                 }
             }
         }
     };
-    if (DBG & 16) { if (tid == 0 && blockIdx.x == 0x7fffffff) reinterpret_cast<int*>(p.y)[0] = pbase[0] + (int)(size_t)d_src[0] + d_off[1] + b_addr[0]; return; }
     if (taphalf == 0) run(std::integral_constant<int, 0>{}, std::integral_constant<int, T0N>{});
     else run(std::integral_constant<int, T0N>{}, std::integral_constant<int, NT>{});
-    if (DBG & 8) {
-        float tsum = 0.f;
-#pragma unroll
-        for (int i = 0; i < MI; ++i)
-#pragma unroll
-            for (int j = 0; j < NI; ++j)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) tsum += acc[i][j][r];
-        if (tsum == 123.456f) reinterpret_cast<float*>(p.y)[0] = tsum;
-        return;
-    }
 
     // ---- K-slice reduction through LDS (the ring is free): sub-block u of a pixel block is finalised by slice u % KS (NSUB >= KS)
     // or by slice u (NSUB < KS); partial sums are added in ascending slice order whatever the owner is (deterministic)
@@ -1169,15 +1102,6 @@ __global__ __launch_bounds__(512, 2) void conv_glds_kernel(ConvKP p) {
         }
     }
 
-    if (DBG & 32) {
-        float tsum = 0.f;
-#pragma unroll
-        for (int o = 0; o < OWN; ++o)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) tsum += fin[o][r];
-        if (tsum == 123.456f) reinterpret_cast<float*>(p.y)[0] = tsum;
-        return;
-    }
     // ---- epilogue (conv_mfma_kernel's, generalised to "a wave owns OWN 32x32 sub-blocks at (rowoff, coloff)" and 512 threads)
     constexpr int PITCH = BN + 16 / (int)sizeof(T);
     constexpr int PPO = BN / VE;
@@ -1252,7 +1176,6 @@ __global__ __launch_bounds__(512, 2) void conv_glds_kernel(ConvKP p) {
                     bsc[e] = p.bnb_gamma[nb0 + e] * bis[e]; bsh[e] = p.bnb_beta[nb0 + e] - bmu[e] * bsc[e];
                 }
         }
-        if (DBG & 64) { if (sO[tid] == 12345) reinterpret_cast<T*>(p.y)[0] = sO[tid + 1]; return; }
         for (int q = tid; q < BM * PPO; q += NTHR) {
             const int m = q / PPO, pc = q - m * PPO;
             const TilePix tp = tile_pix(p, m);
@@ -1463,11 +1386,8 @@ int make_plan(const salt_conv_args* a, Plan* pl) {
         SALT_FAIL(SALT_E_BADARG, "conv: output grid exceeds buffer");
     if (a->x.B != a->y.B) SALT_FAIL(SALT_E_BADARG, "conv: batch mismatch");
     const int Cout = a->y.C;
-    int min_dy = 1 << 30, max_dy = -(1 << 30), min_dx = 1 << 30, max_dx = -(1 << 30);
-    for (int t = 0; t < a->ntaps; ++t) {
-        min_dy = a->tap_dy[t] < min_dy ? a->tap_dy[t] : min_dy; max_dy = a->tap_dy[t] > max_dy ? a->tap_dy[t] : max_dy;
-        min_dx = a->tap_dx[t] < min_dx ? a->tap_dx[t] : min_dx; max_dx = a->tap_dx[t] > max_dx ? a->tap_dx[t] : max_dx;
-    }
+    const TapBox tb = tap_box(a->tap_dy, a->tap_dx, a->ntaps);
+    const int min_dy = tb.min_dy, max_dy = tb.max_dy, min_dx = tb.min_dx, max_dx = tb.max_dx;
     const int64_t pixels = (int64_t)a->x.B * a->OH * a->OW * (a->nphase > 1 ? a->nphase : 1);
     // 1x1 stride-1 convolution with Cin a multiple of 4 chunks: 4 channel chunks per barrier round (virtual taps, see the kernel)
     const int KCE_ = a->dtype == SALT_F32 ? 16 : 32;
@@ -1486,7 +1406,7 @@ int make_plan(const salt_conv_args* a, Plan* pl) {
     if (id == 0 && v2_ok && v2_env && ((a->cfg & 0xff) == 0 || ((a->cfg & 0xff) >= 9 && (a->cfg & 0xff) <= 13))) {
         if (v2_env >= 6) id = v2_env;
         else {
-            // measured (round-2 variant builds, DESIGN_history.md): the LDS-DMA kernel wins where conv_mfma_kernel's 128x32 tiles cannot
+            // measured (round 2, DESIGN_history.md): the LDS-DMA kernel wins where conv_mfma_kernel's 128x32 tiles cannot
             // fill the chip with 64-channel tiles - the 8x8 maps (2048-3200 pixels, 512-768 channels: 24.0 -> 18.1 us) - ties on the
             // 16x16 / 32x32 maps and loses on the large maps, whose few channel chunks leave nothing to pipeline.  1 (default): the
             // few-pixel layers only; 2: + the 16x16 maps; 3: every eligible layer.
@@ -1543,8 +1463,6 @@ int make_plan(const salt_conv_args* a, Plan* pl) {
             // (halo rows padded to whole 1-KB DMA instructions; 8 KB behind the ring take the surplus slots' copies)
             const int64_t buf = (int64_t)cdiv(phalo, 16) * 1024 + (int64_t)a->ntaps * (32 * cfg->NI) * 64;
             k.nbuf = 3 * buf + 8192 <= 160 * 1024 ? 3 : 2;
-            static const bool no_perm8 = getenv("SALT_GLDS_NO_PERM8") != nullptr;
-            k.no_perm8 = no_perm8 ? 1 : 0;
             if (cdiv(phalo, 16) > v2_namax(BM) || 2 * buf + 8192 > 160 * 1024) {
                 if (attempt == 0 && cfg->id != 8) { for (const auto& c : kCfgs) if (c.id == 8) cfg = &c; continue; }
                 // tiny maps (4 x 4 and below: a 128-pixel tile is 8+ images, each with its own halo ring): conv_mfma_kernel's tiles
@@ -1692,25 +1610,15 @@ int make_plan(const salt_conv_args* a, Plan* pl) {
 
 template <typename T, int MI, int NI, int WM, int WN, int NT, int MAXA_T = 0, bool INA = false>
 int launch_cfg_nt(const Plan& pl, hipStream_t st) {
-    auto kern = conv_mfma_kernel<T, MI, NI, WM, WN, NT, MAXA_T, INA>;
-    static bool attr_set = false;
-    if (pl.lds > 64 * 1024 && !attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) SALT_FAIL((int)e, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-        attr_set = true;
-    }
-    hipLaunchKernelGGL(kern, pl.grid, dim3(256), pl.lds, st, pl.kp);
-    SALT_CHECK_LAUNCH();
-    return SALT_OK;
+    return salt_launch(conv_mfma_kernel<T, MI, NI, WM, WN, NT, MAXA_T, INA>, pl.grid, dim3(256), pl.lds, st, pl.kp);
 }
 
 template <typename T, int MI, int NI, int WM, int WN>
 int launch_cfg(const Plan& pl, hipStream_t st) {
     if constexpr (sizeof(T) == 2 && MI * WM != 2) {                       // bf16, 128- and 256-pixel tiles: interleaved loader
-        static const bool ilv_off = getenv("SALT_CONV_NO_ILV") != nullptr;
         const ConvKP& k = pl.kp;
         const int npa = (k.nb * k.hh * k.hw * k.vt * 4 + 255) >> 8;
-        const bool ok = !ilv_off && k.x_cs % 8 == 0 && k.Cin % 8 == 0 && (reinterpret_cast<uintptr_t>(k.x) & 15) == 0;
+        const bool ok = k.x_cs % 8 == 0 && k.Cin % 8 == 0 && (reinterpret_cast<uintptr_t>(k.x) & 15) == 0;
         if (k.in_scale || k.in_fin.acc) {                                  // input transform: the interleaved 9-tap loader only
             if (!ok || k.ntaps != 9 || k.vt != 1) SALT_FAIL(SALT_E_UNSUPPORTED, "conv: the input transform needs a 9-tap bf16 launch over aligned 16-byte pieces");
             if constexpr (MI * WM == 8) { if (npa <= 6) return launch_cfg_nt<T, MI, NI, WM, WN, 9, 6, true>(pl, st); }
@@ -1737,19 +1645,8 @@ int launch_cfg(const Plan& pl, hipStream_t st) {
 
 template <int MI, int NI, int MB, int KS>
 int launch_glds(const Plan& pl, hipStream_t st) {
-    auto go = [&](auto kern, bool& attr_set) -> int {
-        if (!attr_set) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (e != hipSuccess) SALT_FAIL((int)e, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-            attr_set = true;
-        }
-        hipLaunchKernelGGL(kern, pl.grid, dim3(512), pl.lds, st, pl.kp);
-        SALT_CHECK_LAUNCH();
-        return SALT_OK;
-    };
-    static bool set9 = false, set4 = false;                  // per template instantiation
-    if (pl.kp.ntaps == 9) return go(conv_glds_kernel<MI, NI, MB, KS, 9>, set9);
-    return go(conv_glds_kernel<MI, NI, MB, KS, 4>, set4);
+    if (pl.kp.ntaps == 9) return salt_launch(conv_glds_kernel<MI, NI, MB, KS, 9>, pl.grid, dim3(512), pl.lds, st, pl.kp);
+    return salt_launch(conv_glds_kernel<MI, NI, MB, KS, 4>, pl.grid, dim3(512), pl.lds, st, pl.kp);
 }
 
 template <typename T>
@@ -2282,12 +2179,8 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(WgradKP p) {
 //     destination registers (which made the compiler wait for the loads already in flight) - per piece a few VALU instructions;
 //   * the MFMA operands are swapped (D^T): a lane then owns 4 consecutive b-channels of one a-row, the slab is written with
 //     16-byte stores instead of 4-byte ones.
-
-// ROW16: every k-step is one 16-pixel tile row (tw = 16, th = KS, one image per tile, 18-pixel halo rows, unit step): the halo
-// address of a fragment read is a per-tap lane constant plus a compile-time multiple of the halo row - no address arithmetic.
-template <int NT, int KS, bool PAD, bool ROW16>
+template <int NT, int KS, bool PAD>
 __global__ __launch_bounds__(256) void conv_wgrad_fast_kernel(WgradKP p) {
-    static_assert(!ROW16 || NT == 9, "ROW16 shares pixel runs between the three taps of a 3x3 kernel row");
     typedef bf16_t T;
     constexpr int PPR = 8, ROWB = 192, BMP = KS * 16;
     constexpr int MAXP = BMP * PPR / 256, MAXQ = 10, NPIECE = MAXP + MAXQ;
@@ -2383,9 +2276,9 @@ __global__ __launch_bounds__(256) void conv_wgrad_fast_kernel(WgradKP p) {
     // ---- fragment addressing: ds_read_b64_tr_b16 transposes a [4 pixel][16 channel] block per 16-lane group (conv_wgrad_kernel)
     const int khalf = lane >> 5, g16 = (lane >> 4) & 1, i16 = lane & 15, prow = i16 >> 2, pcol = (i16 & 3) * 4;
     const int pa_base = (khalf * 8 + prow) * ROWB + (wa * 32 + g16 * 16 + pcol) * 2;     // + (16 j + 4 h) rows: an immediate
-    int qaddr[ROW16 ? 2 : KS * 2];                                    // halo-row byte address of pixel 16 j + 8 khalf + 4 h + prow
+    int qaddr[KS * 2];                                                // halo-row byte address of pixel 16 j + 8 khalf + 4 h + prow
 #pragma unroll
-    for (int i = 0; i < (ROW16 ? 2 : KS * 2); ++i) {
+    for (int i = 0; i < KS * 2; ++i) {
         const int m = (i >> 1) * 16 + khalf * 8 + (i & 1) * 4 + prow;
         const int tx = m & ((1 << p.tw_log2) - 1), ty = (m >> p.tw_log2) & ((1 << p.th_log2) - 1), bl = m >> (p.tw_log2 + p.th_log2);
         qaddr[i] = (bl * hhw + ty * p.q_step * p.hw + tx * p.q_step) * ROWB + (wb * 32 + g16 * 16 + pcol) * 2;
@@ -2393,47 +2286,19 @@ __global__ __launch_bounds__(256) void conv_wgrad_fast_kernel(WgradKP p) {
     int tob[NT];
 #pragma unroll
     for (int t = 0; t < NT; ++t) tob[t] = p.tap_off[t] * ROWB;
-    // ROW16: the three taps of a kernel row read overlapping pixel runs, so one run of 12 pixels (three transposed quads per
-    // lane) serves all three: tap dx is the run shifted by dx pixels = dx 16-bit elements (dx = 1: four v_alignbit, dx = 2: a
-    // register offset).  11 LDS reads per k-step instead of 20 - the LDS return path, not the MFMA, bounds this kernel.
-    typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-    struct Frag { s16x4 alo, ahi, blo[ROW16 ? 1 : NT], bhi[ROW16 ? 1 : NT]; u32x2 q[ROW16 ? 3 : 1][3]; };
-    int tq[3];
-    if (ROW16) {
-#pragma unroll
-        for (int dy = 0; dy < 3; ++dy) tq[dy] = (khalf * 8 + prow) * ROWB + (wb * 32 + g16 * 16 + pcol) * 2 + dy * (18 * ROWB);
-    }
+    struct Frag { s16x4 alo, ahi, blo[NT], bhi[NT]; };
     auto read_frags = [&](int j, Frag& fr) {
         fr.alo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(sP + pa_base + (j * 16) * ROWB));
         fr.ahi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(sP + pa_base + (j * 16 + 4) * ROWB));
-        if constexpr (ROW16) {
 #pragma unroll
-            for (int dy = 0; dy < 3; ++dy)
-#pragma unroll
-                for (int u = 0; u < 3; ++u)
-                    fr.q[dy][u] = __builtin_bit_cast(u32x2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(sQ + tq[dy] + (j * 18 + u * 4) * ROWB)));
-        } else {
-#pragma unroll
-            for (int t = 0; t < NT; ++t) {
-                fr.blo[t] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(sQ + qaddr[2 * j] + tob[t]));
-                fr.bhi[t] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(sQ + qaddr[2 * j + 1] + tob[t]));
-            }
+        for (int t = 0; t < NT; ++t) {
+            fr.blo[t] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(sQ + qaddr[2 * j] + tob[t]));
+            fr.bhi[t] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(sQ + qaddr[2 * j + 1] + tob[t]));
         }
     };
     auto b_operand = [&](const Frag& fr, int t) -> bf16x8 {
-        if constexpr (ROW16) {
-            const int dy = t / 3, dx = t - dy * 3;
-            const unsigned w0 = fr.q[dy][0].x, w1 = fr.q[dy][0].y, w2 = fr.q[dy][1].x, w3 = fr.q[dy][1].y, w4 = fr.q[dy][2].x;
-            u32x4 v;
-            if (dx == 0) v = u32x4{w0, w1, w2, w3};
-            else if (dx == 1) v = u32x4{__builtin_amdgcn_alignbit(w1, w0, 16), __builtin_amdgcn_alignbit(w2, w1, 16),
-                                        __builtin_amdgcn_alignbit(w3, w2, 16), __builtin_amdgcn_alignbit(w4, w3, 16)};
-            else v = u32x4{w1, w2, w3, w4};
-            return __builtin_bit_cast(bf16x8, v);
-        } else {
-            const s16x8 bv = {fr.blo[t][0], fr.blo[t][1], fr.blo[t][2], fr.blo[t][3], fr.bhi[t][0], fr.bhi[t][1], fr.bhi[t][2], fr.bhi[t][3]};
-            return __builtin_bit_cast(bf16x8, bv);
-        }
+        const s16x8 bv = {fr.blo[t][0], fr.blo[t][1], fr.blo[t][2], fr.blo[t][3], fr.bhi[t][0], fr.bhi[t][1], fr.bhi[t][2], fr.bhi[t][3]};
+        return __builtin_bit_cast(bf16x8, bv);
     };
 
     TileC cur = decode(split);
@@ -2475,7 +2340,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_fast_kernel(WgradKP p) {
 #pragma unroll
                 for (int t = 0; t < NT; ++t) {
                     __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                    __builtin_amdgcn_sched_group_barrier(0x100, ROW16 ? 1 : 2, 0);
+                    __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
                     if (t < nld) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
                 }
             }
@@ -2497,10 +2362,15 @@ __global__ __launch_bounds__(256) void conv_wgrad_fast_kernel(WgradKP p) {
     }
 }
 
-// 8-wave variant of the ROW16 fast path: the same workgroup tile and LDS layout, but two waves per SIMD - waves 0-3 accumulate
-// taps 0-4, waves 4-7 taps 5-8 (80 / 64 accumulator registers per lane instead of 144) - so that one wave's VMEM / LDS issue
-// stalls (a global_load_dwordx4 costs ~115 cycles of issue time) overlap with the other wave's MFMAs.  Each half reads the pixel
-// runs of the two kernel rows its taps touch (8 LDS reads per k-step) and moves half of the tile pieces.
+// 8-wave 3x3 weight gradient on row tiles: every k-step is one 16-pixel tile row (tw = 16, th = 8, one image per tile, 18-pixel
+// halo rows, unit step), so the halo address of a fragment read is a per-row lane constant plus a compile-time multiple of the
+// halo row - no address arithmetic.  The workgroup tile, LDS layout, branch-free loader and slab stores are those of
+// conv_wgrad_fast_kernel, but two waves share a SIMD - waves 0-3 accumulate taps 0-4, waves 4-7 taps 5-8 (80 / 64 accumulator
+// registers per lane instead of 144) - so that one wave's VMEM / LDS issue stalls (a global_load_dwordx4 costs ~115 cycles of
+// issue time) overlap with the other wave's MFMAs.  The three taps of a kernel row read overlapping pixel runs, so one run of
+// 12 pixels (three transposed quads per lane) serves all three: tap dx is the run shifted by dx pixels = dx 16-bit elements
+// (dx = 1: four v_alignbit, dx = 2: a register offset).  Each half reads the runs of the two kernel rows its taps touch (8 LDS
+// reads per k-step; the LDS return path, not the MFMA, bounds this kernel) and moves half of the tile pieces.
 template <bool PAD>
 __global__ __launch_bounds__(512) void conv_wgrad_fast8_kernel(WgradKP p) {
     typedef bf16_t T;
@@ -2594,7 +2464,7 @@ __global__ __launch_bounds__(512) void conv_wgrad_fast8_kernel(WgradKP p) {
         }
     };
 
-    // ---- fragment addressing (conv_wgrad_fast_kernel, ROW16): this wave half reads kernel rows grp and grp + 1
+    // ---- fragment addressing: this wave half reads the 12-pixel runs of kernel rows grp and grp + 1
     const int khalf = lane >> 5, g16 = (lane >> 4) & 1, i16 = lane & 15, prow = i16 >> 2, pcol = (i16 & 3) * 4;
     const int pa_base = (khalf * 8 + prow) * ROWB + (wa * 32 + g16 * 16 + pcol) * 2;
     int tq[2];
@@ -2689,7 +2559,7 @@ __global__ __launch_bounds__(512) void conv_wgrad_fast8_kernel(WgradKP p) {
     }
 }
 
-// fp32 version of the ROW16 fast path (exact fp32: v_mfma_f32_32x32x2_f32, two pixels per k-step, 64 k-steps per 128-pixel tile).
+// fp32 3x3 weight gradient on row tiles (tw = 16, th = 8, one image per tile, 18-pixel halo rows, unit step; exact fp32: v_mfma_f32_32x32x2_f32, two pixels per k-step, 64 k-steps per 128-pixel tile).
 // LDS rows are 64 channels x 4 B; a fragment read is one dword per lane (lanes = consecutive channels: conflict free) at a per-tap
 // lane constant plus a compile-time offset of the k-step, so the unrolled loop has no address arithmetic; the branch-free loader and
 // the 16-byte slab stores are those of conv_wgrad_fast_kernel.  The generic kernel spent ~34 us per tile here, most of it on one
@@ -2905,11 +2775,8 @@ int wgrad_plan(const salt_conv_wgrad_args* a, WgradKP* k, int* nsplit_out) {
     }
     if (a->ntaps < 1 || a->ntaps > 9) SALT_FAIL(SALT_E_BADARG, "wgrad: ntaps %d (max 9 per launch)", a->ntaps);
     if (a->p.B != a->q.B) SALT_FAIL(SALT_E_BADARG, "wgrad: batch mismatch");
-    int min_dy = 1 << 30, max_dy = -(1 << 30), min_dx = 1 << 30, max_dx = -(1 << 30);
-    for (int t = 0; t < a->ntaps; ++t) {
-        min_dy = a->tap_dy[t] < min_dy ? a->tap_dy[t] : min_dy; max_dy = a->tap_dy[t] > max_dy ? a->tap_dy[t] : max_dy;
-        min_dx = a->tap_dx[t] < min_dx ? a->tap_dx[t] : min_dx; max_dx = a->tap_dx[t] > max_dx ? a->tap_dx[t] : max_dx;
-    }
+    const TapBox tb = tap_box(a->tap_dy, a->tap_dx, a->ntaps);
+    const int min_dy = tb.min_dy, max_dy = tb.max_dy, min_dx = tb.min_dx, max_dx = tb.max_dx;
     const int rowb = a->dtype == SALT_F32 ? 256 : 192;
     int th = 1, tw = 1;
     for (int bmp = 128; bmp >= 32; bmp >>= 1) {
@@ -3118,15 +2985,7 @@ extern "C" int salt_adam_pack(const salt_adam_pack_args* a, void* stream) {
     k.p = a->param; k.g = a->grad; k.m = a->exp_avg; k.v = a->exp_avg_sq; k.hyper = a->hyper;
     k.jobs = reinterpret_cast<const salt_pack_conv_weight_args*>(a->jobs); k.job_block0 = a->job_block0; k.njobs = a->njobs; k.pack_blocks = a->pack_blocks;
     k.rest = a->rest; k.rest_block0 = a->rest_block0; k.nrest = a->nrest;
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(adam_pack_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) SALT_FAIL((int)e, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-        attr_set = true;
-    }
-    hipLaunchKernelGGL(adam_pack_kernel, dim3((unsigned)blocks), dim3(256), AP_SEG * AP_SEGF * sizeof(float), (hipStream_t)stream, k);
-    SALT_CHECK_LAUNCH();
-    return SALT_OK;
+    return salt_launch(adam_pack_kernel, dim3((unsigned)blocks), dim3(256), AP_SEG * AP_SEGF * sizeof(float), (hipStream_t)stream, k);
 }
 
 extern "C" int salt_pack_batched(const salt_pack_batched_args* a, void* stream) {
@@ -3171,18 +3030,10 @@ static int launch_wgrad(const WgradKP& k, hipStream_t st) {
             for (int t = 0; t < 9; ++t) row16 = row16 && k.tap_off[t] == (t / 3) * 18 + t % 3;       // raster tap order
             if (row16) {
                 auto kern8 = k.pad_mode ? conv_wgrad_fast8_kernel<true> : conv_wgrad_fast8_kernel<false>;
-                if (lds > 64 * 1024) { hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern8), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-                    if (e != hipSuccess) SALT_FAIL((int)e, "hipFuncSetAttribute: %s", hipGetErrorString(e)); }
-                hipLaunchKernelGGL(kern8, grid, dim3(512), lds, st, k);
-                SALT_CHECK_LAUNCH();
-                return SALT_OK;
+                return salt_launch(kern8, grid, dim3(512), lds, st, k);
             }
-            auto kern = k.pad_mode ? conv_wgrad_fast_kernel<9, 8, true, false> : conv_wgrad_fast_kernel<9, 8, false, false>;
-            if (lds > 64 * 1024) { hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-                if (e != hipSuccess) SALT_FAIL((int)e, "hipFuncSetAttribute: %s", hipGetErrorString(e)); }
-            hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, k);
-            SALT_CHECK_LAUNCH();
-            return SALT_OK;
+            auto kern = k.pad_mode ? conv_wgrad_fast_kernel<9, 8, true> : conv_wgrad_fast_kernel<9, 8, false>;
+            return salt_launch(kern, grid, dim3(256), lds, st, k);
         }
         // round 3: the stride-2 3x3 layers (ResNet layer2-4 conv1): their halo (17 x 17 pixels for an 8 x 8 tile) only leaves room for
         // 64-pixel K tiles, which used to send them to the generic kernel (51 us at 94 TFLOP/s); the fast kernel with 4 k-steps per tile
@@ -3196,21 +3047,13 @@ static int launch_wgrad(const WgradKP& k, hipStream_t st) {
                            k.nb * k.hh * k.hw * 8 <= 10 * 256;
         if (fast1) {
             SALT_WGRAD_PROBE(3)
-            auto kern = k.bmp == 64 ? conv_wgrad_fast_kernel<1, 4, false, false> : conv_wgrad_fast_kernel<1, 8, false, false>;
-            if (lds > 64 * 1024) { hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-                if (e != hipSuccess) SALT_FAIL((int)e, "hipFuncSetAttribute: %s", hipGetErrorString(e)); }
-            hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, k);
-            SALT_CHECK_LAUNCH();
-            return SALT_OK;
+            auto kern = k.bmp == 64 ? conv_wgrad_fast_kernel<1, 4, false> : conv_wgrad_fast_kernel<1, 8, false>;
+            return salt_launch(kern, grid, dim3(256), lds, st, k);
         }
         if (fast64) {
             SALT_WGRAD_PROBE(3)
-            auto kern = k.pad_mode ? conv_wgrad_fast_kernel<9, 4, true, false> : conv_wgrad_fast_kernel<9, 4, false, false>;
-            if (lds > 64 * 1024) { hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-                if (e != hipSuccess) SALT_FAIL((int)e, "hipFuncSetAttribute: %s", hipGetErrorString(e)); }
-            hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, k);
-            SALT_CHECK_LAUNCH();
-            return SALT_OK;
+            auto kern = k.pad_mode ? conv_wgrad_fast_kernel<9, 4, true> : conv_wgrad_fast_kernel<9, 4, false>;
+            return salt_launch(kern, grid, dim3(256), lds, st, k);
         }
     }
     if constexpr (sizeof(T) == 4) {
@@ -3225,11 +3068,7 @@ static int launch_wgrad(const WgradKP& k, hipStream_t st) {
             if (a32 && b32) kern = k.pad_mode ? conv_wgrad_fast32_kernel<true, 4, 0> : conv_wgrad_fast32_kernel<false, 4, 0>;
             else if (a32) kern = k.pad_mode ? conv_wgrad_fast32_kernel<true, 2, 0> : conv_wgrad_fast32_kernel<false, 2, 0>;
             else if (b32) kern = k.pad_mode ? conv_wgrad_fast32_kernel<true, 2, 1> : conv_wgrad_fast32_kernel<false, 2, 1>;
-            if (lds > 64 * 1024) { hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-                if (e != hipSuccess) SALT_FAIL((int)e, "hipFuncSetAttribute: %s", hipGetErrorString(e)); }
-            hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, k);
-            SALT_CHECK_LAUNCH();
-            return SALT_OK;
+            return salt_launch(kern, grid, dim3(256), lds, st, k);
         }
     }
     SALT_WGRAD_PROBE(5)
@@ -3240,17 +3079,8 @@ static int launch_wgrad(const WgradKP& k, hipStream_t st) {
             kg.ksplit = (a32 && b32) ? 4 : (a32 ? 2 : (b32 ? 3 : 0));
         }
     }
-#define SALT_WG(NT) { auto kern = conv_wgrad_kernel<T, NT>; \
-        if (lds > 64 * 1024) { hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-            if (e != hipSuccess) SALT_FAIL((int)e, "hipFuncSetAttribute: %s", hipGetErrorString(e)); } \
-        hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, kg); }
-    if (k.ntaps == 1) SALT_WG(1)
-    else if (k.ntaps <= 3) SALT_WG(3)
-    else if (k.ntaps == 4) SALT_WG(4)
-    else SALT_WG(9)
-#undef SALT_WG
-    SALT_CHECK_LAUNCH();
-    return SALT_OK;
+    auto kern = k.ntaps == 1 ? conv_wgrad_kernel<T, 1> : k.ntaps <= 3 ? conv_wgrad_kernel<T, 3> : k.ntaps == 4 ? conv_wgrad_kernel<T, 4> : conv_wgrad_kernel<T, 9>;
+    return salt_launch(kern, grid, dim3(256), lds, st, kg);
 }
 
 extern "C" int salt_conv_wgrad_kernel_id(const salt_conv_wgrad_args* a) {

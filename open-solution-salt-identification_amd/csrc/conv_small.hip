@@ -616,13 +616,7 @@ extern "C" int salt_conv_first(const salt_conv_first_args* a, void* stream) {
     const size_t lds = sizeof(float) * ((size_t)p.Cin * p.halo * p.halo + (size_t)p.K * p.K * p.Cin * CoutP + 64);
     if (lds > 160 * 1024) SALT_FAIL(SALT_E_LDS, "conv_first: needs %zu bytes of LDS", lds);
     const dim3 grid((unsigned)(p.B * p.tiles_y * p.tiles_x));
-    SALT_DISPATCH_DTYPE(a->dtype, T, {
-        auto kern = conv_first_kernel<T>;
-        if (lds > 64 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        hipLaunchKernelGGL(kern, grid, dim3(256), lds, (hipStream_t)stream, p);
-    })
-    SALT_CHECK_LAUNCH();
-    return SALT_OK;
+    SALT_DISPATCH_DTYPE(a->dtype, T, return salt_launch(conv_first_kernel<T>, grid, dim3(256), lds, (hipStream_t)stream, p))
 }
 
 extern "C" int salt_conv_first_wgrad_parts(const salt_conv_first_wgrad_args* a) {
@@ -655,10 +649,9 @@ extern "C" int salt_conv_first_wgrad(const salt_conv_first_wgrad_args* a, void* 
     SALT_DISPATCH_DTYPE(a->dtype, T, {
         auto kern = p.per <= 1 ? conv_first_wgrad_kernel<T, 1> : p.per <= 4 ? conv_first_wgrad_kernel<T, 4> : p.per <= 12 ? conv_first_wgrad_kernel<T, 12>
                                                                                                                  : conv_first_wgrad_kernel<T, MAXKK>;
-        if (lds > 64 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        hipLaunchKernelGGL(kern, dim3(nparts), dim3(256), lds, (hipStream_t)stream, p);
+        const int rc = salt_launch(kern, dim3(nparts), dim3(256), lds, (hipStream_t)stream, p);
+        if (rc) return rc;
     })
-    SALT_CHECK_LAUNCH();
     const int64_t n = (int64_t)Cout * KKC;
     if (nparts >= 64 && n <= 4096) hipLaunchKernelGGL(partial_sum_wide_kernel, dim3((unsigned)n), dim3(256), 0, (hipStream_t)stream, a->partials, nparts, n, a->grad, a->accumulate);
     else hipLaunchKernelGGL(partial_sum_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a->partials, nparts, n, a->grad, a->accumulate);

@@ -14,7 +14,6 @@
 //     atomics per workgroup), 2 (+)= and the BatchNorm-backward sums of the stored gradient.
 #include "common.h"
 
-#include <cstdlib>
 
 namespace {
 
@@ -394,22 +393,13 @@ template <int CI, int CO, int MODE, int NT = 9, int PH = 1>
 int thin_launch_mode(const ThKP& k, hipStream_t st) {
     constexpr int LDS = PH * CI * NT * CO * 1024 + 2 * CI * 21 * 1024 + 1024 + 4 * 16 * CO * 4;
     static_assert(LDS <= 160 * 1024 && 4 * 2 * 16 * CO * 4 <= PH * CI * NT * CO * 1024, "LDS budget");
-    auto kern = conv_thin_kernel<CI, CO, MODE, NT, PH>;
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) SALT_FAIL((int)e, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-        attr_set = true;
-    }
     int per_cu = (160 * 1024) / LDS;
     constexpr int cap_env = 2;
     if (per_cu > cap_env) per_cu = cap_env;
     if (per_cu < 1) per_cu = 1;
     int wgs = thin_cus() * per_cu;
     if (wgs > k.ntiles) wgs = k.ntiles;
-    hipLaunchKernelGGL(kern, dim3((unsigned)wgs), dim3(256), LDS, st, k);
-    SALT_CHECK_LAUNCH();
-    return SALT_OK;
+    return salt_launch(conv_thin_kernel<CI, CO, MODE, NT, PH>, dim3((unsigned)wgs), dim3(256), LDS, st, k);
 }
 
 template <int CI, int CO>
@@ -425,16 +415,14 @@ int thin_launch(const ThKP& k, hipStream_t st) {
 
 }  // namespace
 
-// ---- host interface (conv_mfma.hip: salt_conv / salt_conv_kernel_id).  SALT_CONV_THIN = 0: off unless asked for per launch
-// (cfg & 0xff == 12).  Returns 0 (not applicable) or 4 CI + CO.
+// ---- host interface (conv_mfma.hip: salt_conv / salt_conv_kernel_id).  cfg & 0xff == 12 asks for this kernel wherever it applies
+// (tests).  Returns 0 (not applicable) or 4 CI + CO.
 int conv_thin_variant(const salt_conv_args* a) {
-    static const int env = getenv("SALT_CONV_THIN") ? atoi(getenv("SALT_CONV_THIN")) : 1;
     if (!a || a->dtype != SALT_F32) return 0;
     const bool phased = a->nphase > 1;           // the phase-fused launch of a stride-2 transposed convolution (4 taps, 4 phases, out_step 2)
     if (a->ntaps != (phased ? 4 : 9)) return 0;
     const bool asked = (a->cfg & 0xff) == 12;
     if ((a->cfg & 0xff) != 0 && !asked) return 0;
-    if (!asked && !env) return 0;
     if (a->in_step != 1 || a->out_oy || a->out_ox) return 0;
     if (phased ? (a->nphase != 4 || a->out_step != 2 || a->bnb_acc || a->accumulate ||
                   a->w_phase_elems != (int64_t)(a->x.C / 16) * 4 * a->y.C * 16 || a->y.H != 2 * a->OH || a->y.W != 2 * a->OW)
@@ -445,12 +433,8 @@ int conv_thin_variant(const salt_conv_args* a) {
     const int Cin = a->x.C, Cout = a->y.C;
     if ((Cin != 16 && Cin != 32) || (Cout != 16 && Cout != 32)) return 0;
     if (a->x.B != a->y.B || a->OH % 16 || a->OW % 16) return 0;
-    int min_dy = 1 << 30, max_dy = -(1 << 30), min_dx = 1 << 30, max_dx = -(1 << 30);
-    for (int t = 0; t < a->ntaps; ++t) {
-        min_dy = a->tap_dy[t] < min_dy ? a->tap_dy[t] : min_dy; max_dy = a->tap_dy[t] > max_dy ? a->tap_dy[t] : max_dy;
-        min_dx = a->tap_dx[t] < min_dx ? a->tap_dx[t] : min_dx; max_dx = a->tap_dx[t] > max_dx ? a->tap_dx[t] : max_dx;
-    }
-    if (max_dy - min_dy > 2 || max_dx - min_dx > 2) return 0;
+    const TapBox tb = tap_box(a->tap_dy, a->tap_dx, a->ntaps);
+    if (tb.max_dy - tb.min_dy > 2 || tb.max_dx - tb.min_dx > 2) return 0;
     if (a->x.cs % 4 || a->y.cs % 4 || ((reinterpret_cast<uintptr_t>(a->x.p) | reinterpret_cast<uintptr_t>(a->y.p) | reinterpret_cast<uintptr_t>(a->w)) & 15)) return 0;
     auto small = [&](const salt_view& v) { return !v.p || (int64_t)v.B * v.H * v.W * v.cs < (int64_t)1 << 31; };
     if (!small(a->x) || !small(a->y) || !small(a->bnb_y) || !small(a->bnb_a)) return 0;
@@ -474,8 +458,8 @@ int conv_thin_launch(const salt_conv_args* a, hipStream_t st) {
     k.B = a->x.B; k.H = a->x.H; k.W = a->x.W; k.x_cs = a->x.cs; k.y_cs = a->y.cs; k.OH = a->OH; k.OW = a->OW;
     k.yH = a->y.H; k.yW = a->y.W; k.out_step = a->out_step;
     k.tiles_x = a->OW / 16; k.tiles_y = a->OH / 16; k.ntiles = a->y.B * k.tiles_x * k.tiles_y;
-    int min_dy = 1 << 30, min_dx = 1 << 30;
-    for (int t = 0; t < a->ntaps; ++t) { min_dy = a->tap_dy[t] < min_dy ? a->tap_dy[t] : min_dy; min_dx = a->tap_dx[t] < min_dx ? a->tap_dx[t] : min_dx; }
+    const TapBox tb = tap_box(a->tap_dy, a->tap_dx, a->ntaps);
+    const int min_dy = tb.min_dy, min_dx = tb.min_dx;
     k.min_dy = min_dy; k.min_dx = min_dx; k.pad_mode = a->pad_mode;
     for (int t = 0; t < 9; ++t) k.tap_off[t] = t < a->ntaps ? (a->tap_dy[t] - min_dy) * 18 + (a->tap_dx[t] - min_dx) : 0;
     k.relu = a->relu; k.accumulate = a->accumulate;
@@ -494,37 +478,24 @@ int conv_thin_launch(const salt_conv_args* a, hipStream_t st) {
 }
 
 // ---- weight gradient of the same layers (conv_mfma.hip: salt_conv_wgrad_nsplit / salt_conv_wgrad).  Returns 0 (not one of its shapes)
-// or the number of slabs it writes; launch: also enqueues it (*rc = status).  SALT_WGRAD_THIN = 0: off.
+// or the number of slabs it writes; launch: also enqueues it (*rc = status).
 namespace {
 template <int AB, int BB, int QS>
 int tw_launch(const TwKP& k, int wgs, hipStream_t st) {
     constexpr int LDS = 2 * (AB * (QS == 1 ? 16 : 8) + BB * (QS == 1 ? 21 : 36)) * 1024 + 1024;
     static_assert(LDS <= 160 * 1024 && 4 * 9 * 16 * AB * 16 * BB * 4 <= LDS, "LDS budget");
-    auto kern = conv_wgrad_thin_kernel<AB, BB, QS>;
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) SALT_FAIL((int)e, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-        attr_set = true;
-    }
-    hipLaunchKernelGGL(kern, dim3((unsigned)wgs), dim3(256), LDS, st, k);
-    SALT_CHECK_LAUNCH();
-    return SALT_OK;
+    return salt_launch(conv_wgrad_thin_kernel<AB, BB, QS>, dim3((unsigned)wgs), dim3(256), LDS, st, k);
 }
 }  // namespace
 
 int conv_wgrad_thin(const salt_conv_wgrad_args* a, bool launch, hipStream_t st, int* rc) {
-    static const int env = getenv("SALT_WGRAD_THIN") ? atoi(getenv("SALT_WGRAD_THIN")) : 1;
-    if (!a || !env || a->dtype != SALT_F32 || a->ntaps != 9 || (a->q_step != 1 && a->q_step != 2) || a->q_plane) return 0;
+    if (!a || a->dtype != SALT_F32 || a->ntaps != 9 || (a->q_step != 1 && a->q_step != 2) || a->q_plane) return 0;
     if (!view_ok(a->p) || !view_ok(a->q) || a->p.B != a->q.B) return 0;
     const int Ca = a->p.C, Cb = a->q.C, qs = a->q_step, tr = qs == 1 ? 16 : 8;
     if ((Ca != 16 && Ca != 32) || (Cb != 16 && Cb != 32) || a->p.H % tr || a->p.W % 16 || (qs == 2 && Cb != 16)) return 0;
-    int min_dy = 1 << 30, max_dy = -(1 << 30), min_dx = 1 << 30, max_dx = -(1 << 30);
-    for (int t = 0; t < 9; ++t) {
-        min_dy = a->tap_dy[t] < min_dy ? a->tap_dy[t] : min_dy; max_dy = a->tap_dy[t] > max_dy ? a->tap_dy[t] : max_dy;
-        min_dx = a->tap_dx[t] < min_dx ? a->tap_dx[t] : min_dx; max_dx = a->tap_dx[t] > max_dx ? a->tap_dx[t] : max_dx;
-    }
-    if (max_dy - min_dy > 2 || max_dx - min_dx > 2) return 0;
+    const TapBox tb = tap_box(a->tap_dy, a->tap_dx, 9);
+    const int min_dy = tb.min_dy, min_dx = tb.min_dx;
+    if (tb.max_dy - min_dy > 2 || tb.max_dx - min_dx > 2) return 0;
     if (a->p.cs % 4 || a->q.cs % 4 || ((reinterpret_cast<uintptr_t>(a->p.p) | reinterpret_cast<uintptr_t>(a->q.p)) & 15)) return 0;
     if ((int64_t)a->p.B * a->p.H * a->p.W * a->p.cs >= (int64_t)1 << 31 || (int64_t)a->q.B * a->q.H * a->q.W * a->q.cs >= (int64_t)1 << 31) return 0;
     const int ntiles = a->p.B * (a->p.H / tr) * (a->p.W / 16);

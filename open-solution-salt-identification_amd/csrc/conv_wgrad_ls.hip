@@ -519,16 +519,7 @@ int wl_launch_inst(const WlKP& k, hipStream_t st) {
     constexpr int TW = 16 / NB, HP = ST == 2 ? 18 : NB * (TW + 2);
     constexpr int SLOT = KU * 16 * 128 + (ST == 2 ? 4 : 1) * KU * HP * 128, NS = ST == 2 ? SALT_WL_NS2S : (KU == 4 ? SALT_WL_NS4 : SALT_WL_NS8);
     constexpr int LDS = NS * SLOT + 1024;
-    auto kern = conv_wgrad_ls_kernel<PAD, NB, KU, ST>;
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) SALT_FAIL((int)e, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-        attr_set = true;
-    }
-    hipLaunchKernelGGL(kern, dim3((unsigned)(8 * k.per_xcd)), dim3(512), LDS, st, k);
-    SALT_CHECK_LAUNCH();
-    return SALT_OK;
+    return salt_launch(conv_wgrad_ls_kernel<PAD, NB, KU, ST>, dim3((unsigned)(8 * k.per_xcd)), dim3(512), LDS, st, k);
 }
 
 }  // namespace

@@ -31,7 +31,6 @@
 // Scope (host: conv_ws_eligible): bf16, 9 taps inside a 3 x 3 window, unit steps, Cin in {32, 64}, Cout in {32, 64}, output grid a
 // multiple of 16 x 16 and equal to y, zero or replicate (clamp) padding, bias / folded BN / ReLU / accumulate / statistics shards /
 // BatchNorm-backward shards.  Everything else stays on conv_mfma_kernel.
-#include <cstdlib>
 #include <type_traits>
 #include "common.h"
 
@@ -616,16 +615,7 @@ int ws_launch_mode(const WsKP& k, hipStream_t st) {
     constexpr int BN = 32 * NI, HP = NCH * 21, WP = NCH * 9 * BN / 16;
     constexpr int LDS = WP * 1024 + 2 * HP * 1024 + 1024 + 4 * BN * 4;
     static_assert(LDS <= 160 * 1024 && 8 * 2 * BN * 4 <= WP * 1024, "LDS budget");
-    auto kern = conv_ws_kernel<NCH, NI, MODE, FOLD>;
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) SALT_FAIL((int)e, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-        attr_set = true;
-    }
-    hipLaunchKernelGGL(kern, dim3((unsigned)(k.slots * k.n_tiles * 8)), dim3(512), LDS, st, k);
-    SALT_CHECK_LAUNCH();
-    return SALT_OK;
+    return salt_launch(conv_ws_kernel<NCH, NI, MODE, FOLD>, dim3((unsigned)(k.slots * k.n_tiles * 8)), dim3(512), LDS, st, k);
 }
 
 template <int NCH, int NI>
@@ -949,16 +939,7 @@ int ls_launch_mode(const LsKP& k, int wgs, hipStream_t st) {
     constexpr int BN = 32 * NI, PC = MT * 21 + 9 * BN / 16, D = NI == 1 ? SALT_LS_D1 : 2;
     constexpr int LDS = D * PC * 1024 + 1024 + 4 * BN * 4;
     static_assert(LDS <= 160 * 1024, "LDS budget");
-    auto kern = conv_ls_kernel<NI, MODE, SALT_LS_NLW, MT>;
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) SALT_FAIL((int)e, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-        attr_set = true;
-    }
-    hipLaunchKernelGGL(kern, dim3((unsigned)wgs), dim3(256 + 64 * SALT_LS_NLW), LDS, st, k);
-    SALT_CHECK_LAUNCH();
-    return SALT_OK;
+    return salt_launch(conv_ls_kernel<NI, MODE, SALT_LS_NLW, MT>, dim3((unsigned)wgs), dim3(256 + 64 * SALT_LS_NLW), LDS, st, k);
 }
 
 template <int NI>
@@ -1353,31 +1334,14 @@ int xs_launch(const XsKP& k, int wgs, hipStream_t st) {
     const bool affine = k.bias || k.scale || k.shift || k.relu;
     const int lds = k.nsc * 32 * 1024 + 3 * 8 * 1024 + 1024 + (affine ? k.n_blocks : 1) * 4 * 64 * 4;
     if (lds > 160 * 1024) SALT_FAIL(SALT_E_LDS, "conv1x1_xs: %d bytes of LDS", lds);
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv1x1_xs_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) SALT_FAIL((int)e, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-        attr_set = true;
-    }
-    hipLaunchKernelGGL(conv1x1_xs_kernel, dim3((unsigned)wgs), dim3(512), lds, st, k);
-    SALT_CHECK_LAUNCH();
-    return SALT_OK;
+    return salt_launch(conv1x1_xs_kernel, dim3((unsigned)wgs), dim3(512), lds, st, k);
 }
 
 template <int NI, int MODE>
 int l1_launch_mode(const L1KP& k, int wgs, hipStream_t st) {
     constexpr int BN = 32 * NI, PC = 32 + 2 * BN / 16, D = NI == 1 ? 4 : 3;
     constexpr int LDS = D * PC * 1024 + 1024 + 4 * BN * 4;
-    auto kern = conv1x1_ls_kernel<NI, MODE>;
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) SALT_FAIL((int)e, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-        attr_set = true;
-    }
-    hipLaunchKernelGGL(kern, dim3((unsigned)wgs), dim3(512), LDS, st, k);
-    SALT_CHECK_LAUNCH();
-    return SALT_OK;
+    return salt_launch(conv1x1_ls_kernel<NI, MODE>, dim3((unsigned)wgs), dim3(512), LDS, st, k);
 }
 
 template <int NI>
@@ -1532,18 +1496,15 @@ int stem16_launch_mode(const S16KP& k, hipStream_t st) {
 }  // namespace
 
 // ---- host interface (conv_mfma.hip: salt_conv / salt_conv_stats_parts try this first)
-// SALT_CONV_WS = 0: off unless asked for per launch; 1 (default): on for launches with at least half a tile per CU.
-// cfg & 0xff == 9 asks for this kernel wherever it applies, whatever the tile count (tests); cfg >> 8 (if non-zero) caps the
+// On for launches with at least half a tile per CU.  cfg & 0xff == 9 asks for this kernel wherever it applies, whatever the tile count (tests); cfg >> 8 (if non-zero) caps the
 // workgroups per XCD, so that small test tensors exercise the multi-tile pipeline.  A launch it does not apply to falls back to
 // conv_mfma_kernel's own heuristic; salt_conv_kernel_id tells which kernel a launch gets.
 int conv_ws_tiles(const salt_conv_args* a);
 
 bool conv_ws_eligible(const salt_conv_args* a) {
-    static const int env = getenv("SALT_CONV_WS") ? atoi(getenv("SALT_CONV_WS")) : 1;
     if (!a || a->dtype != SALT_BF16) return false;
     const bool asked = (a->cfg & 0xff) == 9;
     if ((a->cfg & 0xff) != 0 && !asked) return false;
-    if (!asked && !env) return false;
     if (a->ntaps != 9 || a->in_step != 1 || a->out_step != 1 || a->out_oy || a->out_ox || a->nphase > 1) return false;
     // plain launches, or the FUSED fold of a 3x3 replicate-padded convolution's data gradient (two pad rows on top, two columns right)
     const bool fold = !a->strip && (a->fold_top || a->fold_right);
@@ -1567,12 +1528,8 @@ bool conv_ws_eligible(const salt_conv_args* a) {
     if (a->x.cs % 8 || a->y.cs % 8 || ((reinterpret_cast<uintptr_t>(a->x.p) | reinterpret_cast<uintptr_t>(a->y.p) | reinterpret_cast<uintptr_t>(a->w)) & 15)) return false;
     if (a->x.B != a->y.B) return false;
     if (a->fin_acc && (a->OH % 16 || a->OW % 16)) return false;           // forward statistics: whole tiles only (no per-pixel mask there)
-    int min_dy = 1 << 30, max_dy = -(1 << 30), min_dx = 1 << 30, max_dx = -(1 << 30);
-    for (int t = 0; t < 9; ++t) {
-        min_dy = a->tap_dy[t] < min_dy ? a->tap_dy[t] : min_dy; max_dy = a->tap_dy[t] > max_dy ? a->tap_dy[t] : max_dy;
-        min_dx = a->tap_dx[t] < min_dx ? a->tap_dx[t] : min_dx; max_dx = a->tap_dx[t] > max_dx ? a->tap_dx[t] : max_dx;
-    }
-    if (max_dy - min_dy != 2 || max_dx - min_dx != 2) return false;
+    const TapBox tb = tap_box(a->tap_dy, a->tap_dx, 9);
+    if (tb.max_dy - tb.min_dy != 2 || tb.max_dx - tb.min_dx != 2) return false;
     auto small = [](const salt_view& v) { return !v.p || (int64_t)v.B * v.H * v.W * v.cs < (int64_t)1 << 31; };
     if (!small(a->x) || !small(a->y) || !small(a->bnb_y) || !small(a->bnb_a) || !small(a->res)) return false;
     if (a->res.p && (a->res.cs % 8 || (reinterpret_cast<uintptr_t>(a->res.p) & 15) || a->accumulate || a->fin_acc || a->bnb_acc || fold)) return false;
@@ -1603,8 +1560,8 @@ int conv_ws_launch(const salt_conv_args* a, hipStream_t st) {
     // fused fold: tile columns are RIGHT-aligned with the extended grid, so that the two pad columns share a tile (and a wave) with the
     // last image column; rows start at 0: the two pad rows share the first tile row's first wave with image row 0
     k.ox_shift = a->fold_right ? k.tiles_x * 16 - a->OW : 0;
-    int min_dy = 1 << 30, min_dx = 1 << 30;
-    for (int t = 0; t < 9; ++t) { min_dy = a->tap_dy[t] < min_dy ? a->tap_dy[t] : min_dy; min_dx = a->tap_dx[t] < min_dx ? a->tap_dx[t] : min_dx; }
+    const TapBox tb = tap_box(a->tap_dy, a->tap_dx, 9);
+    const int min_dy = tb.min_dy, min_dx = tb.min_dx;
     k.min_dy = min_dy; k.min_dx = min_dx; k.pad_mode = a->pad_mode;
     for (int t = 0; t < 9; ++t) k.tap_off[t] = (a->tap_dy[t] - min_dy) * 18 + (a->tap_dx[t] - min_dx);
     k.relu = a->relu; k.accumulate = a->accumulate;
@@ -1630,7 +1587,7 @@ int conv_ws_launch(const salt_conv_args* a, hipStream_t st) {
     SALT_FAIL(SALT_E_BADARG, "conv_ws: channels %d -> %d", Cin, Cout);
 }
 
-// ---- conv_ls_kernel host side.  SALT_CONV_LS = 0: off unless asked for per launch (cfg & 0xff == 10); 1 (default): on.
+// ---- conv_ls_kernel host side.  cfg & 0xff == 10 asks for this kernel wherever it applies (tests).
 // Returns NI (1 | 2) when the launch runs on conv_ls_kernel, else 0.
 static int ls_common_ok(const salt_conv_args* a) {
     if (!a || a->dtype != SALT_BF16) return 0;
@@ -1644,12 +1601,8 @@ static int ls_common_ok(const salt_conv_args* a) {
     if (a->x_plane && (a->x.cs != 64 || Cin % 64 || a->x_plane % 8 || a->x_plane < (int64_t)a->x.B * a->x.H * a->x.W * 64)) return 0;
     if (a->x.cs % 8 || a->y.cs % 8 || ((reinterpret_cast<uintptr_t>(a->x.p) | reinterpret_cast<uintptr_t>(a->y.p) | reinterpret_cast<uintptr_t>(a->w)) & 15)) return 0;
     if (a->OH != a->y.H || a->OW != a->y.W || a->OH % 16 || a->OW % 16 || a->x.B != a->y.B) return 0;
-    int min_dy = 1 << 30, max_dy = -(1 << 30), min_dx = 1 << 30, max_dx = -(1 << 30);
-    for (int t = 0; t < 9; ++t) {
-        min_dy = a->tap_dy[t] < min_dy ? a->tap_dy[t] : min_dy; max_dy = a->tap_dy[t] > max_dy ? a->tap_dy[t] : max_dy;
-        min_dx = a->tap_dx[t] < min_dx ? a->tap_dx[t] : min_dx; max_dx = a->tap_dx[t] > max_dx ? a->tap_dx[t] : max_dx;
-    }
-    if (max_dy - min_dy != 2 || max_dx - min_dx != 2) return 0;
+    const TapBox tb = tap_box(a->tap_dy, a->tap_dx, 9);
+    if (tb.max_dy - tb.min_dy != 2 || tb.max_dx - tb.min_dx != 2) return 0;
     auto small = [](const salt_view& v) { return !v.p || (int64_t)v.B * v.H * v.W * v.cs < (int64_t)1 << 31; };
     // x: the loaders address an IMAGE with 32-bit lane offsets behind a 64-bit base (round 5: the 512 -> 256 convolution over the 64-image
     // 256 x 256 hypercolumn is 2^31 elements); everything the epilogue touches is addressed from the tensor's base with 32 bits
@@ -1667,11 +1620,9 @@ static int ls_common_ok(const salt_conv_args* a) {
 }
 
 int conv_ls_variant(const salt_conv_args* a) {
-    static const int env = getenv("SALT_CONV_LS") ? atoi(getenv("SALT_CONV_LS")) : 1;
     if (!ls_common_ok(a)) return 0;
     const bool asked = (a->cfg & 0xff) == 10;
     if ((a->cfg & 0xff) != 0 && !asked) return 0;
-    if (!asked && !env) return 0;
     const int Cout = a->y.C;
     int wpx = ws_cus() / 8;
     const int64_t ntiles = (int64_t)a->x.B * (a->OH / 16) * (a->OW / 16);
@@ -1694,8 +1645,8 @@ int conv_ls_launch(const salt_conv_args* a, hipStream_t st) {
     k.B = a->x.B; k.H = a->x.H; k.W = a->x.W; k.x_cs = a->x.cs; k.y_cs = a->y.cs; k.OH = a->OH; k.OW = a->OW; k.Cout = a->y.C;
     k.tiles_x = a->OW / 16; k.tiles_y = a->OH / 16; k.ntiles = k.B * k.tiles_x * k.tiles_y;
     k.nchunk = a->x.C / 32;
-    int min_dy = 1 << 30, min_dx = 1 << 30;
-    for (int t = 0; t < 9; ++t) { min_dy = a->tap_dy[t] < min_dy ? a->tap_dy[t] : min_dy; min_dx = a->tap_dx[t] < min_dx ? a->tap_dx[t] : min_dx; }
+    const TapBox tb = tap_box(a->tap_dy, a->tap_dx, 9);
+    const int min_dy = tb.min_dy, min_dx = tb.min_dx;
     k.min_dy = min_dy; k.min_dx = min_dx; k.pad_mode = a->pad_mode;
     for (int t = 0; t < 9; ++t) k.tap_off[t] = (a->tap_dy[t] - min_dy) * 18 + (a->tap_dx[t] - min_dx);
     k.relu = a->relu; k.accumulate = a->accumulate;
@@ -1733,13 +1684,11 @@ int conv_ls_launch(const salt_conv_args* a, hipStream_t st) {
 }
 
 
-// ---- conv1x1_ls_kernel host side.  SALT_CONV_1X1_LS = 0: off unless asked for per launch (cfg & 0xff == 11).  Returns NI (1 | 2) or 0.
+// ---- conv1x1_ls_kernel host side.  cfg & 0xff == 11 asks for this kernel wherever it applies (tests).  Returns NI (1 | 2) or 0.
 int conv1x1_ls_variant(const salt_conv_args* a) {
-    static const int env = getenv("SALT_CONV_1X1_LS") ? atoi(getenv("SALT_CONV_1X1_LS")) : 1;
     if (!a || a->dtype != SALT_BF16 || a->ntaps != 1 || a->tap_dy[0] || a->tap_dx[0]) return 0;
     const bool asked = (a->cfg & 0xff) == 11;
     if ((a->cfg & 0xff) != 0 && !asked) return 0;
-    if (!asked && !env) return 0;
     if ((a->in_step != 1 && a->in_step != 2) || a->out_step != 1 || a->out_oy || a->out_ox || a->nphase > 1) return 0;
     if (a->strip || a->fold_top || a->fold_bottom || a->fold_left || a->fold_right) return 0;
     // eval / plain epilogues, or the train-mode statistics through the fp64 shards finalized by the consumer (as conv_ls_kernel's MODE 1)
@@ -1769,11 +1718,9 @@ int conv1x1_ls_variant(const salt_conv_args* a) {
 }
 
 // conv1x1_xs_kernel instead: plain epilogue, unit step, <= 256 input channels, many 64-channel blocks per pixel tile and enough tiles for
-// the chip.  SALT_CONV_1X1_XS=0: off; cfg bit 19 (with cfg & 0xff == 11): asked for (tests walk it on small tensors).
+// the chip.  cfg bit 19 (with cfg & 0xff == 11): asked for (tests walk it on small tensors).
 static bool conv1x1_xs_ok(const salt_conv_args* a) {
-    static const int env = getenv("SALT_CONV_1X1_XS") ? atoi(getenv("SALT_CONV_1X1_XS")) : 1;
     const bool asked = (a->cfg & 0xff) == 11 && ((a->cfg >> 19) & 1);
-    if (!env && !asked) return false;
     if (a->in_step != 1 || a->fin_acc) return false;
     const int Cin = a->x.C, Cout = a->y.C;
     if (Cin % 64 || Cin > 256 || Cout % 64) return false;
@@ -1826,24 +1773,18 @@ int conv1x1_ls_launch(const salt_conv_args* a, hipStream_t st) {
 }
 
 
-// ---- conv_stem16_kernel host side.  SALT_CONV_STEM16 = 0: off unless asked for per launch (cfg & 0xff == 13).
+// ---- conv_stem16_kernel host side.  cfg & 0xff == 13 asks for this kernel wherever it applies (tests).
 int conv_stem16_variant(const salt_conv_args* a) {
-    static const int env = getenv("SALT_CONV_STEM16") ? atoi(getenv("SALT_CONV_STEM16")) : 1;
     if (!a || a->dtype != SALT_BF16 || a->ntaps != 16) return 0;
     const bool asked = (a->cfg & 0xff) == 13;
     if ((a->cfg & 0xff) != 0 && !asked) return 0;
-    if (!asked && !env) return 0;
     if (a->in_step != 1 || a->out_step != 1 || a->out_oy || a->out_ox || a->nphase > 1 || a->pad_mode != 0) return 0;
     if (a->strip || a->fold_top || a->fold_bottom || a->fold_left || a->fold_right || a->x_plane || a->y_plane || a->res.p || a->accumulate) return 0;
     if (a->stats || a->fin_ticket || a->bnb_acc || a->bnb_partials || a->bnb_ticket || a->in_scale || a->in_fin_acc) return 0;
     if (a->fin_acc && (a->bias || a->scale || a->shift || a->relu)) { /* MODE 1 applies the affine part before the sums, as conv_ws_kernel */ }
     if (a->x.C != 16 || a->y.C != 64 || a->x.B != a->y.B || a->OH != a->y.H || a->OW != a->y.W || a->OH % 16 || a->OW % 16) return 0;
-    int min_dy = 1 << 30, max_dy = -(1 << 30), min_dx = 1 << 30, max_dx = -(1 << 30);
-    for (int t = 0; t < 16; ++t) {
-        min_dy = a->tap_dy[t] < min_dy ? a->tap_dy[t] : min_dy; max_dy = a->tap_dy[t] > max_dy ? a->tap_dy[t] : max_dy;
-        min_dx = a->tap_dx[t] < min_dx ? a->tap_dx[t] : min_dx; max_dx = a->tap_dx[t] > max_dx ? a->tap_dx[t] : max_dx;
-    }
-    if (max_dy - min_dy > 3 || max_dx - min_dx > 3) return 0;
+    const TapBox tb = tap_box(a->tap_dy, a->tap_dx, 16);
+    if (tb.max_dy - tb.min_dy > 3 || tb.max_dx - tb.min_dx > 3) return 0;
     if (a->x.cs % 8 || a->y.cs % 8 || ((reinterpret_cast<uintptr_t>(a->x.p) | reinterpret_cast<uintptr_t>(a->y.p) | reinterpret_cast<uintptr_t>(a->w)) & 15)) return 0;
     if ((int64_t)a->x.B * a->x.H * a->x.W * a->x.cs >= (int64_t)1 << 31 || (int64_t)a->y.B * a->y.H * a->y.W * a->y.cs >= (int64_t)1 << 31) return 0;
     if (!asked && (int64_t)a->y.B * (a->OH / 16) * (a->OW / 16) < ws_cus() / 2) return 0;
@@ -1857,8 +1798,8 @@ int conv_stem16_launch(const salt_conv_args* a, hipStream_t st) {
     k.bias = a->bias; k.scale = a->scale; k.shift = a->shift;
     k.B = a->x.B; k.H = a->x.H; k.W = a->x.W; k.x_cs = a->x.cs; k.y_cs = a->y.cs; k.OH = a->OH; k.OW = a->OW;
     k.tiles_x = a->OW / 16; k.tiles_y = a->OH / 16; k.ntiles = a->y.B * k.tiles_x * k.tiles_y;
-    int min_dy = 1 << 30, min_dx = 1 << 30;
-    for (int t = 0; t < 16; ++t) { min_dy = a->tap_dy[t] < min_dy ? a->tap_dy[t] : min_dy; min_dx = a->tap_dx[t] < min_dx ? a->tap_dx[t] : min_dx; }
+    const TapBox tb = tap_box(a->tap_dy, a->tap_dx, 16);
+    const int min_dy = tb.min_dy, min_dx = tb.min_dx;
     k.min_dy = min_dy; k.min_dx = min_dx;
     for (int t = 0; t < 16; ++t) k.tap_off[t] = (a->tap_dy[t] - min_dy) * 19 + (a->tap_dx[t] - min_dx);
     k.relu = a->relu; k.fin_acc = a->fin_acc;

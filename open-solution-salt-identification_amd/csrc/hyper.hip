@@ -652,12 +652,8 @@ extern "C" int salt_hyper_stencil(const salt_hyper_stencil_args* a, void* stream
         if (a->dtype == SALT_F32) kern = npf <= 4 ? (p.head_y ? hyper_stencil_fwd_kernel<float, 4, true> : hyper_stencil_fwd_kernel<float, 4, false>) : nullptr;
         else kern = npf <= 2 ? (p.head_y ? hyper_stencil_fwd_kernel<bf16_t, 2, true> : hyper_stencil_fwd_kernel<bf16_t, 2, false>) : nullptr;
         if (!kern) SALT_FAIL(SALT_E_UNSUPPORTED, "hyper_stencil: %d pieces per thread", npf);
-        if (lds > 64 * 1024) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (e != hipSuccess) SALT_FAIL((int)e, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-        }
-        hipLaunchKernelGGL(kern, dim3(p.per_xcd * 8), dim3(HS_NT), lds, st, p);
-        SALT_CHECK_LAUNCH();
+        const int rc = salt_launch(kern, dim3(p.per_xcd * 8), dim3(HS_NT), lds, st, p);
+        if (rc) return rc;
         if (p.head_y && p.cblocks > 1) {
             const int64_t hw = (int64_t)y.H * y.W, total = (int64_t)y.B * p.head_co * hw;
             hipLaunchKernelGGL(head_sum_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, p.head_ws, p.head_b, p.head_y, p.cblocks, p.head_co, hw, total);
@@ -718,11 +714,5 @@ extern "C" int salt_hyper_stencil(const salt_hyper_stencil_args* a, void* stream
     void (*kern)(HsbKP) = nullptr;
     if (a->dtype == SALT_F32) kern = nslot == 1 ? hyper_stencil_bwd_kernel<float, 1, 2, 3> : hyper_stencil_bwd_kernel<float, 2, 1, 1>;
     else kern = nslot == 1 ? hyper_stencil_bwd_kernel<bf16_t, 1, 2, 3> : hyper_stencil_bwd_kernel<bf16_t, 2, 1, 1>;
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) SALT_FAIL((int)e, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-    }
-    hipLaunchKernelGGL(kern, dim3(p.per_xcd * 8), dim3(HB_NT), lds, st, p);
-    SALT_CHECK_LAUNCH();
-    return SALT_OK;
+    return salt_launch(kern, dim3(p.per_xcd * 8), dim3(HB_NT), lds, st, p);
 }

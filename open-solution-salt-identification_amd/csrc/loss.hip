@@ -8,7 +8,6 @@
 // pass does the label scan, the Jaccard gradient g_k, the dot with elu(errors) and the scatter of
 // d loss / d logit back to NCHW order.  Ties keep flat-index order (stable sort), so results are
 // deterministic; the loss value itself is tie-order invariant.
-#include <cstdlib>
 #include "common.h"
 
 namespace {
@@ -27,148 +26,15 @@ __device__ __forceinline__ float key_to_float(unsigned k) {
     return __uint_as_float(u);
 }
 
-__global__ __launch_bounds__(LT) void lovasz_kernel(salt_lovasz_args a) {
-    __shared__ unsigned hist[256];
-    __shared__ unsigned base[256];
-    __shared__ unsigned wcount[LW][256];
-    __shared__ float red[LW];
-    __shared__ unsigned scan_w[LW];
-    __shared__ unsigned carry_s;
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int P = a.P;
-    const float* z = a.logits + (int64_t)b * P;
-    const float* y = a.target + (int64_t)b * P;
-    unsigned* k0 = a.ws_keys + (int64_t)b * P;
-    unsigned* v0 = a.ws_vals + (int64_t)b * P;
-    unsigned* k1 = a.ws_keys + ((int64_t)a.B + b) * P;
-    unsigned* v1 = a.ws_vals + ((int64_t)a.B + b) * P;
-
-    // ---- keys + total positives
-    float gsum = 0.f;
-    for (int i = tid; i < P; i += LT) {
-        const float lab = y[i] > 0.5f ? 1.f : 0.f;              // target.long() of a {0.,1.} mask
-        const float e = 1.f - z[i] * (2.f * lab - 1.f);
-        k0[i] = desc_key(e);
-        v0[i] = ((unsigned)i << 1) | (lab > 0.5f ? 1u : 0u);
-        gsum += lab;
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) gsum += __shfl_xor(gsum, o);
-    if (lane == 0) red[wave] = gsum;
-    __syncthreads();
-    float G = 0.f;
-    for (int w = 0; w < LW; ++w) G += red[w];
-    __syncthreads();
-
-    // ---- stable LSD radix sort, 8 bits per pass
-    const unsigned long long lt_mask = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
-    for (int pass = 0; pass < 4; ++pass) {
-        const unsigned* ki = (pass & 1) ? k1 : k0; const unsigned* vi = (pass & 1) ? v1 : v0;
-        unsigned* ko = (pass & 1) ? k0 : k1; unsigned* vo = (pass & 1) ? v0 : v1;
-        const int shift = pass * 8;
-        if (tid < 256) hist[tid] = 0;
-        __syncthreads();
-        for (int i = tid; i < P; i += LT) atomicAdd(&hist[(ki[i] >> shift) & 255u], 1u);
-        __syncthreads();
-        if (tid < 64) {                                           // exclusive scan of 256 counters by one wave
-            unsigned c[4], s = 0;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) { c[j] = hist[tid * 4 + j]; s += c[j]; }
-            unsigned incl = s;
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) { const unsigned t = __shfl_up(incl, o); if (lane >= o) incl += t; }
-            unsigned run = incl - s;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) { base[tid * 4 + j] = run; run += c[j]; }
-        }
-        __syncthreads();
-        for (int c0 = 0; c0 < P; c0 += LT) {
-            for (int i = tid; i < LW * 256; i += LT) (&wcount[0][0])[i] = 0;
-            __syncthreads();
-            const int i = c0 + tid;
-            const bool ok = i < P;
-            unsigned key = 0, val = 0, d = 256;
-            if (ok) { key = ki[i]; val = vi[i]; d = (key >> shift) & 255u; }
-            // lanes of this wave holding the same digit
-            unsigned long long m = __ballot(ok);
-#pragma unroll
-            for (int bit = 0; bit < 8; ++bit) {
-                const unsigned long long bm = __ballot((d >> bit) & 1u);
-                m &= ((d >> bit) & 1u) ? bm : ~bm;
-            }
-            const unsigned rank = (unsigned)__popcll(m & lt_mask);
-            if (ok && rank == 0) wcount[wave][d] = (unsigned)__popcll(m);
-            __syncthreads();
-            if (tid < 256) {                                      // digit tid: prefix over waves, advance base
-                unsigned run = base[tid];
-                for (int w = 0; w < LW; ++w) { const unsigned c = wcount[w][tid]; wcount[w][tid] = run; run += c; }
-                base[tid] = run;
-            }
-            __syncthreads();
-            if (ok) { const unsigned dst = wcount[wave][d] + rank; ko[dst] = key; vo[dst] = val; }
-            __syncthreads();
-        }
-    }
-    // after 4 passes the sorted sequence is back in (k0, v0)
-
-    // ---- fused scan + Jaccard gradient + dot + scatter
-    if (tid == 0) carry_s = 0;
-    __syncthreads();
-    float lsum = 0.f;
-    const float gscale = a.loss_scale / (float)a.B;
-    float* dz = a.dlogits ? a.dlogits + (int64_t)b * P : nullptr;
-    for (int c0 = 0; c0 < P; c0 += LT) {
-        const int i = c0 + tid;
-        const bool ok = i < P;
-        unsigned val = ok ? v0[i] : 0u;
-        const unsigned lab = val & 1u;
-        unsigned incl = ok ? lab : 0u;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) { const unsigned t = __shfl_up(incl, o); if (lane >= o) incl += t; }
-        if (lane == 63) scan_w[wave] = incl;
-        __syncthreads();
-        unsigned woff = carry_s;
-        for (int w = 0; w < wave; ++w) woff += scan_w[w];
-        const unsigned c_k = woff + incl;                         // inclusive count of positives up to rank k
-        __syncthreads();
-        if (tid == LT - 1) carry_s = c_k;
-        if (ok) {
-            const float e = key_to_float(k0[i]);
-            const float kf = (float)(i + 1), ck = (float)c_k, ckm = (float)(c_k - lab);
-            // exactly the reference's fp32 sequence (lovasz_losses.py:27-32): one correctly rounded division, one
-            // subtraction from 1, one first difference; no fma contraction (the difference cancels ~3 digits)
-            const float jk = __fsub_rn(1.f, __fdiv_rn(G - ck, G + (kf - ck)));
-            float jm = 0.f;
-            if (i > 0) jm = __fsub_rn(1.f, __fdiv_rn(G - ckm, G + ((kf - 1.f) - ckm)));
-            const float g = (i > 0) ? __fsub_rn(jk, jm) : jk;
-            const float el = e > 0.f ? e : expm1f(e);
-            lsum += el * g;
-            if (dz) {
-                const float d = e > 0.f ? 1.f : __expf(e);
-                const float s = lab ? 1.f : -1.f;
-                dz[val >> 1] = -s * d * g * gscale;
-            }
-        }
-        __syncthreads();
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) lsum += __shfl_xor(lsum, o);
-    if (lane == 0) red[wave] = lsum;
-    __syncthreads();
-    if (tid == 0) {
-        float t = 0.f;
-        for (int w = 0; w < LW; ++w) t += red[w];
-        if (P == 0) t = 0.f;
-        a.loss_per_image[b] = t;
-    }
-}
-
-// Prefetching variant (the one that is launched): same chunk order as lovasz_kernel (chunk c = elements c*1024 + tid, so the
-// result is identical), but
+// One workgroup per image.  Chunk c is the elements c*1024 + tid; every pass ranks and scatters the chunks in ascending order, which
+// is what makes the sort stable.  Two things keep the per-chunk critical path LDS-only:
 //   * the (key, payload) pairs of the next group of 4 chunks are loaded while the current group is ranked and scattered (the
-//     ping-pong workspace is L2-resident; the per-chunk critical path becomes LDS-only), and
-//   * the digit histogram of pass p+1 is accumulated while pass p scatters (a histogram does not depend on element order),
-//     which removes the four separate counting sweeps.
+//     ping-pong workspace is L2-resident), and
+//   * the digit histogram of pass p+1 is accumulated while pass p scatters (a histogram does not depend on element order), so
+//     there are no separate counting sweeps.
+// Final pass over the sorted sequence, with k = rank + 1, c_k = positives up to rank k (inclusive), G = all positives, in fp32:
+//   J_k = 1 - (G - c_k) / (G + (k - c_k))    (__fsub_rn / __fdiv_rn: one correctly rounded division, one subtraction from 1)
+//   g_k = J_k - J_(k-1)  (g_1 = J_1),  loss += elu(e_k) g_k,  d loss / d logit = -sign d g_k loss_scale / B.
 constexpr int LG = 4;                    // chunks per prefetch group
 __global__ __launch_bounds__(LT) void lovasz_pf_kernel(salt_lovasz_args a) {
     __shared__ unsigned hist[2][256];
@@ -351,7 +217,7 @@ __global__ __launch_bounds__(LT) void lovasz_pf_kernel(salt_lovasz_args a) {
 //   scan    : label scan with the carry of the earlier segments, Jaccard gradient, dot, scatter; per-segment loss partials that
 //             lovasz_mean_split_kernel adds in fixed order.
 // Integer atomics only: results do not depend on scheduling.  Positions, ties and the fp32 operation sequence of g_k are those of
-// lovasz_kernel, so gradients are bit-identical to it; the loss differs in the last bits (different summation tree).
+// lovasz_pf_kernel, so gradients are bit-identical to it; the loss differs in the last bits (different summation tree).
 constexpr int ST = 256, SWV = ST / 64, SL = 2048, SCH = SL / ST, SMAXSEG = 64;
 struct LovaszSplit { int S; unsigned* hist; unsigned* pos; float* part; };      // hist [3][B][S][256], pos [B][S], part [B][S]
 
@@ -496,7 +362,8 @@ __global__ __launch_bounds__(ST) void lovasz_scan_kernel(salt_lovasz_args a, Lov
         if (ok) {
             const float e = key_to_float(ck[u]);
             const float kf = (float)(i + 1), ckf = (float)c_k, ckm = (float)(c_k - lab);
-            // the reference's fp32 sequence (lovasz_losses.py:27-32), as in lovasz_kernel
+            // the reference's fp32 sequence (lovasz_losses.py:27-32): one correctly rounded division, one subtraction from 1, one
+            // first difference; no fma contraction (the difference cancels ~3 digits)
             const float jk = __fsub_rn(1.f, __fdiv_rn(G - ckf, G + (kf - ckf)));
             float jm = 0.f;
             if (i > 0) jm = __fsub_rn(1.f, __fdiv_rn(G - ckm, G + ((kf - 1.f) - ckm)));
@@ -726,9 +593,8 @@ extern "C" int64_t salt_lovasz_split_words(int P) {
 extern "C" int salt_lovasz_hinge(const salt_lovasz_args* a, void* stream) {
     if (!a || !a->logits || !a->target || a->B < 1 || a->P < 0 || !a->ws_keys || !a->ws_vals || !a->loss_per_image || !a->loss)
         SALT_FAIL(SALT_E_BADARG, "lovasz: bad args");
-    static const bool plain = getenv("SALT_LOVASZ_PLAIN") != nullptr;       // A/B switch: the non-prefetching kernel
     const int S = (a->P + SL - 1) / SL;
-    if (a->ws_split && !plain && a->P >= 2 * SL && S <= SMAXSEG) {
+    if (a->ws_split && a->P >= 2 * SL && S <= SMAXSEG) {
         hipStream_t st = (hipStream_t)stream;
         LovaszSplit sp{S, a->ws_split, a->ws_split + (int64_t)3 * a->B * S * 256, reinterpret_cast<float*>(a->ws_split + (int64_t)3 * a->B * S * 256 + (int64_t)a->B * S)};
         const dim3 grid(a->B * S);
@@ -741,8 +607,7 @@ extern "C" int salt_lovasz_hinge(const salt_lovasz_args* a, void* stream) {
         SALT_CHECK_LAUNCH();
         return SALT_OK;
     }
-    if (plain) hipLaunchKernelGGL(lovasz_kernel, dim3(a->B), dim3(LT), 0, (hipStream_t)stream, *a);
-    else hipLaunchKernelGGL(lovasz_pf_kernel, dim3(a->B), dim3(LT), 0, (hipStream_t)stream, *a);
+    hipLaunchKernelGGL(lovasz_pf_kernel, dim3(a->B), dim3(LT), 0, (hipStream_t)stream, *a);
     SALT_CHECK_LAUNCH();
     hipLaunchKernelGGL(mean_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, a->loss_per_image, a->B, a->loss_scale, a->loss);
     SALT_CHECK_LAUNCH();

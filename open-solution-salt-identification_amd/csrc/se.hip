@@ -555,19 +555,9 @@ static int launch_se_fc(const salt_scse_bwd_args* a, int nparts, hipStream_t st,
         Bt = (int)((160 * 1024 - fc_w) / fc_img);
     }
     const size_t fc_lds = fc_img * Bt + (stage_w ? fc_w : 0);
-    if (fc_lds > 64 * 1024) {
-        static bool attr_set = false;
-        if (!attr_set) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(se_fc_bwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (e != hipSuccess) SALT_FAIL((int)e, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-            attr_set = true;
-        }
-    }
-    hipLaunchKernelGGL(se_fc_bwd_kernel, dim3(1), dim3(1024), fc_lds, st, a->partials, nparts, B, C, a->R, a->w1, a->w2, a->gap, a->hidden,
+    return salt_launch(se_fc_bwd_kernel, dim3(1), dim3(1024), fc_lds, st, a->partials, nparts, B, C, a->R, a->w1, a->w2, a->gap, a->hidden,
                        a->gate_c, a->g_w1, a->g_b1, a->g_w2, a->g_b2, a->g_ws, a->g_bs, a->dgap, 1.0f / (float)(a->x.H * a->x.W), a->acc, stage_w, Bt,
                        bnb ? 6 * C + 1 : 2 * C + 1, bnb_out, write_dgap);
-    SALT_CHECK_LAUNCH();
-    return SALT_OK;
 }
 
 extern "C" int salt_scse_fc_grads(const salt_scse_bwd_args* a, void* stream) {

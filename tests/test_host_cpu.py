@@ -447,3 +447,11 @@ def test_switch_table_names_exactly_the_switches_the_code_reads():
     for name, (default, parse, meaning) in switches.SWITCHES.items():
         assert callable(parse) and meaning
 
+
+def test_dynamic_lds_limit_is_raised_in_one_place():
+    """Every launch that needs more than 64 KB of dynamic LDS goes through common.h's salt_launch: no other file of csrc/ raises a
+    kernel's limit itself."""
+    import glob
+    users = sorted(os.path.basename(fn) for fn in glob.glob(os.path.join(PKG, 'csrc', '*.*')) if os.path.isfile(fn) and
+                   fn.endswith(('.hip', '.h', '.py')) and 'hipFuncSetAttribute' in open(fn).read())
+    assert users == ['common.h'], users

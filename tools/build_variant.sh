@@ -2,6 +2,7 @@
 # Build an A/B variant of the library with extra compiler flags: [SRC=<file stem>] tools/build_variant.sh <name> <flags...>
 #   -> open-solution-salt-identification_amd/csrc/_variants/libsaltnet_hip.<name>.so   (run with SALT_LIB=<that path>)
 # SRC names the one source compiled with the flags (default conv_mfma); the other objects come from csrc/_obj (build.py first).
+# The source list is csrc/build.py's SOURCES.
 set -e
 cd "$(dirname "$0")/.."
 name=$1; shift
@@ -9,7 +10,7 @@ SRC=${SRC:-conv_mfma}
 C=open-solution-salt-identification_amd/csrc
 mkdir -p $C/_variants/obj_$name
 objs=""
-for f in runtime conv_mfma conv_ws conv_thin conv_wgrad_ls conv_small head_fused elementwise hyper se loss input; do
+for f in $(python -c "import sys; sys.path.insert(0, '$C'); import build; print(' '.join(s[:-4] for s in build.SOURCES))"); do
   if [ $f = $SRC ]; then
     /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Iinclude -I$C -Wno-unused-value "$@" -c $C/$f.hip -o $C/_variants/obj_$name/$f.o
     objs="$objs $C/_variants/obj_$name/$f.o"

@@ -1,7 +1,7 @@
 #!/usr/bin/env python
-"""Device-side micro-benchmark of dense conv launches: each (shape, cfg[, dbg]) is emitted REP times into one program, captured into
+"""Device-side micro-benchmark of dense conv launches: each (shape, cfg) is emitted REP times into one program, captured into
 a hipGraph (no host launch cost between the kernels) and timed with an event pair around the replay.
-usage: python tools/conv_bench.py "B,Cin,H,W,Cout[,k]:cfg[:dbg]" ...      (cfg 0 = heuristic; set SALT_CONV_V2=0 for the old kernel)"""
+usage: python tools/conv_bench.py "B,Cin,H,W,Cout[,k][:cfg]" ...      (cfg 0 = heuristic; set SALT_CONV_V2=0 for the old kernel)"""
 import os, sys
 R = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for p in (R, R + '/tests'):
@@ -19,10 +19,6 @@ for spec in sys.argv[1:]:
     B, Cin, H, W, Cout = dims[:5]
     k = dims[5] if len(dims) > 5 else 3
     cfg = int(parts[1]) if len(parts) > 1 else 0
-    dbg = parts[2] if len(parts) > 2 else None
-    v2 = parts[3] if len(parts) > 3 else None
-    if dbg is not None:
-        os.environ['SALT_CONV_DBG'] = dbg
     conv = nn.Conv2d(Cin, Cout, k, 1, k // 2, bias=False)
     mod = nn.Sequential(conv).to('cuda:0')
     eng = Engine(mod, torch.device('cuda:0'), 'bf16')
@@ -49,6 +45,5 @@ for spec in sys.argv[1:]:
             torch.cuda.synchronize()
             best = min(best, e0.elapsed_time(e1) * 1e3 / REP)
     fl = 2.0 * B * H * W * Cout * Cin * k * k
-    print('conv B%d %dx%dx%d -> %d k%d cfg%d dbg%s: %7.2f us  %7.1f TF/s' % (B, H, W, Cin, Cout, k, cfg, dbg, best, fl / best / 1e6))
-    os.environ.pop('SALT_CONV_DBG', None)
+    print('conv B%d %dx%dx%d -> %d k%d cfg%d: %7.2f us  %7.1f TF/s' % (B, H, W, Cin, Cout, k, cfg, best, fl / best / 1e6))
     g.fwd.release_graph()
