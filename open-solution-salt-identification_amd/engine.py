@@ -11,7 +11,11 @@ buffers that their producers write in place, so ``torch.cat`` never copies anyth
 
 PyTorch is used for device memory (tensors), streams and nothing else on this path.
 """
+import contextlib
 import ctypes
+from collections import namedtuple
+from dataclasses import dataclass, field
+from typing import Any
 
 import numpy as np
 import torch
@@ -22,6 +26,53 @@ from ._abi import OP_FUNCS, STRUCTS, SaltError, check, fill, lib
 DT_CODE = {'f32': 0, 'bf16': 1}
 TORCH_DT = {'f32': torch.float32, 'bf16': torch.bfloat16}
 VEC = {'f32': 4, 'bf16': 8}
+
+# ---------------------------------------------------------------------- the builder's peephole protocol
+# salt_bn_bwd_args.partials_ready, in saltnet.h's words:
+PARTIALS_OWN = 0         # bn_bwd's own reduction pass; "partials_ready == 0 and fin_acc != NULL: the reduction pass accumulates into [8][2][C] fp64 shards"
+PARTIALS_FILLED = 1      # "`partials` ([nparts][2][C], any nparts >= 1) was filled by the producer of da (salt_conv_args.bnb_*)"
+PARTIALS_FINALIZED = 2   # "the producer also finalized (salt_conv_args.bnb_fin): coef / dgamma / dbeta are ready, only the apply pass runs"
+PARTIALS_SHARDS = 3      # "the producer added the sums to fin_acc (salt_conv_args.bnb_acc without ticket): the apply pass finalizes them"
+
+# Who supplies a layer's BatchNorm-backward sums (Graph._bnb_sums_source); the middle two are also the kinds of carrier a gradient writer offers
+SUMS_OWN = 'own'         # the reduction pass of the layer's own salt_bn_bwd
+SUMS_CONV = 'conv'       # the data-gradient launch that writes dL/da last (salt_conv_args.bnb_*)
+SUMS_SEC = 'sec'         # the main branch's salt_bn_bwd, whose dres IS this layer's dL/da (salt_bn_bwd_args.sec_*)
+SUMS_SCSE = 'scse'       # the scSE backward behind the layer (salt_scse_bwd_args.bnb_acc)
+
+
+@dataclass
+class GradWriter:
+    """One writer of channels [c0, c0 + C) of a Buffer's gradient (Act.grad_state, backward-program order).  ``carrier``: its argument struct
+    if it can also take the BatchNorm-backward sums of the slice's producer - a salt_conv_args (``kind`` SUMS_CONV) or a salt_bn_bwd_args
+    (SUMS_SEC); set by Act.offer_carrier, claimed by Graph._bnb_sums_source."""
+    c0: int
+    C: int
+    kind: Any = None
+    carrier: Any = None
+
+
+# Buffer.grad_bias: the scSE backward left the channel-SE term ``dgap`` [B][C] out of dL/dx; the bn_bwd of x's producer adds it (da_bias).  ``sums_from``:
+# the salt_scse_bwd_args that also took that layer's BatchNorm-backward sums; ``fc_grads``: the deferred salt_scse_fc_grads struct, or None
+GradBias = namedtuple('GradBias', 'c0 C dgap sums_from fc_grads', defaults=(None, None))
+# Buffer.act_op: the salt_affine_act ``struct`` that stores channels [c0, c0 + C), and Buffer.reads right after it (Graph._take_act_op)
+ActOp = namedtuple('ActOp', 'struct reads0 c0 C')
+# Graph.depth_gate -> channel_gate: gate values ``s`` [B][C], dL/ds ``ds`` (None: through the fp64 arena), the backward channel_gate structs ``users`` that
+# add to it, and the gate channels some channel_gate has ``covered``
+DepthGate = namedtuple('DepthGate', 's B C ds users covered')
+
+
+@dataclass
+class Lazy:
+    """Buffer.lazy (SALT_FWD_BN_FOLD candidate): raw convolution output ``y``, the layer's salt_bn_finalize_args ``F``, its affine_act ``sa``, byte
+    offset ``off`` of its statistics shards, Buffer.reads right after ``sa``, the convolution structs that read y through their loader."""
+    y: Any
+    F: Any
+    sa: Any
+    off: int
+    reads0: int
+    users: list = field(default_factory=list)
+    dropped: bool = False          # Graph._resolve_lazies removed ``sa``
 
 
 def fwd_bn_fold():
@@ -57,6 +108,7 @@ class Program:
         self.marks = {}
         self._pre_run = None           # callable(stream, begin) run before the entries are issued (Graph.finalize: shard hygiene)
         self._post_run = None          # callable(begin, end) after they were issued
+        self._graph = None             # captured hipGraph executable: capture() writes, replay() / release_graph() read
 
     def add(self, opname, stream=None, **fields):
         fn, S = OP_FUNCS['salt_' + opname]
@@ -157,12 +209,12 @@ class Program:
         return self
 
     def replay(self, stream=None):
-        if getattr(self, '_graph', None) is None:
+        if self._graph is None:
             raise SaltError('program %s has no captured graph' % self.name)
         check(lib.salt_graph_launch(self._graph, _stream_ptr(stream)), 'graph_launch')
 
     def release_graph(self):
-        if getattr(self, '_graph', None) is not None:
+        if self._graph is not None:
             lib.salt_graph_destroy(self._graph)
             self._graph = None
 
@@ -212,8 +264,13 @@ class Buffer:
         self.t = graph.alloc(self._shape(), graph.tdtype)
         self.grad_t = None
         self.grad_init = np.zeros(self.Ct, dtype=bool)
-        self.grad_writers = []         # one entry per gradient writer in backward-program order: [c0, C, conv-args struct | None]
+        self.grad_writers = []         # GradWriter per gradient writer in backward-program order (Act.grad_state; read by Graph._bnb_sums_source)
         self.reads = 0                 # views handed out (SALT_FWD_BN_FOLD: an activation nobody else reads need not be materialised)
+        self.act_op = None             # ActOp: Graph._bn_train_fwd writes, Graph._take_act_op (scse / head) reads and clears
+        self.bn_train_out = None       # (c0, C) of the train-mode BatchNorm output stored here: _bn_train_fwd writes, scse / _bn_train_bwd read
+        self.grad_bias = None          # GradBias: the backward of Graph.scse writes, Graph._bnb_sums_source / _bn_train_bwd read and clear
+        self.head_fused = None         # the logit-head nn.Conv2d that took the affine_act over: Graph.head writes, _bn_train_bwd reads
+        self.lazy = None               # Lazy: Graph._bn_train_fwd writes, Graph.conv / _resolve_lazies read
 
     def _shape(self):
         return (self.C // self.planes, self.B, self.H, self.W, self.planes) if self.planes else (self.B, self.H, self.W, self.Ct)
@@ -233,6 +290,7 @@ class Act:
     def __init__(self, buf, c0=0, C=None):
         self.buf, self.c0 = buf, c0
         self.C = buf.C if C is None else C
+        self.on_side = False           # produced on the side stream: conv / hyper_level / channel_gate write, consumers read (slice() does not inherit it)
 
     B = property(lambda s: s.buf.B)
     H = property(lambda s: s.buf.H)
@@ -270,13 +328,20 @@ class Act:
     def grad_state(self):
         """-> accumulate flag for the next writer of this slice's gradient; marks it initialised."""
         st = self.buf.grad_init[self.c0:self.c0 + self.C]
-        self.buf.grad_writers.append([self.c0, self.C, None])
+        self.buf.grad_writers.append(GradWriter(self.c0, self.C))
         if st.all():
             return 1
         if st.any():
             raise SaltError('gradient of %s partially initialised' % self.buf.name)
         self.buf.grad_init[self.c0:self.c0 + self.C] = True
         return 0
+
+    def offer_carrier(self, kind, struct):
+        """The LAST writer of this slice's gradient (it completes it) can also take the BatchNorm-backward sums of the slice's producer:
+        ``struct`` is its salt_conv_args (SUMS_CONV) or salt_bn_bwd_args (SUMS_SEC).  (a planar dL/dx has one dense consumer per plane:
+        nothing to ride along)"""
+        if not self.plane_stride():
+            self.buf.grad_writers[-1].kind, self.buf.grad_writers[-1].carrier = kind, struct
 
     def grad_ready(self):
         return bool(self.buf.grad_init[self.c0:self.c0 + self.C].all())
@@ -329,6 +394,15 @@ class Graph:
         self._touched = []
         self.grad_ready = []
         self._scratch_sfx = ''
+        self._virtual_acts = []        # (buffer, reads) of activations never stored: _take_act_op writes, finalize checks
+        self._bias_bufs = []           # buffers that got a GradBias: the backward of scse writes, build_backward checks they were consumed
+        self._lazies = []              # buffers with a Lazy record: _bn_train_fwd writes, _resolve_lazies reads and clears
+        self._n_bnb = 0                # data-gradient launches that carry BatchNorm-backward sums (names their 'bnb%d' partials): _bnb_sums_source
+        self._uses_bwd_packs = False   # _bwd_pack_tag writes, build_backward reads (the first main-stream backward operator joins the packs)
+        self.input_grads = []          # fp32 NCHW dL/d(input) buffers: from_nchw writes, the tests' harness reads
+        self.dlogits = None            # fp32 NCHW dL/d(logits): head / _head_bn / pool_head / to_nchw write, CompiledNet and the backward emitters read
+        self.n_folded = 0              # affine_acts dropped by _resolve_lazies (tests, tools/fwd_fold_probe.py)
+        self._shard_state = None       # {'dirty', 'rezeroed'} of the backward statistics shards: finalize writes, its run hooks and the tests read
         # fp64 statistics shards of the train-mode BatchNorm layers (SALT_BN_FIN=2): slices of one arena per program, cleared by ONE
         # salt_zero at the head of the program
         self._fin_bytes = {'fwd': 0, 'bwd': 0}
@@ -348,19 +422,16 @@ class Graph:
         return Act(Buffer(self, B, H, W, C, name, planes))
 
     # ------------------------------------------------------------------ forward branches on the side stream
+    @contextlib.contextmanager
     def side(self):
         """``with g.side():`` - forward operators emitted inside run on the side stream, concurrently with the main-stream operators
         emitted after the block.  The caller must call ``g.join()`` before emitting the first consumer of their results.  Shared
         scratch workspaces get their own copies ('@side').  Backward operators of the same layers are unaffected."""
-        g = self
-
-        class _Side:
-            def __enter__(self_):
-                g.fwd.default_stream, g._scratch_sfx = 1, '@side'
-
-            def __exit__(self_, *a):
-                g.fwd.default_stream, g._scratch_sfx = 0, ''
-        return _Side()
+        self.fwd.default_stream, self._scratch_sfx = 1, '@side'
+        try:
+            yield
+        finally:
+            self.fwd.default_stream, self._scratch_sfx = 0, ''
 
     def join(self):
         """The next main-stream forward operator waits for everything the side stream has been given so far."""
@@ -370,7 +441,7 @@ class Graph:
         return self.alloc((max(int(n), 1),), torch.float32)
 
     def finalize(self):
-        for buf, reads in getattr(self, '_virtual_acts', []):
+        for buf, reads in self._virtual_acts:
             if buf.reads != reads:
                 raise SaltError('activation %s is applied on the fly by its only consumer (Graph._take_act_op) but another operator asked for its storage' % buf.name)
         sizes = {}
@@ -452,13 +523,13 @@ class Graph:
                 off, n = self.engine.grad_range(p)
                 self.grad_ready.append((off, n, len(self.bwd.ops)))
         self.tape = []
-        for b in getattr(self, '_bias_bufs', []):        # every folded channel-SE term must have met its bn_bwd, or x.grad is incomplete
-            if getattr(b, 'grad_bias', None) is not None:
+        for b in self._bias_bufs:        # every folded channel-SE term must have met its bn_bwd, or x.grad is incomplete
+            if b.grad_bias is not None:
                 raise SaltError('gradient bias of %s was never consumed (no BatchNorm backward read that slice)' % b.name)
         # The data-gradient weight packs of the step were enqueued on the side stream during forward (Engine.refresh): the FIRST
         # main-stream operator of the backward program joins the side stream - before any weight-gradient kernel is enqueued there,
         # so the join waits for the packs only.
-        if getattr(self, '_uses_bwd_packs', False):
+        if self._uses_bwd_packs:
             for i, st in enumerate(self.bwd.streams):
                 if st == 0:
                     self.bwd.streams[i] = 3
@@ -480,15 +551,13 @@ class Graph:
         d = 1 << 20                                     # stand-in pointer (the probes only plan, nothing is launched)
         td = [(kh - (KH - 1), kw) for kh in range(KH) for kw in range(KW)]
         xv, yv, plane = shaped_view(d, B, H, W, C, pc), shaped_view(d, B, H, W, Cout), B * H * W * pc
-        S = fill(STRUCTS['salt_conv_args'](), dtype=self.dt, x=xv, w=d, ntaps=9, tap_dy=[t[0] for t in td], tap_dx=[t[1] for t in td], in_step=1,
-                 pad_mode=1, y=yv, OH=H, OW=W, out_step=1, x_plane=plane)
+        S = self._conv_probe(xv, d, td, 1, 1, yv, H, W)               # (x_plane: _plane_args, xv has cs < C)
         if lib.salt_conv_kernel_id(ctypes.byref(S)) != 10:
             return False
         if not self.train:
             return True
         tg = [(-t[0] - (KH - 1), -t[1]) for t in td]
-        S = fill(STRUCTS['salt_conv_args'](), dtype=self.dt, x=yv, w=d, ntaps=9, tap_dy=[t[0] for t in tg], tap_dx=[t[1] for t in tg], in_step=1,
-                 pad_mode=0, y=xv, OH=H + KH - 1, OW=W + KW - 1, out_step=1, fold_top=KH - 1, fold_right=KW - 1, y_plane=plane)
+        S = self._conv_probe(yv, d, tg, 1, 0, xv, H + KH - 1, W + KW - 1, fold_top=KH - 1, fold_right=KW - 1)      # (y_plane likewise)
         if lib.salt_conv_kernel_id(ctypes.byref(S)) != 9:
             return False
         Wg = fill(STRUCTS['salt_conv_wgrad_args'](), dtype=self.dt, p=yv, q=xv, ntaps=9, tap_dy=[t[0] for t in td], tap_dx=[t[1] for t in td],
@@ -499,13 +568,13 @@ class Graph:
         """SALT_FWD_BN_FOLD: drop the affine_act of every conv -> BN -> ReLU output whose only forward reader is ONE convolution that
         applies the transform in its loader; every other candidate goes back to reading the materialised activation."""
         drop = []
-        for buf in getattr(self, '_lazies', []):
+        for buf in self._lazies:
             lz = buf.lazy
-            if len(lz['users']) == 1 and buf.reads == lz['reads0']:
-                lz['dropped'] = True
-                drop.append(next(i for i, (_, _, st) in enumerate(self.fwd.ops) if st is lz['sa']))
+            if len(lz.users) == 1 and buf.reads == lz.reads0:
+                lz.dropped = True
+                drop.append(next(i for i, (_, _, st) in enumerate(self.fwd.ops) if st is lz.sa))
             else:
-                for st in lz['users']:
+                for st in lz.users:
                     fill(st, x=Act(buf).view(), in_fin=None, in_relu=0)
                     self._fin_patches = [q for q in self._fin_patches if q[0] is not st or q[1] != 'in_fin_acc']
         for i in sorted(drop, reverse=True):
@@ -520,16 +589,21 @@ class Graph:
     def _es(self):
         return 4 if self.dtype == 'f32' else 2
 
-    def _conv_launch(self, prog, x_view, wp, taps_dydx, in_step, pad_mode, y_view, OH, OW, out_step=1, out_oy=0, out_ox=0,
-                     bias=None, scale=None, shift=None, relu=0, accumulate=0, stats=None, stats_cnt=None, part0=0, cfg=0, **fold):
+    def _conv_args(self, x_view, wp, taps_dydx, in_step, pad_mode, y_view, OH, OW, **fields):
+        """The fields of a salt_conv_args over the tap offsets ``taps_dydx`` = [(dy, dx)]: what _conv_launch emits and what every
+        planning probe (_conv_probe) asks the library about."""
         kw = dict(dtype=self.dt, x=x_view, w=wp, ntaps=len(taps_dydx), tap_dy=[t[0] for t in taps_dydx], tap_dx=[t[1] for t in taps_dydx],
-                  in_step=in_step, pad_mode=pad_mode, y=y_view, OH=OH, OW=OW, out_step=out_step, out_oy=out_oy, out_ox=out_ox,
-                  bias=bias, scale=scale, shift=shift, relu=relu, accumulate=accumulate, stats=stats, stats_cnt=stats_cnt,
-                  stats_part0=part0, cfg=cfg)
-        stream = fold.pop('stream', None)
-        kw.update(fold)
+                  in_step=in_step, pad_mode=pad_mode, y=y_view, OH=OH, OW=OW, out_step=1)
+        kw.update(fields)
         kw.update(self._plane_args(x_view, y_view))
-        return prog.add('conv', stream=stream, **kw)
+        return kw
+
+    def _conv_probe(self, *a, **fields):
+        """A filled salt_conv_args that is only planned with (salt_conv_kernel_id / salt_conv_stats_parts), never launched."""
+        return fill(STRUCTS['salt_conv_args'](), **self._conv_args(*a, **fields))
+
+    def _conv_launch(self, prog, x_view, wp, taps_dydx, in_step, pad_mode, y_view, OH, OW, part0=0, stream=None, **fields):
+        return prog.add('conv', stream=stream, **self._conv_args(x_view, wp, taps_dydx, in_step, pad_mode, y_view, OH, OW, stats_part0=part0, **fields))
 
     @staticmethod
     def _plane_args(x_view, y_view):
@@ -542,10 +616,8 @@ class Graph:
             kw['x_plane'] = x_view.B * x_view.H * x_view.W * x_view.cs
         return kw
 
-    def _conv_parts(self, x_view, taps_dydx, in_step, y_view, OH, OW, cfg=0):
-        S = STRUCTS['salt_conv_args']()
-        fill(S, dtype=self.dt, x=x_view, w=1, ntaps=len(taps_dydx), tap_dy=[t[0] for t in taps_dydx], tap_dx=[t[1] for t in taps_dydx],
-             in_step=in_step, pad_mode=0, y=y_view, OH=OH, OW=OW, out_step=1, cfg=cfg, **self._plane_args(x_view, y_view))
+    def _conv_parts(self, x_view, taps_dydx, in_step, y_view, OH, OW, **fields):
+        S = self._conv_probe(x_view, 1, taps_dydx, in_step, 0, y_view, OH, OW, **fields)
         n = lib.salt_conv_stats_parts(ctypes.byref(S))
         if n < 0:
             raise SaltError('conv plan failed: ' + lib.salt_last_error().decode())
@@ -568,15 +640,18 @@ class Graph:
         ticket = self.alloc((16,), torch.int32)
         return acc.data_ptr(), ticket.data_ptr()
 
+    def _bn_fin_fields(self, bn):
+        """-> (the layer's work vectors, the fields of its salt_bn_finalize_args)"""
+        w = self.engine.bn_work(bn)
+        nbt = bn.num_batches_tracked.data_ptr() if bn.num_batches_tracked is not None else None
+        return w, dict(C=bn.num_features, gamma=bn.weight.data_ptr(), beta=bn.bias.data_ptr(), running_mean=bn.running_mean.data_ptr(),
+                       running_var=bn.running_var.data_ptr(), num_batches_tracked=nbt, momentum=bn.momentum, eps=bn.eps, mean=w['mean'].data_ptr(),
+                       invstd=w['invstd'].data_ptr(), scale=w['scale'].data_ptr(), shift=w['shift'].data_ptr())
+
     def _bn_train_fwd(self, y, bn, relu, res, out, nparts, stats, cnt, producer=None):
         """``producer``: the argument struct of the ONE convolution launch that writes y - it then finalizes the statistics itself
         (salt_conv_args.fin) and no bn_finalize operator is emitted."""
-        w = self.engine.bn_work(bn)
-        nbt = bn.num_batches_tracked.data_ptr() if bn.num_batches_tracked is not None else None
-        fin = dict(C=bn.num_features, gamma=bn.weight.data_ptr(),
-                   beta=bn.bias.data_ptr(), running_mean=bn.running_mean.data_ptr(), running_var=bn.running_var.data_ptr(),
-                   num_batches_tracked=nbt, momentum=bn.momentum, eps=bn.eps, mean=w['mean'].data_ptr(), invstd=w['invstd'].data_ptr(),
-                   scale=w['scale'].data_ptr(), shift=w['shift'].data_ptr())
+        w, fin = self._bn_fin_fields(bn)
         F = None
         if producer is not None:
             F = fill(STRUCTS['salt_bn_finalize_args'](), **fin)
@@ -587,12 +662,12 @@ class Graph:
                 F = None
         else:
             self.fwd.add('bn_finalize', stats=stats, stats_cnt=cnt, nparts=nparts, **fin)
-        if res is not None and getattr(res, 'on_side', False):
+        if res is not None and res.on_side:
             self.join()                          # the residual branch ran on the side stream
         out.buf.bn_train_out = (out.c0, out.C)      # dL/d(out) is consumed by this layer's bn_bwd only: it may take a per-image bias (scse)
         sa = self.fwd.add('affine_act', dtype=self.dt, y=y.view(), scale=w['scale'].data_ptr(), shift=w['shift'].data_ptr(),
                           res=res.view() if res is not None else null_view(), relu=int(relu), a=out.view())
-        out.buf.act_op = (sa, out.buf.reads, out.c0, out.C)     # Graph.scse may take this operator over (the activation is then never stored)
+        out.buf.act_op = ActOp(sa, out.buf.reads, out.c0, out.C)     # Graph.scse may take this operator over (the activation is then never stored)
         if F is not None:                        # the producer only adds to the shards; this operator finalizes them
             self.fwd.set_fields(sa, fin=ctypes.addressof(F))
             off = self._fin_slot('fwd', 8 * (2 * bn.num_features + 1), (producer, 'fin_acc'), (sa, 'fin_acc'))
@@ -600,113 +675,137 @@ class Graph:
                     and self.fwd.streams[-1] == 0):
                 # measurement switch: if the ONLY forward reader of `out` turns out to be one 3x3 convolution, that launch
                 # applies this BatchNorm + ReLU in its loader (salt_conv_args.in_*) and this affine_act is dropped (build_backward)
-                out.buf.lazy = dict(y=y, F=F, sa=sa, off=off, reads0=out.buf.reads, users=[], dropped=False)
-                self._lazies = getattr(self, '_lazies', []) + [out.buf]
+                out.buf.lazy = Lazy(y=y, F=F, sa=sa, off=off, reads0=out.buf.reads)
+                self._lazies.append(out.buf)
         return w
+
+    def _bn_behind(self, launch, shards, nparts, y, bn, relu, res, out, sfx):
+        """The train-mode BatchNorm behind the launch(es) that write ``y``.  ``launch(**stats)`` emits them and returns the last one's
+        argument struct.  ``shards`` (it is ONE launch, of a kernel that can) and SALT_BN_FIN != 0: the launch adds y's statistics to the
+        fp64 shards and _bn_train_fwd wires them to its struct; otherwise per-tile partials in the 'stats' / 'stats_cnt' workspaces + a
+        bn_finalize operator.  ``sfx``: suffix of the workspace names (Graph.side: a side-stream launch must not share the main
+        stream's).  -> (bn work vectors, producer | None)"""
+        if shards and self._fin_on():
+            prod = launch()
+            return self._bn_train_fwd(y, bn, relu, res, out, nparts, None, None, producer=prod), prod
+        stats, cnt = Scratch('stats' + sfx, 4 * lib.salt_bn_stats_floats(nparts, y.C)), Scratch('stats_cnt' + sfx, nparts * 4)
+        launch(stats=stats, stats_cnt=cnt)
+        return self._bn_train_fwd(y, bn, relu, res, out, nparts, stats, cnt), None
+
+    def _conv_bn_train(self, x, y, launches, bn, relu, res, out, sfx, plan=None):
+        """Convolution x -> y whose output feeds a train-mode BatchNorm: plan the statistics partials, launch, _bn_behind.
+        ``launches`` = [(packed weights, [(dy, dx)], in_step, pad_mode, OH, OW, salt_conv_args fields)]: one entry, or the output-parity
+        phases of an unfused transposed convolution (each planned against a dense stand-in of its own grid; they chain stats_part0).
+        ``plan``: the fields of a single launch that its partial count depends on."""
+        one = len(launches) == 1
+        parts = [self._conv_parts(x.view(), td, in_step, y.view() if one else shaped_view(1, x.B, OH, OW, y.C), OH, OW, **(plan or {}))
+                 for _, td, in_step, _, OH, OW, _ in launches]
+
+        def launch(**stats):
+            part0 = 0
+            for (wp, td, in_step, pad_mode, OH, OW, fields), n in zip(launches, parts):
+                prod = self._conv_launch(self.fwd, x.view(), wp, td, in_step, pad_mode, y.view(), OH, OW, part0=part0, **fields, **stats)
+                part0 += n
+            return prod
+        return self._bn_behind(launch, one, sum(parts), y, bn, relu, res, out, sfx)
 
     def _bn_train_bwd(self, y, bn, relu, res, out, w):
         """emit backward of out = relu?(bn(y) (+res)); returns nothing, leaves grad in y.grad (and res.grad)."""
-        hconv = getattr(out.buf, 'head_fused', None)
-        if hconv is not None:
+        if out.buf.head_fused is not None:
             # `out` was never stored: its only reader was the logit head (Graph.head took the affine_act over) - head gradients and this
             # BatchNorm's backward from (y, dlogits) alone
             if res is not None:
                 raise SaltError('fused head behind a residual BatchNorm')
-            C, Cout = bn.num_features, hconv.weight.shape[0]
-            S = fill(STRUCTS['salt_head_bn_bwd_args'](), y=y.view())
-            nparts = lib.salt_head_bn_bwd_parts(ctypes.byref(S))
-            assert y.grad_state() == 0, 'conv output gradient has a single producer'
-            sb = self.bwd.add('head_bn_bwd', dtype=self.dt, y=y.view(), relu=int(relu), mean=w['mean'].data_ptr(), invstd=w['invstd'].data_ptr(),
-                              gamma=bn.weight.data_ptr(), beta=bn.bias.data_ptr(), w=hconv.weight.data_ptr(), Cout=Cout, dy_nchw=self.dlogits.data_ptr(),
-                              partials=Scratch('head', nparts * Cout * (C + 1) * 4), nparts=nparts, gw=self._gp(hconv.weight),
-                              gb=self._gp(hconv.bias) if hconv.bias is not None else None, dgamma=self._gp(bn.weight), dbeta=self._gp(bn.bias),
-                              coef=self.f32(3 * C).data_ptr(), dy=y.gview())
-            self._fin_slot('bwd', 8 * 2 * C, (sb, 'fin_acc'))
-            return
-        S = STRUCTS['salt_bn_bwd_args']()
-        fill(S, y=y.view())
-        nparts = lib.salt_bn_bwd_parts(ctypes.byref(S))
+            return self._head_bn_bwd(y, bn, relu, out.buf.head_fused, w)
+        nparts = lib.salt_bn_bwd_parts(ctypes.byref(fill(STRUCTS['salt_bn_bwd_args'](), y=y.view())))
         C = bn.num_features
         gw, gb = self._gp(bn.weight), self._gp(bn.bias)
         coef = self.f32(3 * C)
-        dres = null_view()
-        acc_res = 0
-        if res is not None:
-            acc_res = res.grad_state()
-            dres = res.gview()
-        acc_y = y.grad_state()
-        assert acc_y == 0, 'conv output gradient has a single producer'
-        partials, ready = Scratch('bn_bwd', nparts * 2 * C * 4), 0
-        wr = out.buf.grad_writers
-        # (round 6: only the LAST writer has to cover exactly this slice - earlier writers of the same buffer, e.g. the decoder's data
-        #  gradient over the whole concat buffer an encoder output lives in, are complete before it runs)
-        same = (lambda w_: (w_[0], w_[1]) == (out.c0, out.C))
-        ok_wr = bool(wr) and same(wr[-1])
-        sec = wr[-1][2] if (ok_wr and isinstance(wr[-1][2], tuple) and wr[-1][2][0] == 'sec') else None
-        if sec is not None and not relu and res is None and self._fin_mode() == 2:
-            # round 6: dL/d(out) is the dres the main branch's bn_bwd wrote (this is a projection shortcut's BatchNorm): that apply pass
-            # took this layer's sums as well (salt_bn_bwd_args.sec_*) - apply-only here
-            partials, ready, producer = None, 3, sec[1]
-            self.bwd.set_fields(producer, sec_y=y.view(), sec_mean=w['mean'].data_ptr(), sec_invstd=w['invstd'].data_ptr())
-        elif sec is not None:
-            pass                                   # (a shape the secondary sums do not cover: this layer keeps its reduction pass)
-        elif ok_wr and wr[-1][2] is not None and C % self.ve == 0:
-            # the LAST writer of dL/d(out) is a plain data-gradient launch (it completes the gradient: earlier writers of the same
-            # slice were accumulated): its epilogue also reduces this layer's BatchNorm-backward sums over its pixel tiles
-            # (salt_conv_args.bnb_*), and bn_bwd skips its own pass over da and y.  With a residual the mask comes from `out`.
-            s = wr[-1][2]
-            nparts = lib.salt_conv_stats_parts(ctypes.byref(s))
-            if nparts < 1:
-                raise SaltError('conv plan failed: ' + lib.salt_last_error().decode())
-            self._n_bnb = getattr(self, '_n_bnb', 0) + 1
-            if self._fin_mode() == 2:
-                partials, ready = None, 3          # the launch adds the sums to fp64 shards; the apply pass of bn_bwd finalizes them
-            elif self._fin_mode() == 1:
-                partials, ready = None, 2          # the launch also finalizes (salt_conv_args.bnb_fin): bn_bwd is the apply pass only
-            else:
-                partials, ready = Scratch('bnb%d' % self._n_bnb, nparts * 2 * C * 4), 1
-            self.bwd.set_fields(s, bnb_y=y.view(), bnb_mean=w['mean'].data_ptr(), bnb_invstd=w['invstd'].data_ptr(), bnb_gamma=bn.weight.data_ptr(),
-                                bnb_beta=bn.bias.data_ptr(), bnb_partials=partials, bnb_relu=int(relu),
-                                bnb_a=out.view() if (relu and res is not None) else null_view())
-            producer = s
+        acc_res, dres = (res.grad_state(), res.gview()) if res is not None else (0, null_view())
+        assert y.grad_state() == 0, 'conv output gradient has a single producer'
+        kind, producer, partials, ready, nparts = self._bnb_sums_source(y, bn, relu, res, out, w, nparts)
         # without a residual a = relu(y*scale + shift): the kernel recomputes the mask from y and never reads `a`
         s2 = self.bwd.add('bn_bwd', dtype=self.dt, da=out.gview(), a=out.view() if (relu and res is not None) else null_view(), y=y.view(), relu=int(relu),
                           mean=w['mean'].data_ptr(), invstd=w['invstd'].data_ptr(), gamma=bn.weight.data_ptr(), beta=bn.bias.data_ptr(),
                           partials=partials, nparts=nparts, dgamma=gw, dbeta=gb, accumulate_param_grads=0,
                           coef=coef.data_ptr(), dy=y.gview(), dres=dres, accumulate_dres=acc_res, partials_ready=ready)
-        bias = getattr(out.buf, 'grad_bias', None)
+        bias = out.buf.grad_bias
         if bias is not None:
-            # (c0, C, dgap): the scSE backward left the channel-SE term out of dL/d(out); THIS bn_bwd - the slice's only consumer - adds it
-            if (bias[0], bias[1]) != (out.c0, out.C):
-                raise SaltError('gradient bias of %s covers channels [%d, %d), this BatchNorm backward reads [%d, %d)'
-                                % (out.buf.name, bias[0], bias[0] + bias[1], out.c0, out.c0 + out.C))
-            sums = bias[3] if len(bias) > 3 else None       # the scSE backward also took this layer's BatchNorm-backward sums (salt_scse_bwd_args.bnb_acc)
-            if ready != 0:
-                raise SaltError('a per-image gradient bias needs the reduction pass of bn_bwd (the producer of dL/da is not a convolution)')
-            if sums is not None:
-                ready, producer = 3, sums
-                self.bwd.set_fields(s2, partials=None, partials_ready=3)
-                self.bwd.patches = [q for q in self.bwd.patches if q[0] is not s2 or q[1] != ('partials',)]
-                self.bwd.set_fields(sums, bn_mean=w['mean'].data_ptr(), bn_invstd=w['invstd'].data_ptr())
-            self.bwd.set_fields(s2, da_bias=bias[2].data_ptr())
+            # the scSE backward left the channel-SE term out of dL/d(out); THIS bn_bwd - the slice's only consumer - adds it
+            self.bwd.set_fields(s2, da_bias=bias.dgap.data_ptr())
             out.buf.grad_bias = None
-        if res is not None and acc_res == 0 and ready == 3 and self._fin_mode() == 2 and C % self.ve == 0 and 256 % (C // self.ve) == 0 \
-                and getattr(res.buf, 'bn_train_out', None) == (res.c0, res.C) and bias is None and not res.plane_stride() \
-                and switches.get('SALT_BNB_SEC'):
-            res.buf.grad_writers[-1][2] = ('sec', s2)          # the residual's own BatchNorm (a projection shortcut) may ask this pass for its sums
-        if sec is not None and ready == 3 and producer is sec[1]:
+        if res is not None and acc_res == 0 and ready == PARTIALS_SHARDS and self._fin_mode() == 2 and C % self.ve == 0 and 256 % (C // self.ve) == 0 \
+                and res.buf.bn_train_out == (res.c0, res.C) and bias is None and switches.get('SALT_BNB_SEC'):
+            res.offer_carrier(SUMS_SEC, s2)            # the residual's own BatchNorm (a projection shortcut) may ask this pass for its sums (never a planar one)
+        self._bnb_wire(kind, producer, ready, s2, C, bias)
+
+    def _bnb_sums_source(self, y, bn, relu, res, out, w, nparts):
+        """Who supplies the BatchNorm-backward sums of the layer out = relu?(bn(y) (+res))?  -> (SUMS_* kind, the supplier's argument struct
+        | None, the ``partials`` of the layer's bn_bwd, its ``partials_ready`` code, its ``nparts``).  A supplier other than the layer's own
+        reduction pass is told here what to sum over (sec_* / bnb_* / bn_* fields); its shard slots are wired by _bnb_wire once the
+        bn_bwd exists."""
+        C = bn.num_features
+        kind, producer, partials, ready = SUMS_OWN, None, Scratch('bn_bwd', nparts * 2 * C * 4), PARTIALS_OWN
+        wr = out.buf.grad_writers
+        # (round 6: only the LAST writer has to cover exactly this slice - earlier writers of the same buffer, e.g. the decoder's data
+        #  gradient over the whole concat buffer an encoder output lives in, are complete before it runs)
+        last = wr[-1] if (wr and (wr[-1].c0, wr[-1].C) == (out.c0, out.C)) else None
+        if last is not None and last.kind == SUMS_SEC:
+            if not relu and res is None and self._fin_mode() == 2:
+                # round 6: dL/d(out) is the dres the main branch's bn_bwd wrote (this is a projection shortcut's BatchNorm): that apply
+                # pass took this layer's sums as well (salt_bn_bwd_args.sec_*) - apply-only here
+                kind, producer, partials, ready = SUMS_SEC, last.carrier, None, PARTIALS_SHARDS
+                self.bwd.set_fields(producer, sec_y=y.view(), sec_mean=w['mean'].data_ptr(), sec_invstd=w['invstd'].data_ptr())
+            # (else a shape the secondary sums do not cover: this layer keeps its reduction pass)
+        elif last is not None and last.kind == SUMS_CONV and C % self.ve == 0:
+            # the LAST writer of dL/d(out) is a plain data-gradient launch (it completes the gradient: earlier writers of the same
+            # slice were accumulated): its epilogue also reduces this layer's BatchNorm-backward sums over its pixel tiles
+            # (salt_conv_args.bnb_*), and bn_bwd skips its own pass over da and y.  With a residual the mask comes from `out`.
+            kind, producer = SUMS_CONV, last.carrier
+            nparts = lib.salt_conv_stats_parts(ctypes.byref(producer))
+            if nparts < 1:
+                raise SaltError('conv plan failed: ' + lib.salt_last_error().decode())
+            self._n_bnb += 1
+            if self._fin_mode() == 2:
+                partials, ready = None, PARTIALS_SHARDS          # the launch adds the sums to fp64 shards; the apply pass of bn_bwd finalizes them
+            elif self._fin_mode() == 1:
+                partials, ready = None, PARTIALS_FINALIZED       # the launch also finalizes (salt_conv_args.bnb_fin): bn_bwd is the apply pass only
+            else:
+                partials, ready = Scratch('bnb%d' % self._n_bnb, nparts * 2 * C * 4), PARTIALS_FILLED
+            self.bwd.set_fields(producer, bnb_y=y.view(), bnb_mean=w['mean'].data_ptr(), bnb_invstd=w['invstd'].data_ptr(), bnb_gamma=bn.weight.data_ptr(),
+                                bnb_beta=bn.bias.data_ptr(), bnb_partials=partials, bnb_relu=int(relu),
+                                bnb_a=out.view() if (relu and res is not None) else null_view())
+        bias = out.buf.grad_bias
+        if bias is not None:
+            if (bias.c0, bias.C) != (out.c0, out.C):
+                raise SaltError('gradient bias of %s covers channels [%d, %d), this BatchNorm backward reads [%d, %d)'
+                                % (out.buf.name, bias.c0, bias.c0 + bias.C, out.c0, out.c0 + out.C))
+            if ready != PARTIALS_OWN:
+                raise SaltError('a per-image gradient bias needs the reduction pass of bn_bwd (the producer of dL/da is not a convolution)')
+            if bias.sums_from is not None:
+                # the scSE backward also took this layer's BatchNorm-backward sums (salt_scse_bwd_args.bnb_acc)
+                kind, producer, partials, ready = SUMS_SCSE, bias.sums_from, None, PARTIALS_SHARDS
+                self.bwd.set_fields(producer, bn_mean=w['mean'].data_ptr(), bn_invstd=w['invstd'].data_ptr())
+        return kind, producer, partials, ready, nparts
+
+    def _bnb_wire(self, kind, producer, ready, s2, C, bias):
+        """Shard slots / tickets between the supplier of a layer's BatchNorm-backward sums (_bnb_sums_source) and its bn_bwd ``s2``."""
+        if kind == SUMS_SEC:
             self._fin_slot('bwd', 8 * 2 * C, (producer, 'sec_acc'), (s2, 'fin_acc'))
-        elif ready == 3:
-            peers = [(bias[4], 'bnb_acc')] if (bias is not None and len(bias) > 4 and bias[4] is not None) else []   # scse_fc_grads reads the same 6 C + 1 wide rows
+        elif kind == SUMS_SCSE:
+            peers = [(bias.fc_grads, 'bnb_acc')] if bias.fc_grads is not None else []       # scse_fc_grads reads the same 6 C + 1 wide rows
             self._fin_slot('bwd', 8 * 2 * C, (producer, 'bnb_acc'), (s2, 'fin_acc'), *peers)
-        elif ready == 2:
+        elif kind == SUMS_CONV and ready == PARTIALS_SHARDS:
+            self._fin_slot('bwd', 8 * 2 * C, (producer, 'bnb_acc'), (s2, 'fin_acc'))
+        elif kind == SUMS_CONV and ready == PARTIALS_FINALIZED:
             acc, ticket = self._fin_buffers(8 * 2 * C)
             self.bwd.set_fields(producer, bnb_fin=ctypes.addressof(s2), bnb_acc=acc, bnb_ticket=ticket)
-        elif ready == 0 and self._fin_mode() == 2:
+        elif kind == SUMS_OWN and self._fin_mode() == 2:
             self._fin_slot('bwd', 8 * 2 * C, (s2, 'fin_acc'))       # reduction pass -> shards -> apply pass
-        elif ready == 0 and self._fin_mode() == 1:
+        elif kind == SUMS_OWN and self._fin_mode() == 1:
             acc, ticket = self._fin_buffers(8 * 2 * C)       # the reduction pass of bn_bwd finalizes in-launch
             self.bwd.set_fields(s2, fin_acc=acc, fin_ticket=ticket)
+        # (SUMS_CONV with PARTIALS_FILLED, SUMS_OWN under SALT_BN_FIN=0: per-tile partials in scratch, nothing to wire)
 
     # ------------------------------------------------------------------ dense convolution (+BN +ReLU +residual)
     def conv(self, x, conv, bn=None, relu=False, res=None, out=None, replicate=False, name=''):
@@ -719,14 +818,11 @@ class Graph:
         if replicate:
             assert stride == 1
             taps = [(kh, kw, kh - (KH - 1), kw) for kh in range(KH) for kw in range(KW)]
-            pad_mode = 1
-            OH, OW = x.H, x.W
+            pad_mode, OH, OW = 1, x.H, x.W
         else:
             py, px = conv.padding
             taps = conv_taps(KH, KW, py, px)
-            pad_mode = 0
-            OH = (x.H + 2 * py - KH) // stride + 1
-            OW = (x.W + 2 * px - KW) // stride + 1
+            pad_mode, OH, OW = 0, (x.H + 2 * py - KH) // stride + 1, (x.W + 2 * px - KW) // stride + 1
         tk = [(t[0], t[1]) for t in taps]
         td = [(t[2], t[3]) for t in taps]
         pk = eng.packed(conv, tk, transposed=False)
@@ -734,58 +830,43 @@ class Graph:
         if out is None:
             out = self.new_act(x.B, OH, OW, Cout, name)
         assert (out.B, out.H, out.W, out.C) == (x.B, OH, OW, Cout), name
-        y = None
-        w = None
-        lz = getattr(x.buf, 'lazy', None) if (self.train and x.c0 == 0 and x.C == x.buf.C and len(taps) == 9 and stride == 1) else None
+        y = w = None
+        lz = x.buf.lazy if (self.train and x.c0 == 0 and x.C == x.buf.C and len(taps) == 9 and stride == 1) else None
         if bn is not None and self.train:
             y = self.new_act(x.B, OH, OW, Cout, name + '.y')
+            xin, fold = x, {}
             if lz is not None and self._fin_on():
                 # candidate for the loader fold: read the producer's raw output and transform it on the way into LDS
-                nparts = self._conv_parts(lz['y'].view(), td, stride, y.view(), OH, OW)
-                S = fill(STRUCTS['salt_conv_args'](), dtype=self.dt, x=lz['y'].view(), w=1, ntaps=9, tap_dy=[t[0] for t in td], tap_dx=[t[1] for t in td],
-                         in_step=1, pad_mode=pad_mode, y=y.view(), OH=OH, OW=OW, out_step=1, in_fin=ctypes.addressof(lz['F']), in_fin_acc=8, in_relu=1)
+                S = self._conv_probe(lz.y.view(), 1, td, 1, pad_mode, y.view(), OH, OW, in_fin=ctypes.addressof(lz.F), in_fin_acc=8, in_relu=1)
                 if lib.salt_conv_kernel_id(ctypes.byref(S)) in (1, 2, 3, 4):
-                    prod = self._conv_launch(self.fwd, lz['y'].view(), pk.data_ptr(), td, stride, pad_mode, y.view(), OH, OW, bias=bias,
-                                             in_fin=ctypes.addressof(lz['F']), in_relu=1)
-                    self._fin_patches.append((prod, 'in_fin_acc', 'fwd', lz['off']))
-                    lz['users'].append(prod)
-                else:
-                    lz = None
-                    prod = self._conv_launch(self.fwd, x.view(), pk.data_ptr(), td, stride, pad_mode, y.view(), OH, OW, bias=bias)
-                w = self._bn_train_fwd(y, bn, relu, res, out, nparts, None, None, producer=prod)
-            elif self._fin_on():
+                    xin, fold = lz.y, dict(in_fin=ctypes.addressof(lz.F), in_relu=1)
+            if not fold:
                 lz = None
-                nparts = self._conv_parts(x.view(), td, stride, y.view(), OH, OW)
-                prod = self._conv_launch(self.fwd, x.view(), pk.data_ptr(), td, stride, pad_mode, y.view(), OH, OW, bias=bias)
-                w = self._bn_train_fwd(y, bn, relu, res, out, nparts, None, None, producer=prod)
-            else:
-                lz = None
-                nparts = self._conv_parts(x.view(), td, stride, y.view(), OH, OW)
-                stats, cnt = Scratch('stats' + self._scratch_sfx, 4 * lib.salt_bn_stats_floats(nparts, Cout)), Scratch('stats_cnt' + self._scratch_sfx, nparts * 4)
-                self._conv_launch(self.fwd, x.view(), pk.data_ptr(), td, stride, pad_mode, y.view(), OH, OW, bias=bias, stats=stats, stats_cnt=cnt)
-                w = self._bn_train_fwd(y, bn, relu, res, out, nparts, stats, cnt)
+            # (workspace names carry _scratch_sfx: a side-stream launch gets its own 'stats@side')
+            w, prod = self._conv_bn_train(xin, y, [(pk.data_ptr(), td, stride, pad_mode, OH, OW, dict(bias=bias, **fold))], bn, relu, res, out,
+                                          self._scratch_sfx)
+            if fold:
+                self._fin_patches.append((prod, 'in_fin_acc', 'fwd', lz.off))
+                lz.users.append(prod)
         elif bn is not None:
             w = eng.bn_work(bn)
+            act = dict(bias=bias, scale=w['scale'].data_ptr(), shift=w['shift'].data_ptr())
             if res is None:
-                self._conv_launch(self.fwd, x.view(), pk.data_ptr(), td, stride, pad_mode, out.view(), OH, OW, bias=bias,
-                                  scale=w['scale'].data_ptr(), shift=w['shift'].data_ptr(), relu=int(relu))
+                self._conv_launch(self.fwd, x.view(), pk.data_ptr(), td, stride, pad_mode, out.view(), OH, OW, relu=int(relu), **act)
             elif Cout % self.ve == 0 and not switches.get('SALT_NO_RES_FOLD'):
                 # eval-mode residual block: folded BN + identity add + ReLU all in the convolution's epilogue (salt_conv_args.res) - the
                 # same values as the separate affine_act pass below, bit for bit, without its launch and its trip over `out`
-                if getattr(res, 'on_side', False):
+                if res.on_side:
                     self.join()
-                self._conv_launch(self.fwd, x.view(), pk.data_ptr(), td, stride, pad_mode, out.view(), OH, OW, bias=bias,
-                                  scale=w['scale'].data_ptr(), shift=w['shift'].data_ptr(), relu=int(relu), res=res.view())
+                self._conv_launch(self.fwd, x.view(), pk.data_ptr(), td, stride, pad_mode, out.view(), OH, OW, relu=int(relu), res=res.view(), **act)
             else:
-                self._conv_launch(self.fwd, x.view(), pk.data_ptr(), td, stride, pad_mode, out.view(), OH, OW, bias=bias,
-                                  scale=w['scale'].data_ptr(), shift=w['shift'].data_ptr(), relu=0)
-                if getattr(res, 'on_side', False):
+                self._conv_launch(self.fwd, x.view(), pk.data_ptr(), td, stride, pad_mode, out.view(), OH, OW, relu=0, **act)
+                if res.on_side:
                     self.join()
                 self.fwd.add('affine_act', dtype=self.dt, y=out.view(), scale=None, shift=None, res=res.view(), relu=int(relu), a=out.view())
         else:
             assert res is None
             self._conv_launch(self.fwd, x.view(), pk.data_ptr(), td, stride, pad_mode, out.view(), OH, OW, bias=bias, relu=int(relu))
-
         out.on_side = self.fwd.default_stream == 1
         if self.train:
             def backward():
@@ -799,12 +880,11 @@ class Graph:
                     if relu:
                         self.bwd.add('relu_bwd', dtype=self.dt, da=out.gview(), a=out.view(), dy=out.gview(), accumulate=0)
                 # weight gradient: P = dY (a = cout), Q = X (b = cin)
-                if lz is not None and lz['dropped']:
+                if lz is not None and lz.dropped:
                     # the activation was never materialised and the weight-gradient kernels (LDS-DMA loaders) cannot transform their
                     # operand: a graph built under SALT_FWD_BN_FOLD has no backward pass (fail loudly, never a wrong gradient)
                     raise SaltError('SALT_FWD_BN_FOLD graphs are forward-only (the folded activation of %s does not exist for the weight gradient)' % name)
-                xq = x
-                self._wgrad(dy.gview(), xq.view(), td, tk, stride, pad_mode, conv.weight, KH, KW)
+                self._wgrad(dy.gview(), x.view(), td, tk, stride, pad_mode, conv.weight, KH, KW)
                 # data gradient
                 if x.buf.name != '__input__':
                     self._dgrad(conv, x, dy, taps, stride, replicate, KH, KW)
@@ -839,15 +919,11 @@ class Graph:
         return (kh, kw) == (1, 1) and ci == C and 1 <= co <= 4 and C % self.ve == 0 and 1 <= cpv <= 64 and cpv & (cpv - 1) == 0
 
     def _head_bn(self, y, bn, relu, hconv, logits, producer):
-        """forward salt_head_bn behind ``producer`` (which adds y's statistics to the fp64 shards) + the tape entry of salt_head_bn_bwd,
-        which leaves dL/dy in y.grad: returned through ``self._head_bn_bwd`` - the caller's own backward closure calls it first."""
-        eng = self.engine
+        """forward salt_head_bn behind ``producer`` (which adds y's statistics to the fp64 shards); the caller's backward closure starts
+        with its counterpart _head_bn_bwd."""
         C = bn.num_features
-        w = eng.bn_work(bn)
-        nbt = bn.num_batches_tracked.data_ptr() if bn.num_batches_tracked is not None else None
-        F = fill(STRUCTS['salt_bn_finalize_args'](), C=C, gamma=bn.weight.data_ptr(), beta=bn.bias.data_ptr(), running_mean=bn.running_mean.data_ptr(),
-                 running_var=bn.running_var.data_ptr(), num_batches_tracked=nbt, momentum=bn.momentum, eps=bn.eps, mean=w['mean'].data_ptr(),
-                 invstd=w['invstd'].data_ptr(), scale=w['scale'].data_ptr(), shift=w['shift'].data_ptr())
+        w, fin = self._bn_fin_fields(bn)
+        F = fill(STRUCTS['salt_bn_finalize_args'](), **fin)
         self.keep.append(F)
         Cout = hconv.weight.shape[0]
         hb = self.fwd.add('head_bn', dtype=self.dt, y=y.view(), fin=ctypes.addressof(F), relu=int(relu), w=hconv.weight.data_ptr(),
@@ -855,19 +931,21 @@ class Graph:
         self._fin_slot('fwd', 8 * (2 * C + 1), (producer, 'fin_acc'), (hb, 'fin_acc'))
         self.dlogits = self.alloc(tuple(logits.shape), torch.float32)
 
-        def backward():
-            S = fill(STRUCTS['salt_head_bn_bwd_args'](), y=y.view())
-            nparts = lib.salt_head_bn_bwd_parts(ctypes.byref(S))
-            assert y.grad_state() == 0, 'conv output gradient has a single producer'
-            coef = self.f32(3 * C)
-            sb = self.bwd.add('head_bn_bwd', dtype=self.dt, y=y.view(), relu=int(relu), mean=w['mean'].data_ptr(), invstd=w['invstd'].data_ptr(),
-                              gamma=bn.weight.data_ptr(), beta=bn.bias.data_ptr(), w=hconv.weight.data_ptr(), Cout=Cout, dy_nchw=self.dlogits.data_ptr(),
-                              partials=Scratch('head', nparts * Cout * (C + 1) * 4), nparts=nparts, gw=self._gp(hconv.weight),
-                              gb=self._gp(hconv.bias) if hconv.bias is not None else None, dgamma=self._gp(bn.weight), dbeta=self._gp(bn.bias),
-                              coef=coef.data_ptr(), dy=y.gview())
-            self._fin_slot('bwd', 8 * 2 * C, (sb, 'fin_acc'))
-        self._head_bn_bwd = backward
         return w
+
+    def _head_bn_bwd(self, y, bn, relu, hconv, w):
+        """backward of the fused BatchNorm apply + ReLU + logit head (Graph.head / _head_bn): head gradients and the BatchNorm backward
+        from (y, dlogits) alone; leaves dL/dy in y.grad."""
+        C, Cout = bn.num_features, hconv.weight.shape[0]
+        S = fill(STRUCTS['salt_head_bn_bwd_args'](), y=y.view())
+        nparts = lib.salt_head_bn_bwd_parts(ctypes.byref(S))
+        assert y.grad_state() == 0, 'conv output gradient has a single producer'
+        sb = self.bwd.add('head_bn_bwd', dtype=self.dt, y=y.view(), relu=int(relu), mean=w['mean'].data_ptr(), invstd=w['invstd'].data_ptr(),
+                          gamma=bn.weight.data_ptr(), beta=bn.bias.data_ptr(), w=hconv.weight.data_ptr(), Cout=Cout, dy_nchw=self.dlogits.data_ptr(),
+                          partials=Scratch('head', nparts * Cout * (C + 1) * 4), nparts=nparts, gw=self._gp(hconv.weight),
+                          gb=self._gp(hconv.bias) if hconv.bias is not None else None, dgamma=self._gp(bn.weight), dbeta=self._gp(bn.bias),
+                          coef=self.f32(3 * C).data_ptr(), dy=y.gview())
+        self._fin_slot('bwd', 8 * 2 * C, (sb, 'fin_acc'))
 
     def hyper_level(self, x, conv, c0, name='hyper.z'):
         """z = [W[:, c0 : c0 + x.C, kh, kw]]_taps x  at x's (LOW) resolution: one 1x1 convolution x.C -> 9 Cout whose output channel
@@ -922,32 +1000,30 @@ class Graph:
         ac = int(bool(getattr(getattr(self.engine, 'module', None), 'align_corners', False)))
         y = self.new_act(x.B, x.H, x.W, Cout, name + '.y')
         self._conv_launch(self.fwd, x.view(), pk.data_ptr(), td, 1, 1, y.view(), x.H, x.W, bias=bias)
-        if any(getattr(z, 'on_side', False) for z in zs):
+        if any(z.on_side for z in zs):
             self.join()
         st = dict(dtype=self.dt, nlev=len(zs), z=[z.view() for z in zs], R=list(Rs), y_in=y.view(), backward=0, align_corners=ac)
+        zs, Rs = list(zs), list(Rs)
+
+        def backward_from_dy():
+            """dL/dy -> the stencil adjoint into every dL/dz, the weight gradient and the data gradient of the full-resolution part"""
+            for z in zs:
+                assert z.grad_state() == 0
+            self.bwd.add('hyper_stencil', dtype=self.dt, nlev=len(zs), z=[z.gview() for z in zs], R=Rs, y_in=null_view(), y=y.gview(),
+                         backward=1, align_corners=ac)
+            self._wgrad(y.gview(), x.view(), td, tk, 1, 1, conv.weight, KH, KW, b_slice=(0, Cin))
+            self._dgrad(conv, x, y, taps, 1, True, KH, KW, d1=d1)
         if self.train and head is not None:
             # round 6: BatchNorm apply + ReLU + logit head in ONE pass over the raw sum (salt_head_bn): the block's activation and its
             # gradient are never stored.  Backward: salt_head_bn_bwd writes dL/dy directly (head gradients + BatchNorm-backward sums in
             # its first pass), then the stencil adjoint / weight gradient / data gradient as below.
             prod = self.fwd.add('hyper_stencil', y=y.view(), **st)
             w = self._head_bn(y, bn, relu, head[0], head[1], prod)
-            zs_, Rs_ = list(zs), list(Rs)
-
-            hb_bwd = self._head_bn_bwd
-
-            def backward():
-                hb_bwd()
-                for z in zs_:
-                    assert z.grad_state() == 0
-                self.bwd.add('hyper_stencil', dtype=self.dt, nlev=len(zs_), z=[z.gview() for z in zs_], R=Rs_, y_in=null_view(), y=y.gview(),
-                             backward=1, align_corners=ac)
-                self._wgrad(y.gview(), x.view(), td, tk, 1, 1, conv.weight, KH, KW, b_slice=(0, Cin))
-                self._dgrad(conv, x, y, taps, 1, True, KH, KW, d1=d1)
-            self.tape.append(backward)
+            self.tape.append(lambda: (self._head_bn_bwd(y, bn, relu, head[0], w), backward_from_dy()))
             return None
         if self.train:
-            prod = self.fwd.add('hyper_stencil', y=y.view(), **st)
-            w = self._bn_train_fwd(y, bn, relu, None, out, 0, None, None, producer=prod)
+            # (hyper_factor_ok: consumer-side shards only - the stencil has no per-tile partials protocol, so no workspace is ever named)
+            w, _ = self._bn_behind(lambda: self.fwd.add('hyper_stencil', y=y.view(), **st), True, 0, y, bn, relu, None, out, '')
         elif head is not None:
             w = eng.bn_work(bn)
             hconv, logits = head
@@ -963,15 +1039,7 @@ class Graph:
             self.fwd.add('hyper_stencil', y=out.view(), scale=w['scale'].data_ptr(), shift=w['shift'].data_ptr(), relu=int(relu), **st)
         out.on_side = False
         if self.train:
-            def backward():
-                self._bn_train_bwd(y, bn, relu, None, out, w)
-                for z in zs:
-                    assert z.grad_state() == 0
-                self.bwd.add('hyper_stencil', dtype=self.dt, nlev=len(zs), z=[z.gview() for z in zs], R=list(Rs), y_in=null_view(), y=y.gview(),
-                             backward=1, align_corners=ac)
-                self._wgrad(y.gview(), x.view(), td, tk, 1, 1, conv.weight, KH, KW, b_slice=(0, Cin))
-                self._dgrad(conv, x, y, taps, 1, True, KH, KW, d1=d1)
-            self.tape.append(backward)
+            self.tape.append(lambda: (self._bn_train_bwd(y, bn, relu, None, out, w), backward_from_dy()))
         return out
 
     def _wgrad(self, p_view, q_view, taps_dydx, taps_khkw, q_step, pad_mode, weight, KH, KW, b_slice=None, tapgemm=None):
@@ -990,17 +1058,14 @@ class Graph:
             taps_khkw = list(tapgemm[1])
         for i in range(0, len(taps_dydx), 9 if len(taps_dydx) != 16 else 4):
             chunk = list(range(i, min(i + (9 if len(taps_dydx) != 16 else 4), len(taps_dydx))))
-            S = STRUCTS['salt_conv_wgrad_args']()
             qp = q_view.B * q_view.H * q_view.W * q_view.cs if 0 < q_view.cs < q_view.C else 0       # planar Q (Act._view of a whole planar buffer)
-            fill(S, dtype=self.dt, p=p_view, q=q_view, ntaps=len(chunk), tap_dy=[taps_dydx[j][0] for j in chunk],
-                 tap_dx=[taps_dydx[j][1] for j in chunk], q_step=q_step, pad_mode=pad_mode, q_plane=qp)
-            ns = lib.salt_conv_wgrad_nsplit(ctypes.byref(S))
+            wg = dict(dtype=self.dt, p=p_view, q=q_view, ntaps=len(chunk), tap_dy=[taps_dydx[j][0] for j in chunk],
+                      tap_dx=[taps_dydx[j][1] for j in chunk], q_step=q_step, pad_mode=pad_mode, q_plane=qp)
+            ns = lib.salt_conv_wgrad_nsplit(ctypes.byref(fill(STRUCTS['salt_conv_wgrad_args'](), **wg)))
             if ns < 0:
                 raise SaltError('wgrad plan failed: ' + lib.salt_last_error().decode())
             nbytes = ns * len(chunk) * Ca * Cb * 4
-            self.bwd.add('conv_wgrad', stream=1, dtype=self.dt, p=p_view, q=q_view, ntaps=len(chunk), tap_dy=[taps_dydx[j][0] for j in chunk],
-                                 tap_dx=[taps_dydx[j][1] for j in chunk], q_step=q_step, pad_mode=pad_mode,
-                         partials=Scratch('wgrad', nbytes), nsplit=ns, q_plane=qp)
+            self.bwd.add('conv_wgrad', stream=1, partials=Scratch('wgrad', nbytes), nsplit=ns, **wg)
             rt = range(len(taps_khkw)) if tapgemm is not None else chunk
             rfields = dict(nsplit=ns, ntaps=len(chunk), Ca=Ca, Cb=Cb, KH=KH, KW=KW, tap_kh=[taps_khkw[j][0] for j in rt],
                            tap_kw=[taps_khkw[j][1] for j in rt], accumulate=0, **extra)
@@ -1028,8 +1093,7 @@ class Graph:
                 # gradient) the launch can carry the BatchNorm-backward sums of x's producer
                 s = self._conv_launch(self.bwd, dy.gview(), pk.data_ptr(), td, 1, 0, x.gview(), Hp, Wp, accumulate=acc,
                                       fold_top=top, fold_right=right, stream=self._bwd_pack_tag())
-                if not x.plane_stride():               # (a planar dL/dx has one dense consumer per plane: nothing to ride along)
-                    x.buf.grad_writers[-1][2] = s
+                x.offer_carrier(SUMS_CONV, s)
                 return
             # strip fold: interior pixels go straight into x.grad, only the pad ring takes the detour through scratch
             scs = _round_up(x.C, self.ve)
@@ -1043,8 +1107,7 @@ class Graph:
         if stride == 1:
             td = [(-t[2], -t[3]) for t in taps]
             s = self._conv_launch(self.bwd, dy.gview(), pk.data_ptr(), td, 1, 0, x.gview(), x.H, x.W, accumulate=acc, stream=self._bwd_pack_tag())
-            if not x.plane_stride():
-                x.buf.grad_writers[-1][2] = s      # a plain full-grid launch: can carry the BatchNorm-backward sums of x's producer
+            x.offer_carrier(SUMS_CONV, s)              # a plain full-grid launch: can carry the BatchNorm-backward sums of x's producer
             return
         # stride 2: the data gradient is a transposed convolution - four output-parity phases
         phases = []
@@ -1059,8 +1122,7 @@ class Graph:
             pk_t, elems = eng.packed_phases(conv, phase_taps, transposed=True, bwd=True)
             s = self._conv_launch(self.bwd, dy.gview(), pk_t.data_ptr(), td_u, 1, 0, x.gview(), x.H // 2, x.W // 2, out_step=2, accumulate=acc,
                                   nphase=4, w_phase_elems=elems, stream=self._bwd_pack_tag())
-            if not x.plane_stride():
-                x.buf.grad_writers[-1][2] = s      # all four parities of an even grid: every pixel once - can carry the BatchNorm-backward sums (round 6)
+            x.offer_carrier(SUMS_CONV, s)              # all four parities of an even grid: every pixel once - can carry the BatchNorm-backward sums (round 6)
             return
         if any(not sel for _, _, sel in phases) and not acc:
             self.fill(x, 0.0, grad=True)
@@ -1133,58 +1195,24 @@ class Graph:
                        if (fy + p - u) % 2 == 0 and (fx + p - v) % 2 == 0]
                 phases.append((fy, fx, sel))
         fused = self._phase_fused([[((s_[2], s_[3]), (s_[0], s_[1])) for s_ in sel] for _, _, sel in phases], OH, OW)
-        total_parts, stats, cnt, fin_prod = 0, None, None, None
         if fused is not None:
             # ONE launch for the four output-parity phases of the transposed convolution
             td_u, phase_taps = fused
             pk_t, elems = eng.packed_phases(deconv, phase_taps, transposed=True)
-            if train_bn:
-                S = STRUCTS['salt_conv_args']()
-                fill(S, dtype=self.dt, x=x.view(), w=1, ntaps=len(td_u), tap_dy=[t[0] for t in td_u], tap_dx=[t[1] for t in td_u], in_step=1, pad_mode=0,
-                     y=tgt.view(), OH=x.H, OW=x.W, out_step=2, nphase=4, w_phase_elems=elems)
-                total_parts = lib.salt_conv_stats_parts(ctypes.byref(S))
-                if total_parts < 0:
-                    raise SaltError('conv plan failed: ' + lib.salt_last_error().decode())
-                if self._fin_on():
-                    fin_prod = self._conv_launch(self.fwd, x.view(), pk_t.data_ptr(), td_u, 1, 0, tgt.view(), x.H, x.W, out_step=2, bias=bias,
-                                                 nphase=4, w_phase_elems=elems)
-                else:
-                    stats = Scratch('stats', 4 * lib.salt_bn_stats_floats(total_parts, Cout))
-                    cnt = Scratch('stats_cnt', total_parts * 4)
-                    self._conv_launch(self.fwd, x.view(), pk_t.data_ptr(), td_u, 1, 0, tgt.view(), x.H, x.W, out_step=2, bias=bias, stats=stats, stats_cnt=cnt,
-                                      nphase=4, w_phase_elems=elems)
-            elif bn is not None:
-                self._conv_launch(self.fwd, x.view(), pk_t.data_ptr(), td_u, 1, 0, tgt.view(), x.H, x.W, out_step=2, bias=bias,
-                                  scale=w['scale'].data_ptr(), shift=w['shift'].data_ptr(), relu=int(relu), nphase=4, w_phase_elems=elems)
-            else:
-                self._conv_launch(self.fwd, x.view(), pk_t.data_ptr(), td_u, 1, 0, tgt.view(), x.H, x.W, out_step=2, bias=bias, relu=int(relu),
-                                  nphase=4, w_phase_elems=elems)
-            phases = []
-        part0 = 0
-        plans = []
-        for fy, fx, sel in phases:
-            td = [(s[2], s[3]) for s in sel]
-            n = self._conv_parts(x.view(), td, 1, shaped_view(1, x.B, x.H, x.W, Cout), x.H, x.W) if train_bn else 0
-            plans.append(n)
-            total_parts += n
-        if fused is None:
-            stats = Scratch('stats', 4 * lib.salt_bn_stats_floats(total_parts, Cout)) if train_bn else None
-            cnt = Scratch('stats_cnt', total_parts * 4) if train_bn else None
-        for (fy, fx, sel), n in zip(phases, plans):
-            pk = eng.packed(deconv, [(s[0], s[1]) for s in sel], transposed=True)       # n = cout (D1), c = cin (D0)
-            td = [(s[2], s[3]) for s in sel]
-            if train_bn:
-                self._conv_launch(self.fwd, x.view(), pk.data_ptr(), td, 1, 0, tgt.view(), x.H, x.W, out_step=2, out_oy=fy, out_ox=fx,
-                                  bias=bias, stats=stats, stats_cnt=cnt, part0=part0)
-            elif bn is not None:
-                self._conv_launch(self.fwd, x.view(), pk.data_ptr(), td, 1, 0, tgt.view(), x.H, x.W, out_step=2, out_oy=fy, out_ox=fx,
-                                  bias=bias, scale=w['scale'].data_ptr(), shift=w['shift'].data_ptr(), relu=int(relu))
-            else:
-                self._conv_launch(self.fwd, x.view(), pk.data_ptr(), td, 1, 0, tgt.view(), x.H, x.W, out_step=2, out_oy=fy, out_ox=fx,
-                                  bias=bias, relu=int(relu))
-            part0 += n
+            plan = dict(out_step=2, nphase=4, w_phase_elems=elems)
+            launches = [(pk_t.data_ptr(), td_u, 1, 0, x.H, x.W, dict(bias=bias, **plan))]
+        else:
+            plan = None
+            launches = [(eng.packed(deconv, [(s[0], s[1]) for s in sel], transposed=True).data_ptr(), [(s[2], s[3]) for s in sel], 1, 0, x.H, x.W,
+                         dict(out_step=2, out_oy=fy, out_ox=fx, bias=bias)) for fy, fx, sel in phases]       # n = cout (D1), c = cin (D0)
         if train_bn:
-            self._bn_train_fwd(tgt, bn, relu, None, out, total_parts, stats, cnt, producer=fin_prod)
+            # The workspace names carry NO _scratch_sfx here, unlike conv / _stem_s2d: a transposed convolution emitted inside Graph.side()
+            # shares 'stats' / 'stats_cnt' with the main stream.  Known asymmetry, kept as it is (it decides which workspace a launch uses).
+            self._conv_bn_train(x, tgt, launches, bn, relu, None, out, '', plan=plan)
+        else:
+            act = dict(scale=w['scale'].data_ptr(), shift=w['shift'].data_ptr()) if bn is not None else {}
+            for wp, td, in_step, pad_mode, oh, ow, fields in launches:
+                self._conv_launch(self.fwd, x.view(), wp, td, in_step, pad_mode, tgt.view(), oh, ow, relu=int(relu), **act, **fields)
         if self.train:
             def backward():
                 if bn is None:
@@ -1217,17 +1245,15 @@ class Graph:
         common = dict(dtype=self.dt, x=x_nchw.data_ptr(), B=B, Cin=Cin, H=H, W=W, w=conv.weight.data_ptr(), K=K, stride=stride, pad=pad, bias=bias)
         if self.train:
             y = self.new_act(B, OH, OW, Cout, name + '.y')
-            S = STRUCTS['salt_conv_first_args']()
-            fill(S, B=B, Cin=Cin, H=H, W=W, K=K, stride=stride, pad=pad)
+            S = fill(STRUCTS['salt_conv_first_args'](), B=B, Cin=Cin, H=H, W=W, K=K, stride=stride, pad=pad)
             nparts = lib.salt_conv_first_stats_parts(ctypes.byref(S))
-            stats, cnt = Scratch('stats' + self._scratch_sfx, 4 * lib.salt_bn_stats_floats(nparts, Cout)), Scratch('stats_cnt' + self._scratch_sfx, nparts * 4)
-            self.fwd.add('conv_first', y=y.view(), relu=0, stats=stats, stats_cnt=cnt, **common)
-            w = self._bn_train_fwd(y, bn, relu, None, out, nparts, stats, cnt)
+            # (the direct kernel knows the per-tile partials protocol only)
+            w, _ = self._bn_behind(lambda **st: self.fwd.add('conv_first', y=y.view(), relu=0, **st, **common), False, nparts, y, bn, relu, None, out,
+                                   self._scratch_sfx)
 
             def backward():
                 self._bn_train_bwd(y, bn, relu, None, out, w)
-                S2 = STRUCTS['salt_conv_first_wgrad_args']()
-                fill(S2, B=B, Cin=Cin, H=H, W=W, K=K, stride=stride, pad=pad)
+                S2 = fill(STRUCTS['salt_conv_first_wgrad_args'](), B=B, Cin=Cin, H=H, W=W, K=K, stride=stride, pad=pad)
                 np_ = lib.salt_conv_first_wgrad_parts(ctypes.byref(S2))
                 self.bwd.add('conv_first_wgrad', stream=1, dtype=self.dt, x=x_nchw.data_ptr(), B=B, Cin=Cin, H=H, W=W, K=K, stride=stride, pad=pad,
                              dy=y.gview(), partials=Scratch('wgrad', np_ * Cout * Cin * K * K * 4), nparts=np_,
@@ -1254,14 +1280,7 @@ class Graph:
         out = self.new_act(B, OH, OW, Cout, name)
         if self.train:
             y = self.new_act(B, OH, OW, Cout, name + '.y')
-            nparts = self._conv_parts(z.view(), taps, 1, y.view(), OH, OW)
-            if self._fin_on():
-                prod = self._conv_launch(self.fwd, z.view(), wp.data_ptr(), taps, 1, 0, y.view(), OH, OW)
-                w = self._bn_train_fwd(y, bn, relu, None, out, nparts, None, None, producer=prod)
-            else:
-                stats, cnt = Scratch('stats' + self._scratch_sfx, 4 * lib.salt_bn_stats_floats(nparts, Cout)), Scratch('stats_cnt' + self._scratch_sfx, nparts * 4)
-                self._conv_launch(self.fwd, z.view(), wp.data_ptr(), taps, 1, 0, y.view(), OH, OW, stats=stats, stats_cnt=cnt)
-                w = self._bn_train_fwd(y, bn, relu, None, out, nparts, stats, cnt)
+            w, _ = self._conv_bn_train(z, y, [(wp.data_ptr(), taps, 1, 0, OH, OW, {})], bn, relu, None, out, self._scratch_sfx)
 
             def backward():
                 self._bn_train_bwd(y, bn, relu, None, out, w)
@@ -1271,15 +1290,12 @@ class Graph:
                 per = 8 if len(taps) > 9 else 9
                 for i in range(0, len(taps), per):
                     chunk = list(range(i, min(i + per, len(taps))))
-                    S = STRUCTS['salt_conv_wgrad_args']()
-                    fill(S, dtype=self.dt, p=y.gview(), q=z.view(), ntaps=len(chunk), tap_dy=[taps[j][0] for j in chunk],
-                         tap_dx=[taps[j][1] for j in chunk], q_step=1, pad_mode=0)
-                    ns = lib.salt_conv_wgrad_nsplit(ctypes.byref(S))
+                    wg = dict(dtype=self.dt, ntaps=len(chunk), tap_dy=[taps[j][0] for j in chunk], tap_dx=[taps[j][1] for j in chunk], q_step=1, pad_mode=0)
+                    ns = lib.salt_conv_wgrad_nsplit(ctypes.byref(fill(STRUCTS['salt_conv_wgrad_args'](), p=y.gview(), q=z.view(), **wg)))
                     nbytes = ns * len(chunk) * Cout * 16 * 4
                     # the stem is the last layer of backward: its weight gradient runs on the MAIN stream (own workspace), which is
                     # idle by then, instead of queueing behind the side stream's remaining weight gradients
-                    self.bwd.add('conv_wgrad', stream=0, dtype=self.dt, p=y.gview(), q=z.view(), ntaps=len(chunk), tap_dy=[taps[j][0] for j in chunk],
-                                 tap_dx=[taps[j][1] for j in chunk], q_step=1, pad_mode=0, partials=Scratch('wgrad@main', nbytes), nsplit=ns)
+                    self.bwd.add('conv_wgrad', stream=0, p=y.gview(), q=z.view(), partials=Scratch('wgrad@main', nbytes), nsplit=ns, **wg)
                     self.bwd.add('wgrad_reduce', stream=0, partials=Scratch('wgrad@main', nbytes), nsplit=ns, ntaps=len(chunk), Ca=Cout, Cb=16, KH=TT, KW=TT,
                                  tap_kh=[j // TT for j in chunk], tap_kw=[j % TT for j in chunk], grad=gw_tmp, accumulate=0)
                 self.bwd.add('stem_grad_unfold', stream=0, g16=gw_tmp, Cout=Cout, Cin=Cin, K=K, grad=self._gp(conv.weight), accumulate=0)
@@ -1301,9 +1317,7 @@ class Graph:
             sa, Fbn = taken
             hb = self.fwd.add('head_bn', dtype=self.dt, y=sa.y, fin=ctypes.addressof(Fbn), relu=int(sa.relu), w=conv.weight.data_ptr(),
                               bias=conv.bias.data_ptr() if conv.bias is not None else None, Cout=Cout, y_nchw=logits_nchw.data_ptr())
-            for i, q in enumerate(self._fin_patches):    # the statistics shards the dropped affine_act would have finalized
-                if q[0] is sa and q[1] == 'fin_acc':
-                    self._fin_patches[i] = (hb, 'fin_acc', q[2], q[3])
+            self._retarget_fin_acc(sa, hb, 'fin_acc')
             self.dlogits = self.alloc(tuple(logits_nchw.shape), torch.float32)
             x.buf.head_fused = conv
             self.tape.append(lambda: None)               # the head's backward is part of the producer layer's closure (Graph._bn_train_bwd)
@@ -1314,9 +1328,7 @@ class Graph:
             self.dlogits = self.alloc(tuple(logits_nchw.shape), torch.float32)
 
             def backward():
-                S = STRUCTS['salt_head1x1_bwd_args']()
-                fill(S, x=x.view())
-                nparts = lib.salt_head1x1_bwd_parts(ctypes.byref(S))
+                nparts = lib.salt_head1x1_bwd_parts(ctypes.byref(fill(STRUCTS['salt_head1x1_bwd_args'](), x=x.view())))
                 acc = x.grad_state()
                 self.bwd.add('head1x1_bwd', dtype=self.dt, x=x.view(), w=conv.weight.data_ptr(), Cout=Cout, dy_nchw=self.dlogits.data_ptr(),
                              dx=x.gview(), accumulate=acc, partials=Scratch('head', nparts * Cout * (x.C + 1) * 4), nparts=nparts,
@@ -1351,7 +1363,7 @@ class Graph:
         self.fwd.add('layout', dtype=self.dt, nchw=x_nchw.data_ptr(), nhwc=a.view(), to_nhwc=1)
         if self.train:
             dx = self.alloc((B, C, H, W), torch.float32)
-            self.input_grads = getattr(self, 'input_grads', []) + [dx]
+            self.input_grads.append(dx)
 
             def backward():
                 if a.grad_ready():
@@ -1370,28 +1382,21 @@ class Graph:
             self.tape.append(backward)
 
     # ------------------------------------------------------------------ pooling / resize
-    def maxpool2(self, x, out=None, name=''):
-        if out is None:
-            out = self.new_act(x.B, x.H // 2, x.W // 2, x.C, name)
-        self.fwd.add('maxpool2', dtype=self.dt, x=x.view(), y=out.view())
+    def _maxpool(self, op, x, out):
+        self.fwd.add(op, dtype=self.dt, x=x.view(), y=out.view())
         if self.train:
             def backward():
                 acc = x.grad_state()
-                self.bwd.add('maxpool2_bwd', dtype=self.dt, x=x.view(), dy=out.gview(), dx=x.gview(), accumulate=acc)
+                self.bwd.add(op + '_bwd', dtype=self.dt, x=x.view(), dy=out.gview(), dx=x.gview(), accumulate=acc)
             self.tape.append(backward)
         return out
 
+    def maxpool2(self, x, out=None, name=''):
+        return self._maxpool('maxpool2', x, self.new_act(x.B, x.H // 2, x.W // 2, x.C, name) if out is None else out)
+
     def maxpool3s2(self, x, out=None, name=''):
         """nn.MaxPool2d(3, 2, 1) - the ResNet stem pool of ResNetEncoders(pool0=True) (architectures/encoders.py:23-27)."""
-        if out is None:
-            out = self.new_act(x.B, (x.H + 1) // 2, (x.W + 1) // 2, x.C, name)
-        self.fwd.add('maxpool3s2', dtype=self.dt, x=x.view(), y=out.view())
-        if self.train:
-            def backward():
-                acc = x.grad_state()
-                self.bwd.add('maxpool3s2_bwd', dtype=self.dt, x=x.view(), dy=out.gview(), dx=x.gview(), accumulate=acc)
-            self.tape.append(backward)
-        return out
+        return self._maxpool('maxpool3s2', x, self.new_act(x.B, (x.H + 1) // 2, (x.W + 1) // 2, x.C, name) if out is None else out)
 
     def avgpool2(self, x, out=None, name=''):
         if out is None:
@@ -1418,32 +1423,27 @@ class Graph:
         return out
 
     def add(self, a, b, out=None, name=''):
+        """out = a + b; ``b`` None: out = a (Graph.copy)"""
         if out is None:
             out = self.new_act(a.B, a.H, a.W, a.C, name)
-        self.fwd.add('add', dtype=self.dt, a=a.view(), b=b.view(), y=out.view(), accumulate=0)
+        self.fwd.add('add', dtype=self.dt, a=a.view(), b=b.view() if b is not None else null_view(), y=out.view(), accumulate=0)
         if self.train:
             def backward():
-                for t in (a, b):
+                for t in (a, b) if b is not None else (a,):
                     acc = t.grad_state()
                     self.bwd.add('add', dtype=self.dt, a=out.gview(), b=null_view(), y=t.gview(), accumulate=acc)
             self.tape.append(backward)
         return out
 
     def copy(self, a, out):
-        self.fwd.add('add', dtype=self.dt, a=a.view(), b=null_view(), y=out.view(), accumulate=0)
-        if self.train:
-            def backward():
-                acc = a.grad_state()
-                self.bwd.add('add', dtype=self.dt, a=out.gview(), b=null_view(), y=a.gview(), accumulate=acc)
-            self.tape.append(backward)
-        return out
+        return self.add(a, None, out)
 
     def _take_act_op(self, x):
         """x = relu?(bn(y)) written by the LAST forward operator (a consumer-side-finalize salt_affine_act without residual, main stream)
         and read by nobody yet: remove that operator from the program and hand back (its argument struct, the layer's
         salt_bn_finalize_args) - the caller's kernels apply the transform to y themselves.  Graph.finalize fails loudly if anybody asks
         for a storage view of the activation afterwards."""
-        rec = getattr(x.buf, 'act_op', None)
+        rec = x.buf.act_op
         if rec is None or not self.fwd.ops or self.fwd.ops[-1][0] != 'affine_act':
             return None
         sa, reads0, c0, C = rec
@@ -1453,8 +1453,12 @@ class Graph:
         self.fwd.ops.pop(); self.fwd.streams.pop()
         self.fwd._entries = None
         x.buf.act_op = None
-        self._virtual_acts = getattr(self, '_virtual_acts', []) + [(x.buf, x.buf.reads)]
+        self._virtual_acts.append((x.buf, x.buf.reads))
         return sa, STRUCTS['salt_bn_finalize_args'].from_address(sa.fin)
+
+    def _retarget_fin_acc(self, sa, st, field):
+        """The statistics shards the taken-over affine_act ``sa`` would have finalized go to ``st.field`` instead."""
+        self._fin_patches = [(st, field, q[2], q[3]) if (q[0] is sa and q[1] == 'fin_acc') else q for q in self._fin_patches]
 
     # ------------------------------------------------------------------ scSE
     def scse(self, x, cse, sse, out=None, name=''):
@@ -1477,17 +1481,13 @@ class Graph:
         else:
             xv_, in_kw, in_bwd = None, {}, {}
         xview = (lambda: xv_) if taken is not None else x.view
-        S = STRUCTS['salt_scse_args']()
-        fill(S, x=xview())
-        nparts = lib.salt_scse_parts(ctypes.byref(S))
+        nparts = lib.salt_scse_parts(ctypes.byref(fill(STRUCTS['salt_scse_args'](), x=xview())))
         gap, hid, gc, gs = self.f32(B * C), self.f32(B * R), self.f32(B * C), self.f32(B * x.H * x.W)
         sf = self.fwd.add('scse', dtype=self.dt, x=xview(), w1=l1.weight.data_ptr(), b1=l1.bias.data_ptr(), w2=l2.weight.data_ptr(),
                           b2=l2.bias.data_ptr(), R=R, ws=cs.weight.data_ptr(), bs=cs.bias.data_ptr(), gap_partials=Scratch('se', B * nparts * (2 * C + 1) * 4),
                           nparts=nparts, gap=gap.data_ptr(), hidden=hid.data_ptr(), gate_c=gc.data_ptr(), gate_s=gs.data_ptr(), y=out.view(), **in_kw)
         if taken is not None:
-            for i, q in enumerate(self._fin_patches):    # the statistics shards the dropped affine_act would have finalized
-                if q[0] is sa and q[1] == 'fin_acc':
-                    self._fin_patches[i] = (sf, 'in_fin_acc', q[2], q[3])
+            self._retarget_fin_acc(sa, sf, 'in_fin_acc')
         if shards:
             self._fin_slot('fwd', B * C, (sf, 'gap_acc'))
         if self.train:
@@ -1507,18 +1507,18 @@ class Graph:
                 sg = self.bwd.add('scse_fc_grads', stream=1, **kw) if defer else None
                 # round 6: with the input transform the kernel holds everything the producer layer's BatchNorm backward sums over - it takes
                 # them too and that layer's bn_bwd loses its reduction pass (saltnet.h salt_scse_bwd_args.bnb_acc; SALT_SE_BNB=0: off)
-                carry = (taken is not None and shards and getattr(x.buf, 'bn_train_out', None) == (x.c0, x.C) and acc == 0
+                carry = (taken is not None and shards and x.buf.bn_train_out == (x.c0, x.C) and acc == 0
                          and x.B * x.H * x.W < (1 << 31) and switches.get('SALT_SE_BNB'))
                 if shards:
                     self._fin_slot('bwd', B * ((6 if carry else 2) * C + 1), (sb, 'acc'), *([(sg, 'acc')] if sg is not None else []))
                 # x = relu(bn(conv)): its only gradient consumer is that layer's bn_bwd, which can add the channel-SE term dgap[b][c]
                 # wherever it reads dL/dx - the broadcast-add pass over dx (read + write of the whole tensor) disappears
-                if (getattr(x.buf, 'bn_train_out', None) == (x.c0, x.C) and acc == 0 and x.B * x.H * x.W < (1 << 31)):
-                    if getattr(x.buf, 'grad_bias', None) is not None:
+                if (x.buf.bn_train_out == (x.c0, x.C) and acc == 0 and x.B * x.H * x.W < (1 << 31)):
+                    if x.buf.grad_bias is not None:
                         raise SaltError('two pending gradient biases on %s' % x.buf.name)
                     self.bwd.set_fields(sb, skip_bcast=1)
-                    x.buf.grad_bias = (x.c0, x.C, dgap) + ((sb, sg) if carry else ())
-                    self._bias_bufs = getattr(self, '_bias_bufs', []) + [x.buf]
+                    x.buf.grad_bias = GradBias(x.c0, x.C, dgap, *((sb, sg) if carry else ()))
+                    self._bias_bufs.append(x.buf)
             self.tape.append(backward)
         return out
 
@@ -1534,19 +1534,16 @@ class Graph:
         B, C = int(d.shape[0]), fc.weight.shape[0]
         s = self.f32(B * C)
         self.fwd.add('depth_gate', d=d.data_ptr(), w=fc.weight.data_ptr(), bias=fc.bias.data_ptr(), B=B, C=C, s=s.data_ptr(), backward=0)
-        gate = dict(s=s, B=B, C=C, ds=None, users=[], covered=np.zeros(C, dtype=bool))
+        gate = DepthGate(s, B, C, self.f32(B * C) if (self.train and not self._gate_shards()) else None, [], np.zeros(C, dtype=bool))
         if self.train:
-            if not self._gate_shards():
-                gate['ds'] = self.f32(B * C)
-
             def backward():
-                if not gate['covered'].all():
-                    raise SaltError('depth_gate: %d of %d gate channels never met a channel_gate' % (int((~gate['covered']).sum()), C))
+                if not gate.covered.all():
+                    raise SaltError('depth_gate: %d of %d gate channels never met a channel_gate' % (int((~gate.covered).sum()), C))
                 sb = self.bwd.add('depth_gate', d=d.data_ptr(), B=B, C=C, s=s.data_ptr(), backward=1,
-                                  ds=gate['ds'].data_ptr() if gate['ds'] is not None else None, gw=self._gp(fc.weight), gb=self._gp(fc.bias),
+                                  ds=gate.ds.data_ptr() if gate.ds is not None else None, gw=self._gp(fc.weight), gb=self._gp(fc.bias),
                                   accumulate=0)
-                if gate['ds'] is None:
-                    self._fin_slot('bwd', B * C, (sb, 'ds_acc'), *[(u, 'ds_acc') for u in gate['users']])
+                if gate.ds is None:
+                    self._fin_slot('bwd', B * C, (sb, 'ds_acc'), *[(u, 'ds_acc') for u in gate.users])
             self.tape.append(backward)
         return gate
 
@@ -1557,14 +1554,14 @@ class Graph:
         inplace = out is not None and out.buf is x.buf and (out.c0, out.C) == (x.c0, x.C)
         if out is None:
             out = self.new_act(x.B, x.H, x.W, x.C, name)
-        if gate['covered'][c0:c0 + x.C].any() or c0 + x.C > gate['C'] or x.B != gate['B']:
-            raise SaltError('channel_gate: channels [%d, %d) of a %d-channel gate' % (c0, c0 + x.C, gate['C']))
-        gate['covered'][c0:c0 + x.C] = True
+        if gate.covered[c0:c0 + x.C].any() or c0 + x.C > gate.C or x.B != gate.B:
+            raise SaltError('channel_gate: channels [%d, %d) of a %d-channel gate' % (c0, c0 + x.C, gate.C))
+        gate.covered[c0:c0 + x.C] = True
         S = fill(STRUCTS['salt_channel_gate_args'](), dtype=self.dt, x=x.view())
         nparts = lib.salt_channel_gate_parts(ctypes.byref(S))
         if nparts < 1:
             raise SaltError('channel_gate: %d channels are not supported' % x.C)
-        self.fwd.add('channel_gate', dtype=self.dt, x=x.view(), y=out.view(), s=gate['s'].data_ptr(), sC=gate['C'], c0=c0, backward=0)
+        self.fwd.add('channel_gate', dtype=self.dt, x=x.view(), y=out.view(), s=gate.s.data_ptr(), sC=gate.C, c0=c0, backward=0)
         out.on_side = self.fwd.default_stream == 1
         if self.train:
             def backward():
@@ -1572,9 +1569,9 @@ class Graph:
                     raise SaltError('channel_gate: dL/d(%s) was never written' % name)
                 acc = 0 if inplace else x.grad_state()
                 kw = dict(dtype=self.dt, x=out.view() if inplace else x.view(), y=out.gview(), dx=out.gview() if inplace else x.gview(),
-                          s=gate['s'].data_ptr(), sC=gate['C'], c0=c0, backward=1, accumulate=acc, inplace=int(inplace), nparts=nparts)
-                if gate['ds'] is not None:
-                    kw.update(ds=gate['ds'].data_ptr(), partials=Scratch('gate', x.B * nparts * x.C * 4))
-                gate['users'].append(self.bwd.add('channel_gate', **kw))
+                          s=gate.s.data_ptr(), sC=gate.C, c0=c0, backward=1, accumulate=acc, inplace=int(inplace), nparts=nparts)
+                if gate.ds is not None:
+                    kw.update(ds=gate.ds.data_ptr(), partials=Scratch('gate', x.B * nparts * x.C * 4))
+                gate.users.append(self.bwd.add('channel_gate', **kw))
             self.tape.append(backward)
         return out

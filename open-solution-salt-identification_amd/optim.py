@@ -75,7 +75,7 @@ class FusedAdam(torch.optim.Optimizer):
         eng = self._eng
         if eng.dtype != 'bf16':
             return None
-        if getattr(eng, '_pack_batched_n', -1) != len(eng._pack_ops):
+        if eng._pack_batched_n != len(eng._pack_ops):
             eng._build_pack_batch()
             eng._packed_version = eng._packed_bwd_version = -1
         if self._pack_gen == eng._pack_generation:

@@ -54,7 +54,8 @@ class CompiledNet:
         # second network input of a depth-conditioned network: the tiles' depths [B,1], static like x
         self.d = g.d = g.alloc((B, 1), torch.float32) if getattr(engine.module, 'uses_depth', False) else None
         engine.module.emit(g, self.x, self.logits)
-        self.dlogits = getattr(g, 'dlogits', None)
+        self.dlogits = g.dlogits
+        self.target = self.loss = None   # static target / loss scalar of a training instance: written below, read by bind() and the loss programs
         if train:
             self.target = g.alloc(tuple(oshape), torch.float32)
             self.loss = g.alloc((1,), torch.float32)
@@ -90,7 +91,7 @@ class CompiledNet:
         return self._slots[which][1]
 
     def _static(self, which):
-        return {'x': self.x, 'd': self.d, 'target': getattr(self, 'target', None), 'loss': getattr(self, 'loss', None)}[which]
+        return {'x': self.x, 'd': self.d, 'target': self.target, 'loss': self.loss}[which]
 
     def bind(self, **tensors):
         """bind(x=t, d=t1, target=t2, loss=t3): point the programs at these device tensors.  ``key=None`` points that key back at its static
@@ -170,6 +171,11 @@ class Engine:
         self._folded_version = None
         self.world = 1
         self.side_stream = torch.cuda.Stream(device=device)     # weight-gradient kernels overlap the data-gradient chain
+        self._pack_generation = 0       # bumped by _build_pack_batch; step_graph() recaptures an executable of an older generation
+        self._pack_batched_n = -1       # len(_pack_ops) the batched pack programs were built for: packed*() reset it, refresh / step_graph / FusedAdam compare
+        self._adam_packed_version = None   # weight version whose forward packs FusedAdam wrote itself: optim.py writes, refresh reads
+        self._graph_stream = None       # capture / replay stream of the step graphs: step_graph creates it, run_step_graph reads
+        self._pack_fork = None          # (pack program, one-entry side-stream program) cached by _pack_fork_entries
         self.eager_done = set()          # (shape, loss kind) whose first training step already ran eagerly (models.SegmentationModel._fused_step)
 
     # ------------------------------------------------------------------ flat parameter storage
@@ -376,16 +382,16 @@ class Engine:
         self._pack_batched_n = len(self._pack_ops)
         # a captured step graph bakes the device pointers of THESE tables in: every rebuild starts a new generation, and step_graph()
         # recaptures an executable of an older one instead of replaying it against freed tables
-        self._pack_generation = getattr(self, '_pack_generation', 0) + 1
+        self._pack_generation += 1
 
     def refresh(self, train):
         """Bring the packed weight copies (and, in eval mode, the folded BN constants) up to date."""
-        if getattr(self, '_pack_batched_n', -1) != len(self._pack_ops):
+        if self._pack_batched_n != len(self._pack_ops):
             self._build_pack_batch()
             self._packed_version = self._packed_bwd_version = -1
         if self._packed_version != self.wver:
             # the optimizer step that produced this weight version wrote the vector-path forward packs itself (FusedAdam -> salt_adam_pack)
-            (self._pack_batched_rest if getattr(self, '_adam_packed_version', None) == self.wver else self._pack_batched).run()
+            (self._pack_batched_rest if self._adam_packed_version == self.wver else self._pack_batched).run()
             self._packed_version = self.wver
         if train and self._packed_bwd_version != self.wver and len(self._pack_batched_bwd):
             # ordered after the optimizer step on the main stream; the backward program's first data-gradient joins (engine.py)
@@ -412,7 +418,7 @@ class Engine:
         # net / optimizer can never alias a stale executable through a recycled id()
         cache = net.__dict__.setdefault('_step_graphs', {})
         key = (kind, float(loss_scale))
-        if getattr(self, '_pack_batched_n', -1) != len(self._pack_ops):
+        if self._pack_batched_n != len(self._pack_ops):
             self._build_pack_batch()
         hit = cache.get(key)
         if hit is not None and hit[0] is optimizer and hit[2] == self._pack_generation:
@@ -422,7 +428,7 @@ class Engine:
         optimizer._bind()
         optimizer._sync_hyper()
         loss_prog = net.loss_program(kind, loss_scale)
-        st = self._graph_stream = getattr(self, '_graph_stream', None) or torch.cuda.Stream(device=self.device)
+        st = self._graph_stream = self._graph_stream or torch.cuda.Stream(device=self.device)
         torch.cuda.synchronize()
         exec_ = ctypes.c_void_p()
         with torch.cuda.stream(st):
@@ -452,7 +458,7 @@ class Engine:
 
     def _pack_fork_entries(self):
         """The data-gradient pack launch as a one-entry program tagged for the side stream (the executor forks with an event)."""
-        if getattr(self, '_pack_fork', None) is None or self._pack_fork[0] is not self._pack_batched_bwd:
+        if self._pack_fork is None or self._pack_fork[0] is not self._pack_batched_bwd:
             Entry = _abi.STRUCTS['salt_program_entry']
             arr = (Entry * 1)()
             name, fn, s = self._pack_batched_bwd.ops[0]

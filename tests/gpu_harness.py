@@ -41,7 +41,7 @@ class BlockRun:
         self.g.dlogits.copy_(gy)
         self.g.bwd.run(side=self.eng.side_stream)
         torch.cuda.synchronize()
-        gx = [t.cpu() for t in getattr(self.g, 'input_grads', [])]
+        gx = [t.cpu() for t in self.g.input_grads]
         grads = OrderedDict()
         for name, p in self.module.named_parameters():
             if id(p) in self.eng._off:

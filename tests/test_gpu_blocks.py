@@ -418,7 +418,7 @@ def test_backward_program_is_idempotent_without_a_fresh_forward(dtype):
     gy = T(fx['gy']).to('cuda:0')
     tol = 1e-4 if dtype == 'f32' else 2e-2          # (a doubled sum is an O(1) error; the fp64 atomics' arrival order is last bits)
     gx1, g1 = run.backward(gy)
-    st = getattr(run.g, '_shard_state', None)
+    st = run.g._shard_state
     assert st is not None and st['dirty'] and st['rezeroed'] == 0
     gx2, g2 = run.backward(gy)                       # no forward in between
     assert st['rezeroed'] == 1

@@ -324,7 +324,7 @@ def test_bn_apply_in_consumer_loader_forward_is_bit_identical(shape, monkeypatch
         assert _kernel_ids(run.g.fwd) == [1, 1]
         n_aff = sum(1 for name, _, _ in run.g.fwd.ops if name == 'affine_act')
         assert n_aff == (1 if fold else 2), n_aff
-        assert getattr(run.g, 'n_folded', 0) == (1 if fold else 0)
+        assert run.g.n_folded == (1 if fold else 0)
         y = run.forward()
         outs[fold] = (y.clone(), b1.running_mean.clone(), b1.running_var.clone(), b2.running_mean.clone(), b2.running_var.clone())
     for a, b in zip(outs[''], outs['1']):

@@ -455,3 +455,36 @@ def test_dynamic_lds_limit_is_raised_in_one_place():
     users = sorted(os.path.basename(fn) for fn in glob.glob(os.path.join(PKG, 'csrc', '*.*')) if os.path.isfile(fn) and
                    fn.endswith(('.hip', '.h', '.py')) and 'hipFuncSetAttribute' in open(fn).read())
     assert users == ['common.h'], users
+
+
+def test_builder_state_is_declared_not_probed_with_getattr_defaults():
+    """The graph builder's peephole state is declared in the __init__ of its class (engine.py / runtime.py: neutral value + who writes
+    and who reads it) and read as a plain attribute.  A getattr() WITH a default on one of these names means an attribute that only
+    exists once somebody has assigned it came back."""
+    import re
+    declared = {
+        'Buffer': ['act_op', 'bn_train_out', 'grad_bias', 'head_fused', 'lazy'],
+        'Act': ['on_side'],
+        'Graph': ['_virtual_acts', '_bias_bufs', '_lazies', '_n_bnb', '_uses_bwd_packs', 'input_grads', 'dlogits', 'n_folded', '_shard_state'],
+        'Program': ['_graph'],
+        'CompiledNet': ['target', 'loss'],
+        'Engine': ['_pack_generation', '_pack_batched_n', '_adam_packed_version', '_graph_stream', '_pack_fork'],
+    }
+    names = {n for ns in declared.values() for n in ns}
+    for fn in ('engine.py', 'runtime.py'):
+        with open(os.path.join(PKG, fn)) as f:
+            src = f.read()
+        for m in re.finditer(r"getattr\(\s*[^,()]+(?:\([^()]*\))?[^,()]*,\s*['\"](\w+)['\"]\s*,", src):
+            assert m.group(1) not in names, '%s: getattr(..., %r, default) on declared builder state' % (fn, m.group(1))
+    import ast
+    assigned = {}
+    for fn in ('engine.py', 'runtime.py'):
+        with open(os.path.join(PKG, fn)) as f:
+            tree = ast.parse(f.read())
+        for cls in (n for n in tree.body if isinstance(n, ast.ClassDef)):
+            init = [n for n in cls.body if isinstance(n, ast.FunctionDef) and n.name == '__init__']
+            targets = [t for n in ast.walk(init[0]) if isinstance(n, ast.Assign) for t in n.targets] if init else []
+            targets = [e for t in targets for e in (t.elts if isinstance(t, ast.Tuple) else [t])]
+            assigned[cls.name] = {t.attr for t in targets if isinstance(t, ast.Attribute) and isinstance(t.value, ast.Name) and t.value.id == 'self'}
+    for cls, ns in declared.items():
+        assert not set(ns) - assigned[cls], '%s.__init__ does not declare %s' % (cls, sorted(set(ns) - assigned[cls]))

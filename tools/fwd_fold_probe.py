@@ -39,4 +39,4 @@ kid = {}
 for n, _, s in g.fwd.ops:
     if n == 'conv' and s.in_fin:
         k = int(lib.salt_conv_kernel_id(ctypes.byref(s))); kid[k] = kid.get(k, 0) + 1
-print('SALT_FWD_BN_FOLD=%s folded=%d ops=%d affine_act=%d fwd_ms=%s folded_kernel_ids=%s' % (os.environ.get('SALT_FWD_BN_FOLD', '0'), getattr(g, 'n_folded', 0), len(names), names.count('affine_act'), res, kid))
+print('SALT_FWD_BN_FOLD=%s folded=%d ops=%d affine_act=%d fwd_ms=%s folded_kernel_ids=%s' % (os.environ.get('SALT_FWD_BN_FOLD', '0'), g.n_folded, len(names), names.count('affine_act'), res, kid))
