@@ -1147,6 +1147,54 @@ typedef struct {
 } salt_pool_head_bwd_args;
 int salt_pool_head_bwd(const salt_pool_head_bwd_args*, void* stream);
 
+/* ------------------------------------------------------------------ second-level (stacking) network (architectures/misc.py:8-36):
+ * Conv2dBnRelu(M, F, (3,3)) with the replicate-top-2 / replicate-right-2 pad (base.py:26) straight from the fp32 NCHW stack
+ * [B,M,H,W] of first-level probability maps, on the matrix cores, with one of two epilogues:
+ *   conv[b,y,x,f] = bias[f] + sum_{m,kh,kw} w[f][m][kh][kw] x[b,m,max(y+kh-2,0),min(x+kw,W-1)]      (x rounded to `dtype` first)
+ *   train form (y.p != NULL):  y = conv (raw, NHWC, `dtype`); stats / stats_cnt = per-tile (sum, M2 about the tile's own mean,
+ *       count) of the STORED y, tile < salt_stack_conv_stats_parts (salt_bn_finalize's protocol, fixed order: no atomics);
+ *       xs[b,y,x,0..Mpad) = x as NHWC in `dtype`, Mpad = M rounded up to 16, channels >= M zero (Q of the weight gradient)
+ *   eval form (logits_nchw != NULL):  a = relu?(conv * scale + shift) * gate[b][f];  logits[b,k,y,x] = head_b[k] + sum_f head_w[k][f] a
+ *       (fp32 NCHW; nothing else is written)
+ * 1 <= M <= 64, F in {16, 32, 64}, K <= 4, any H, W >= 1; anything else is SALT_E_UNSUPPORTED.  x is never written. */
+typedef struct {
+    int dtype;
+    const float* x;           /* fp32 NCHW [B,M,H,W] */
+    int B;
+    int M;
+    int H;
+    int W;
+    const float* w;           /* fp32 master weight [F][M][3][3] */
+    const float* bias;        /* [F] or NULL */
+    int F;
+    salt_view y;              /* train form: [B,H,W,F], 16-byte aligned, cs a multiple of 4 (f32) / 8 (bf16) */
+    salt_view xs;             /* train form: [B,H,W,Mpad], same alignment rules */
+    float* stats;             /* train form: [nparts][2][F] (sized by salt_bn_stats_floats) */
+    float* stats_cnt;         /* train form: [nparts] */
+    const float* scale;       /* eval form: folded BatchNorm [F], or both NULL */
+    const float* shift;
+    int relu;
+    const float* gate;        /* eval form: [B][gate_cs] per-image channel gate (channels 0 .. F-1 of each row), or NULL */
+    int gate_cs;
+    const float* head_w;      /* eval form: [K][F] fp32 (the head's [K,F,1,1] weight in place) */
+    const float* head_b;      /* [K] or NULL */
+    int K;
+    float* logits_nchw;       /* eval form: out fp32 [B,K,H,W] */
+} salt_stack_conv_args;
+int salt_stack_conv(const salt_stack_conv_args*, void* stream);
+int salt_stack_conv_stats_parts(const salt_stack_conv_args*);   /* < 0: unsupported shape (salt_last_error says why) */
+
+/* grad[f][m][kh][kw] (+)= gpad[f][m][kh][kw], m < M, of a weight gradient reduced over the padded channels ([F][Mpad][3][3]) */
+typedef struct {
+    const float* gpad;
+    int F;
+    int M;
+    int Mpad;
+    float* grad;              /* [F][M][3][3] */
+    int accumulate;
+} salt_stack_grad_unfold_args;
+int salt_stack_grad_unfold(const salt_stack_grad_unfold_args*, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -554,6 +554,65 @@ class EmptinessClassifier(HipNetwork):
         g.pool_head(x, self.classifier[1], logits)
 
 
+class StackingFCN(HipNetwork):
+    """architectures.misc.StackingFCN (misc.py:8-20), the second-level network of main.py's SECOND_LEVEL switch: one replicate-padded
+    3x3 Conv2dBnRelu over the ``input_model_nr`` stacked out-of-fold probability maps and a 1x1 logit head.  The input is the fp32
+    [B, input_model_nr, H, W] tensor the stacking loader emits; eval is ONE launch (Graph.stack_conv).  F.dropout2d(p=dropout_2d) is
+    an identity here as everywhere else in this file (torch 0.3.1 defaults to training=False, and the registry passes 0)."""
+
+    def __init__(self, input_model_nr, num_classes, filter_nr=32, dropout_2d=0.0):
+        super().__init__()
+        from .engine import stack_conv_parts
+        stack_conv_parts(1, input_model_nr, 1, 1, filter_nr)          # SaltError for a shape the kernel does not run
+        if not 1 <= num_classes <= 4:
+            raise SaltError('%s: %d classes (the fused 1x1 head takes 1 .. 4)' % (type(self).__name__, num_classes))
+        self.input_model_nr, self.num_classes, self.dropout_2d = input_model_nr, num_classes, dropout_2d
+        self.conv = nn.Sequential(Conv2dBnRelu(input_model_nr, filter_nr, kernel_size=(3, 3)))
+        self._more_modules(filter_nr)
+        self.final = nn.Sequential(nn.Conv2d(filter_nr, num_classes, kernel_size=1, padding=0))
+
+    def _more_modules(self, filter_nr):
+        """Hook: modules the reference registers between ``conv`` and ``final`` (state_dict order)."""
+
+    def output_shape(self, shape):
+        B, M, H, W = shape
+        if M != self.input_model_nr:
+            raise SaltError('%s was built for %d stacked maps, the batch has %d' % (type(self).__name__, self.input_model_nr, M))
+        return (B, self.num_classes, H, W)
+
+    def dead_parameter_names(self):
+        return []
+
+    def _gate(self, g):
+        return None
+
+    def emit(self, g, x_nchw, logits):
+        self.output_shape(tuple(x_nchw.shape))
+        blk = self.conv[0]
+        gate = self._gate(g)
+        if not g.train:
+            g.stack_conv(x_nchw, blk.conv, blk.batch_norm, relu=blk.use_relu, head=self.final[0], gate=gate, logits=logits)
+            return
+        a = g.stack_conv(x_nchw, blk.conv, blk.batch_norm, relu=blk.use_relu)
+        if gate is not None:
+            a = g.channel_gate(a, gate, 0, name='depth_gate')
+        g.head(a, self.final[0], logits)
+
+
+class StackingFCNWithDepth(StackingFCN):
+    """architectures.misc.StackingFCNWithDepth (misc.py:23-36): the same with DepthChannelExcitation between the block and the head."""
+
+    uses_depth = True
+
+    def _more_modules(self, filter_nr):
+        self.depth_channel_excitation = DepthChannelExcitation(filter_nr)
+
+    def _gate(self, g):
+        if getattr(g, 'd', None) is None:
+            raise SaltError('StackingFCNWithDepth needs the graph\'s depth input (CompiledNet allocates it)')
+        return g.depth_gate(g.d, self.depth_channel_excitation.fc[0])
+
+
 class TernausUNetResNet(HipNetwork):
     """unet_models.UNetResNet — TernausNet-style decoder (DecoderBlockV2), exported as unet_models.UNetResNet."""
 

@@ -374,6 +374,16 @@ def conv_taps(KH, KW, pad_y, pad_x):
     return [(kh, kw, kh - pad_y, kw - pad_x) for kh in range(KH) for kw in range(KW)]
 
 
+def stack_conv_parts(B, M, H, W, F):
+    """BatchNorm partials a salt_stack_conv launch over a [B,M,H,W] stack with F filters writes; SaltError for a shape the kernel does
+    not run (host-side rules of csrc/stacking.hip: 1 <= M <= 64, F in {16, 32, 64}) - nothing touches the GPU."""
+    S = fill(STRUCTS['salt_stack_conv_args'](), B=B, M=M, H=H, W=W, F=F)
+    n = lib.salt_stack_conv_stats_parts(ctypes.byref(S))
+    if n < 1:
+        raise SaltError(lib.salt_last_error().decode(errors='replace'))
+    return n
+
+
 class Graph:
     """Forward + backward programs of one network instance for fixed (B, H, W), dtype and BN mode."""
 
@@ -1304,6 +1314,64 @@ class Graph:
             w = eng.bn_work(bn)
             self._conv_launch(self.fwd, z.view(), wp.data_ptr(), taps, 1, 0, out.view(), OH, OW,
                               scale=w['scale'].data_ptr(), shift=w['shift'].data_ptr(), relu=int(relu))
+        return out
+
+    # ------------------------------------------------------------------ second-level network (fp32 NCHW stack of probability maps)
+    def stack_conv(self, x_nchw, conv, bn, relu=True, head=None, gate=None, logits=None, name='stack'):
+        """Conv2dBnRelu(M, F, (3,3)) of the reference's StackingFCN (architectures/misc.py:13,28; base.py:21-37) straight from the fp32
+        NCHW batch ``x_nchw`` [B,M,H,W] (salt_stack_conv, csrc/stacking.hip).
+        eval: ONE launch that also applies the channel ``gate`` (a Graph.depth_gate record, or None) and the 1x1 ``head`` and writes the
+        fp32 NCHW ``logits``; returns None.
+        train: the raw output y, its per-tile BatchNorm partials and the NHWC copy xs of the input; returns relu(bn(y)) for
+        Graph.channel_gate / Graph.head.  Backward: BatchNorm backward, then the weight gradient with P = dL/dy, Q = xs through the
+        dense kernels (the padded input channels are dropped by salt_stack_grad_unfold); the input gets no gradient."""
+        eng = self.engine
+        B, M, H, W = x_nchw.shape
+        F = conv.weight.shape[0]
+        if tuple(conv.weight.shape) != (F, M, 3, 3) or bn is None:
+            raise SaltError('stack_conv: weight %s does not fit the %d-map stack (a 3x3 Conv2dBnRelu is expected)' % (tuple(conv.weight.shape), M))
+        nparts = stack_conv_parts(B, M, H, W, F)
+        bias = conv.bias.data_ptr() if conv.bias is not None else None
+        common = dict(dtype=self.dt, x=x_nchw.data_ptr(), B=B, M=M, H=H, W=W, w=conv.weight.data_ptr(), bias=bias, F=F)
+        if not self.train:
+            if head is None or logits is None:
+                raise SaltError('stack_conv: the eval form is the whole network - it needs the head and the logits buffer')
+            K = head.weight.shape[0]
+            if tuple(head.weight.shape) != (K, F, 1, 1) or tuple(logits.shape) != (B, K, H, W) or not 1 <= K <= 4:
+                raise SaltError('stack_conv: head %s / logits %s do not fit (1x1, F = %d, at most 4 classes)' % (tuple(head.weight.shape), tuple(logits.shape), F))
+            if gate is not None and (gate.C != F or gate.B != B):
+                raise SaltError('stack_conv: a [%d, %d] gate on %d images x %d filters' % (gate.B, gate.C, B, F))
+            w = eng.bn_work(bn)
+            self.fwd.add('stack_conv', scale=w['scale'].data_ptr(), shift=w['shift'].data_ptr(), relu=int(relu),
+                         gate=gate.s.data_ptr() if gate is not None else None, gate_cs=gate.C if gate is not None else 0,
+                         head_w=head.weight.data_ptr(), head_b=head.bias.data_ptr() if head.bias is not None else None, K=K,
+                         logits_nchw=logits.data_ptr(), **common)
+            return None
+        Mpad = _round_up(M, 16)
+        y = self.new_act(B, H, W, F, name + '.y')
+        xs = self.new_act(B, H, W, Mpad, name + '.xs')
+        out = self.new_act(B, H, W, F, name)
+        # (the kernel knows the per-tile partials protocol only, like conv_first)
+        w, _ = self._bn_behind(lambda **st: self.fwd.add('stack_conv', y=y.view(), xs=xs.view(), **st, **common), False, nparts, y, bn, relu, None, out,
+                               self._scratch_sfx)
+        td = [(kh - 2, kw) for kh in range(3) for kw in range(3)]
+
+        def backward():
+            self._bn_train_bwd(y, bn, relu, None, out, w)
+            gw = self._gp(conv.weight)
+            gtmp = gw if Mpad == M else self.f32(F * Mpad * 9).data_ptr()
+            wg = dict(dtype=self.dt, p=y.gview(), q=xs.view(), ntaps=9, tap_dy=[t[0] for t in td], tap_dx=[t[1] for t in td], q_step=1, pad_mode=1)
+            ns = lib.salt_conv_wgrad_nsplit(ctypes.byref(fill(STRUCTS['salt_conv_wgrad_args'](), **wg)))
+            if ns < 1:
+                raise SaltError('stack_conv: weight-gradient plan failed: ' + lib.salt_last_error().decode())
+            nbytes = ns * 9 * F * Mpad * 4
+            # the last layer of backward: on the main stream with its own workspace, like the stem's (Graph._stem_s2d)
+            self.bwd.add('conv_wgrad', stream=0, partials=Scratch('wgrad@main', nbytes), nsplit=ns, **wg)
+            self.bwd.add('wgrad_reduce', stream=0, partials=Scratch('wgrad@main', nbytes), nsplit=ns, ntaps=9, Ca=F, Cb=Mpad, KH=3, KW=3,
+                         tap_kh=[t // 3 for t in range(9)], tap_kw=[t % 3 for t in range(9)], grad=gtmp, accumulate=0)
+            if Mpad != M:
+                self.bwd.add('stack_grad_unfold', stream=0, gpad=gtmp, F=F, M=M, Mpad=Mpad, grad=gw, accumulate=0)
+        self.tape.append(backward)
         return out
 
     # ------------------------------------------------------------------ logit head: 1x1 conv to <= 4 channels, fp32 NCHW out

@@ -43,6 +43,14 @@ ARCHITECTURES = {
     'EmptinessClassifier': {'model': A.EmptinessClassifier,
                             'model_config': {'encoder_depth': 18, 'pretrained': False},
                             'init_weights': False},
+    # models.py:51-58: the second-level networks of main.py's SECOND_LEVEL switch (loader_mode 'stacking').  'init_weights' is recorded as
+    # the reference has it and has no effect: its set_model replaces the initialiser with a no-op too (models.py:184)
+    'StackingFCN': {'model': A.StackingFCN,
+                    'model_config': {'input_model_nr': 32, 'filter_nr': 32, 'dropout_2d': 0.0},
+                    'init_weights': True},
+    'StackingFCNWithDepth': {'model': A.StackingFCNWithDepth,
+                             'model_config': {'input_model_nr': 32, 'filter_nr': 32, 'dropout_2d': 0.0},
+                             'init_weights': True},
     'VanillaUNet': {'model': A.VanillaUNet, 'model_config': {'in_channels': 1, 'base_filters': 16, 'levels': 4}, 'init_weights': False},
 }
 
@@ -105,6 +113,8 @@ class Model:
 
 
 class SegmentationModel(Model):
+    takes_depth = False          # batches are (X, *targets); SegmentationModelWithDepth: (X, D, *targets)
+
     def __init__(self, architecture_config, training_config, callbacks_config):
         super().__init__(architecture_config, training_config, callbacks_config)
         self.activation_func = self.architecture_config['model_params']['activation']
@@ -124,7 +134,13 @@ class SegmentationModel(Model):
     def set_model(self):
         mp = self.architecture_config['model_params']
         config = ARCHITECTURES[mp['architecture']]
-        self.model = config['model'](num_classes=mp['out_channels'], **config['model_config'])
+        model_config = dict(config['model_config'])
+        # the second-level networks: how many first-level maps are stacked is the user's data, not the registry's (the reference makes
+        # its users edit the registry entry)
+        model_config.update({k: mp[k] for k in ('input_model_nr', 'filter_nr') if k in mp and k in model_config})
+        self.model = config['model'](num_classes=mp['out_channels'], **model_config)
+        if getattr(self.model, 'uses_depth', False) and not self.takes_depth:
+            raise SaltError('%s is depth-conditioned: train it with SegmentationModelWithDepth on (X, D, target) batches' % mp['architecture'])
         if 'compute_dtype' in mp:
             self.model.set_compute_dtype(mp['compute_dtype'])
         if 'align_corners' in mp:            # True: bilinear up-sampling as torch 0.3.1 (the reference's pinned version) evaluated it
@@ -279,10 +295,12 @@ class SegmentationModelWithDepth(SegmentationModel):
     loss through the autograd bridge; everything else (load, persist, data-parallel buckets, FusedAdam) is SegmentationModel's - the two
     gate parameters are ordinary live parameters of the flat buffers."""
 
+    takes_depth = True
+
     def set_model(self):
         super().set_model()
         if not getattr(self.model, 'uses_depth', False):
-            raise SaltError('SegmentationModelWithDepth needs a depth-conditioned architecture (UNetResNetWithDepth), got %s'
+            raise SaltError('SegmentationModelWithDepth needs a depth-conditioned architecture (UNetResNetWithDepth, StackingFCNWithDepth), got %s'
                             % self.architecture_config['model_params']['architecture'])
 
     def _depth(self, D, X):
