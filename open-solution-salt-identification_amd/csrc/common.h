@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include <atomic>
 #include "saltnet.h"
 
@@ -55,6 +56,19 @@ template <> __device__ __forceinline__ u32x4 pack16<bf16_t>(const float* f) {
     u32x4 v;
     v.x = f2bf_pk(f[0], f[1]); v.y = f2bf_pk(f[2], f[3]); v.z = f2bf_pk(f[4], f[5]); v.w = f2bf_pk(f[6], f[7]);
     return v;
+}
+
+// 16-byte piece load from global with channel-tail / alignment handling (conv_mfma.hip, conv_wgrad.hip).
+template <typename T>
+__device__ __forceinline__ u32x4 load_piece(const T* base, int64_t off, int ch0, int C, bool vec_ok) {
+    constexpr int VE = Elem<T>::VE;
+    if (vec_ok && ch0 + VE <= C) return *reinterpret_cast<const u32x4*>(base + off);
+    float f[VE];
+#pragma unroll
+    for (int j = 0; j < VE; ++j) f[j] = (ch0 + j < C) ? Elem<T>::ld(base + off + j) : 0.f;
+    if (sizeof(T) == 4) return pack16<T>(f);
+    // bf16: repack exactly (values came from bf16, conversion is lossless)
+    return pack16<T>(f);
 }
 
 // bilinear xR source coordinates of destination index d along an axis of n source elements (ac = 0: align_corners=False, 1: True;
@@ -117,11 +131,30 @@ int conv_stem16_launch(const salt_conv_args* a, hipStream_t st);
 // conv_thin.hip: the persistent weight-stationary kernel of the fp32 3x3 layers with 16 / 32 channels on both sides (0 = not applicable)
 int conv_thin_variant(const salt_conv_args* a);
 int conv_thin_launch(const salt_conv_args* a, hipStream_t st);
-// conv_thin.hip: weight gradient of the same layers; 0 = not one of its shapes, else the number of slabs
+// conv_thin.hip: weight gradient of the same layers (salt_conv_wgrad in conv_wgrad.hip tries it first); 0 = not one of its shapes, else the number of slabs
 int conv_wgrad_thin(const salt_conv_wgrad_args* a, bool launch, hipStream_t st, int* rc);
 
 // conv_wgrad_ls.hip: loader-specialised row-streaming weight gradient (bf16, 3x3, unit step); 0 = not one of its shapes, else nsplit
 int conv_wgrad_ls(const salt_conv_wgrad_args* a, bool launch, hipStream_t st, int* rc);
+
+// Split budget of the split-K weight-gradient launches: wgrad_plan (conv_wgrad.hip) and conv_wgrad_ls (conv_wgrad_ls.hip) bound the
+// workgroups of a launch and give every split at least min_tiles 128-pixel tiles (every split costs a partial slab, written by the
+// launch and read again by the reduce: 147 KB for a 64 x 64 3x3 layer).  SALT_WGRAD_TPW=N (> 0) overrides min_tiles.
+//   bf16: >= 8 tiles per split.  128 workgroups per launch (round 6; 512 before): backward is bound by the kernel time of its two
+//     queues together: a weight-gradient launch that holds every CU slows the data-gradient chain beside it by more than its
+//     own shorter run is worth, and every split less is a slab less to write and reduce.  Same box, C2 step: 512 5.05 - 5.08 ms,
+//     256 5.00, 160 5.00, 128 4.97 - 4.99, 96 5.03, 64 5.13, 32 5.97 (profiles/r06_wgrad_wgs_ab.txt)
+//   fp32: 2 tiles - the exact-f32 MFMA is 16x slower, so a workgroup's 1024 pixels were ~200 us of matrix work on 32 workgroups
+//     (vanilla U-Net fp32: 7.47 -> 6.13 ms per step) - and about 256 workgroups per launch (round 3): what SALT_WGRAD_TPW=4 gave the
+//     ResNet34 layers (23.5 ms per step against 24.4 with 2) and SALT_WGRAD_TPW=2 the small levels of the vanilla net (4.17 against
+//     4.27 ms): the 8x8 / 16x16 levels run on the generic kernel, whose time is the length of a workgroup's tile chain, while more
+//     than ~256 workgroups take CUs from the data-gradient chain.  (512 with SALT_WGRAD_TPW set: the A/B that found this.)
+struct WgradBudget { int target_wgs, min_tiles; };
+inline WgradBudget wgrad_split_budget(int dtype) {
+    static const int env = getenv("SALT_WGRAD_TPW") ? atoi(getenv("SALT_WGRAD_TPW")) : 0;
+    const bool f32 = dtype == SALT_F32;
+    return WgradBudget{f32 ? (env > 0 ? 512 : 256) : 128, env > 0 ? env : (f32 ? 2 : 8)};
+}
 
 // Launch `kern<<<grid, block, lds, st>>>(args...)` and run the launch check.  A launch that needs more than the default 64 KB of dynamic
 // LDS raises the kernel's limit to the CU's 160 KB first, once per kernel address: the addresses already raised fill a table from

@@ -477,7 +477,7 @@ int conv_thin_launch(const salt_conv_args* a, hipStream_t st) {
     SALT_FAIL(SALT_E_UNSUPPORTED, "conv_thin: variant %d", v);
 }
 
-// ---- weight gradient of the same layers (conv_mfma.hip: salt_conv_wgrad_nsplit / salt_conv_wgrad).  Returns 0 (not one of its shapes)
+// ---- weight gradient of the same layers (conv_wgrad.hip: salt_conv_wgrad_nsplit / salt_conv_wgrad).  Returns 0 (not one of its shapes)
 // or the number of slabs it writes; launch: also enqueues it (*rc = status).
 namespace {
 template <int AB, int BB, int QS>

@@ -3,7 +3,7 @@
 //   dW[t][a][b] = sum_p P[p, a] * Q[pad(p + tap_t), b]      (P = dL/dy, Q = x; loss.backward() of common_blocks/models.py:133 over
 //                                                            architectures/base.py:7-37, unet_models.py:21-30, torchvision BasicBlock)
 //
-// Why a third weight-gradient structure.  conv_wgrad_fast8_kernel (conv_mfma.hip) stages every 128-pixel tile global -> registers ->
+// Why a third weight-gradient structure.  conv_wgrad_fast8_kernel (conv_wgrad.hip) stages every 128-pixel tile global -> registers ->
 // LDS inside the waves that feed the matrix pipe: its k-loop takes 15.5 us with and 9.3 us without the global loads - the
 // ~115 issue cycles of every global_load_dwordx4 ADD to the MFMA time, exactly what conv_ls_kernel's clocks showed for the forward
 // convolutions.  Same cure here:
@@ -531,7 +531,7 @@ extern "C" int salt_debug_wl_clk(unsigned long long* host_out, int n) {
 }
 #endif
 
-// salt_conv_wgrad / salt_conv_wgrad_nsplit try this first (conv_mfma.hip).  Returns 0 when the launch is not one of this kernel's
+// salt_conv_wgrad / salt_conv_wgrad_nsplit try this first (conv_wgrad.hip).  Returns 0 when the launch is not one of this kernel's
 // shapes, else nsplit (>= 1); with `launch` it also enqueues the kernel (a->partials, a->nsplit as returned here) and puts the
 // launch status into *rc.
 int conv_wgrad_ls(const salt_conv_wgrad_args* a, bool launch, hipStream_t st, int* rc) {
@@ -562,11 +562,10 @@ int conv_wgrad_ls(const salt_conv_wgrad_args* a, bool launch, hipStream_t st, in
     k.ncol = cdiv(k.PW, TW); k.U = cdiv(k.PH, KU);
     k.total = cdiv(k.B, NB) * k.ncol * k.U;
     k.a_blocks = cdiv(k.Ca, 64); k.b_blocks = cdiv(k.Cb, 64);
-    // split rule of wgrad_plan: a workgroup budget per launch and a minimum of pixels per split (every split costs a slab round trip)
-    // round 6: 128 workgroups per launch instead of 512 (wgrad_plan in conv_mfma.hip has the measurements: backward is bound by the
-    // kernel time of both queues together, a weight-gradient launch on every CU slows the data-gradient chain beside it)
-    constexpr int target_wgs = 128;
-    static const int tpw = getenv("SALT_WGRAD_TPW") ? atoi(getenv("SALT_WGRAD_TPW")) : 8;          // in 128-pixel tiles, as before
+    // split rule of wgrad_plan: a workgroup budget per launch and a minimum of pixels per split (wgrad_split_budget in common.h has the
+    // measurements), here in units of KU tile rows
+    const WgradBudget bud = wgrad_split_budget(SALT_BF16);
+    const int target_wgs = bud.target_wgs, tpw = bud.min_tiles;                 // in 128-pixel tiles, as before
     const int blocks = k.a_blocks * k.b_blocks;
     int upw_min = tpw * 8 / KU; if (upw_min < 1) upw_min = 1;
     int ns = target_wgs / blocks;

@@ -1,52 +1,17 @@
-"""conv_wgrad_ls_kernel (loader-specialised, row-streaming bf16 weight gradient) through the C-ABI:
-salt_conv_wgrad + salt_wgrad_reduce against torch's fp32 weight gradient of the same bf16-rounded operands, and against the
-previous kernels (SALT_WGRAD_LS=0 in a child process is not needed: the generic path is reached with a shape the new kernel
-declines).  Replaces autograd of common_blocks/models.py:133 over architectures/base.py:7-37 / unet_models.py:21-30."""
-import ctypes
+"""conv_wgrad_ls_kernel (csrc/conv_wgrad_ls.hip: loader-specialised, row-streaming bf16 weight gradient) through the C-ABI
+(tests/wgrad_abi.py): salt_conv_wgrad + salt_wgrad_reduce against torch's float64 weight gradient of the same bf16-rounded operands,
+and against the kernels it replaced by default (csrc/conv_wgrad.hip, one child process with SALT_WGRAD_LS=0).  Replaces autograd of
+common_blocks/models.py:133 over architectures/base.py:7-37 / unet_models.py:21-30."""
 import os
 
 import pytest
 import torch
 import torch.nn.functional as F
 
+import wgrad_abi
+from wgrad_abi import mk as _mk, wgrad_hip as _wgrad_hip
+
 pytestmark = pytest.mark.gpu
-
-
-def _wgrad_hip(p_nhwc, q_nhwc, taps, pad_mode, nsplit=None, q_planar=False, Ca=None, Cb=None, q_step=1):
-    """p_nhwc [B,H,W,Csa] / q_nhwc [B,QH,QW,Csb] bf16 device tensors (views of Ca / Cb leading channels); returns dW [Ca][Cb][3][3] fp32."""
-    import salt_amd  # noqa: F401
-    from salt_amd._abi import STRUCTS, lib, fill, check
-    from salt_amd.engine import shaped_view
-    B, H, W, csa = p_nhwc.shape
-    _, QH, QW, csb = q_nhwc.shape
-    csa, csb = p_nhwc.stride(2), q_nhwc.stride(2)                 # pixel stride of a channel slice of a wider buffer
-    Ca = csa if Ca is None else Ca
-    Cb = csb if Cb is None else Cb
-    pv = shaped_view(p_nhwc.data_ptr(), B, H, W, Ca, csa)
-    if q_planar:
-        # q_nhwc is [planes][B,QH,QW,64]: the view names one plane's pixel stride, q_plane the plane stride
-        qv = shaped_view(q_nhwc.data_ptr(), B, QH, QW, Cb, 64)
-        qp = B * QH * QW * 64
-    else:
-        qv = shaped_view(q_nhwc.data_ptr(), B, QH, QW, Cb, csb)
-        qp = 0
-    S = fill(STRUCTS['salt_conv_wgrad_args'](), dtype=1, p=pv, q=qv, ntaps=9, tap_dy=[t[0] for t in taps], tap_dx=[t[1] for t in taps],
-             q_step=q_step, pad_mode=pad_mode, q_plane=qp)
-    ns = lib.salt_conv_wgrad_nsplit(ctypes.byref(S))
-    assert ns >= 1, lib.salt_last_error()
-    if nsplit is not None:
-        ns = nsplit
-    part = torch.full((ns, 9, Ca, Cb), float('nan'), device='cuda:0')
-    S.partials = part.data_ptr()
-    S.nsplit = ns
-    st = torch.cuda.current_stream().cuda_stream
-    check(lib.salt_conv_wgrad(ctypes.byref(S), st), 'salt_conv_wgrad')
-    grad = torch.full((Ca, Cb, 3, 3), float('nan'), device='cuda:0')
-    R = fill(STRUCTS['salt_wgrad_reduce_args'](), partials=part.data_ptr(), nsplit=ns, ntaps=9, Ca=Ca, Cb=Cb, KH=3, KW=3,
-             tap_kh=[t // 3 for t in range(9)], tap_kw=[t % 3 for t in range(9)], grad=grad.data_ptr(), accumulate=0)
-    check(lib.salt_wgrad_reduce(ctypes.byref(R), st), 'salt_wgrad_reduce')
-    torch.cuda.synchronize()
-    return grad.cpu(), ns
 
 
 def _ref(p, q, replicate):
@@ -60,11 +25,6 @@ def _ref(p, q, replicate):
         y = F.conv2d(qq, w, padding=1)
     (y * p.double()).sum().backward()
     return w.grad.float()
-
-
-def _mk(B, C, H, W, seed):
-    g = torch.Generator().manual_seed(seed)
-    return torch.randn(B, C, H, W, generator=g).bfloat16().float()
 
 
 CASES = [
@@ -169,26 +129,26 @@ def test_wgrad_ls_stride2_vs_torch(case, nsplit):
     assert err <= 2e-5, 'rel-L2 %.3e (nsplit %d)' % (err, ns)
 
 
-def test_wgrad_ls_is_the_kernel_that_runs_and_matches_previous_kernels():
-    """The plan hands the ResNet34 layer shapes to the new kernel (salt_conv_wgrad_nsplit follows ITS split rule), and the result
-    equals the previous kernels' (child process with SALT_WGRAD_LS=0) to fp32 summation-order noise."""
+def test_wgrad_ls_is_the_kernel_that_runs_and_matches_previous_kernels(tmp_path):
+    """The plan hands aligned bf16 raster 3x3 launches to conv_wgrad_ls_kernel, and its results equal the float64 reference and the
+    previous kernels' (conv_wgrad_fast8_kernel, conv_wgrad_fast_kernel<9, 8> / <9, 4>: ONE child process with SALT_WGRAD_LS=0 - the
+    library reads the switch once - computes wgrad_abi.PREVIOUS_KERNEL_SHAPES) to fp32 summation-order noise."""
     import subprocess
     import sys
-    code = r'''
-import sys, torch
-sys.path.insert(0, %r); sys.path.insert(0, %r)
-import test_gpu_wgrad_ls as t
-p, q = t._mk(2, 64, 32, 32, 7), t._mk(2, 64, 32, 32, 8)
-taps = [(dy - 1, dx - 1) for dy in range(3) for dx in range(3)]
-got, ns = t._wgrad_hip(p.permute(0, 2, 3, 1).contiguous().bfloat16().cuda(), q.permute(0, 2, 3, 1).contiguous().bfloat16().cuda(), taps, 0)
-torch.save(got, sys.argv[1])
-''' % (os.path.dirname(os.path.abspath(__file__)), os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-    import tempfile
-    outs = []
-    for ls in ('1', '0'):
-        with tempfile.NamedTemporaryFile(suffix='.pt') as f:
-            env = dict(os.environ, SALT_WGRAD_LS=ls)
-            subprocess.run([sys.executable, '-c', code, f.name], check=True, env=env, timeout=600)
-            outs.append(torch.load(f.name))
-    d = float((outs[0].double() - outs[1].double()).norm() / outs[1].double().norm())
-    assert d <= 2e-5, d
+    code = 'import sys, torch; sys.path.insert(0, %r); sys.path.insert(0, %r); import wgrad_abi; torch.save(wgrad_abi.run_previous_shapes(wgrad_abi.FAST), sys.argv[1])' % (
+        os.path.dirname(os.path.abspath(__file__)), os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    out = str(tmp_path / 'previous.pt')
+    subprocess.run([sys.executable, '-c', code, out], check=True, env=dict(os.environ, SALT_WGRAD_LS='0'), timeout=600)
+    prev = torch.load(out)
+    assert os.environ.get('SALT_WGRAD_LS', '1') != '0'
+    new = wgrad_abi.run_previous_shapes(wgrad_abi.LS)
+    assert len(prev) == len(new) == len(wgrad_abi.PREVIOUS_KERNEL_SHAPES)
+    for i, shape in enumerate(wgrad_abi.PREVIOUS_KERNEL_SHAPES):
+        p, q, taps = wgrad_abi.previous_shape_operands(shape, i)
+        ref = wgrad_abi.wgrad_ref(p, q, taps, shape[5], shape[6]).permute(1, 2, 0).reshape(p.shape[1], q.shape[1], 3, 3)
+        for name, got in (('previous', prev[i]), ('ls', new[i])):
+            assert torch.isfinite(got).all(), (name, shape)
+            err = wgrad_abi.rel_l2(got, ref)
+            assert err <= 2e-5, '%s vs float64 %s: rel-L2 %.3e' % (name, shape, err)
+        d = wgrad_abi.rel_l2(new[i], prev[i])
+        assert d <= 2e-5, (shape, d)

@@ -1,7 +1,8 @@
 #!/bin/bash
 # Build an A/B variant of the library with extra compiler flags: [SRC=<file stem>] tools/build_variant.sh <name> <flags...>
 #   -> open-solution-salt-identification_amd/csrc/_variants/libsaltnet_hip.<name>.so   (run with SALT_LIB=<that path>)
-# SRC names the one source compiled with the flags (default conv_mfma); the other objects come from csrc/_obj (build.py first).
+# SRC names the one source compiled with the flags (default conv_mfma: forward / data-gradient convolutions; conv_wgrad: the split-K
+# weight-gradient kernels); the other objects come from csrc/_obj (build.py first).
 # The source list is csrc/build.py's SOURCES.
 set -e
 cd "$(dirname "$0")/.."
