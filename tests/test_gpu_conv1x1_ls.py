@@ -26,7 +26,7 @@ CASES_S2 = [
 ]
 
 
-def _conv1x1(case, cfg):
+def _conv1x1(case, cfg, bound=False):
     import salt_amd  # noqa: F401
     from salt_amd._abi import STRUCTS, lib, fill, check
     from salt_amd.engine import shaped_view
@@ -66,16 +66,32 @@ def _conv1x1(case, cfg):
             v = v.clamp_min(0)
     if acc:
         v = v.bfloat16().float() + y0[..., :Cout].float().cpu()
+    if bound:
+        # the float64 reference of the same operands with conv_abi's derived per-element bound (products exact, fp32 accumulation in any
+        # order, one bf16 storage rounding - two with a residual or accumulate)
+        import conv_abi as CA
+        d = lambda t: t.double().cpu()
+        f64 = CA.conv_ref(x[..., :Cin].cpu(), wf.double()[None], [(0, 0)], 1, 0, H, W, 'bf16', d(bias) if aff else None, d(scale) if aff else None,
+                          d(shift) if aff else None, bool(aff), d(r[..., :Cout]) if res else None, d(y0[..., :Cout]) if acc else None)
+        return y.float().cpu(), v, kid, (y0.float().cpu() if slack else None), f64
     return y.float().cpu(), v, kid, (y0.float().cpu() if slack else None)
+
+
+def _assert_bound(got, f64):
+    import conv_abi as CA
+    r = CA.ratio(got, f64)
+    print('kernel 11 bf16 max err / tol = %.3f' % r)
+    assert r <= 1.0, 'max err / tol = %.3f' % r
 
 
 @pytest.mark.parametrize('case', CASES)
 def test_conv1x1_ls_vs_torch_and_conv_mfma(case):
-    y, ref, kid, y0 = _conv1x1(case, 11)
+    y, ref, kid, y0, f64 = _conv1x1(case, 11, bound=True)
     assert kid == 11, kid
     Cout, slack = case[4], case[8]
     got = y[..., :Cout]
     assert torch.isfinite(got).all()
+    _assert_bound(got, f64)
     err = float((got - ref).abs().max() / ref.abs().max())
     assert err <= 1e-2, err                                                 # one bf16 rounding of the stored value
     if slack:
@@ -99,11 +115,12 @@ CASES_ITEM_MAJOR = [
 
 @pytest.mark.parametrize('case,bits', CASES_ITEM_MAJOR)
 def test_conv1x1_ls_item_major_walk_vs_torch_and_conv_mfma(case, bits):
-    y, ref, kid, y0 = _conv1x1(case, 11 | bits)
+    y, ref, kid, y0, f64 = _conv1x1(case, 11 | bits, bound=True)
     assert kid == 11, kid
     Cout, slack = case[4], case[8]
     got = y[..., :Cout]
     assert torch.isfinite(got).all()
+    _assert_bound(got, f64)
     err = float((got - ref).abs().max() / ref.abs().max())
     assert err <= 1e-2, err
     if slack:
@@ -130,11 +147,12 @@ CASES_XS = [
 
 @pytest.mark.parametrize('case', CASES_XS)
 def test_conv1x1_xs_vs_torch_and_conv_mfma(case):
-    y, ref, kid, y0 = _conv1x1(case, 11 | (1 << 19))
+    y, ref, kid, y0, f64 = _conv1x1(case, 11 | (1 << 19), bound=True)
     assert kid == 11, kid
     Cout, slack = case[4], case[8]
     got = y[..., :Cout]
     assert torch.isfinite(got).all()
+    _assert_bound(got, f64)
     err = float((got - ref).abs().max() / ref.abs().max())
     assert err <= 1e-2, err
     if slack:
@@ -188,6 +206,10 @@ def test_conv1x1_ls_stride2_vs_torch(case):
     v = v.view(B, OH, OW, Cout)
     err = float((y.float().cpu() - v).abs().max() / v.abs().max())
     assert err <= 1e-2, err
+    import conv_abi as CA
+    f64 = CA.conv_ref(x[..., :Cin].cpu(), w.bfloat16().double().cpu().view(1, Cout, Cin), [(0, 0)], 2, 0, OH, OW, 'bf16',
+                      scale=scale.double().cpu() if aff else None, shift=shift.double().cpu() if aff else None)
+    _assert_bound(y.float().cpu(), f64)
 
 
 @pytest.mark.parametrize('case', [(4, 64, 32, 32, 128, 2), (2, 128, 32, 32, 256, 2), (4, 64, 16, 16, 96, 1), (8, 256, 32, 32, 512, 2)])
