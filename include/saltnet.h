@@ -1195,6 +1195,85 @@ typedef struct {
 } salt_stack_grad_unfold_args;
 int salt_stack_grad_unfold(const salt_stack_grad_unfold_args*, void* stream);
 
+/* ------------------------------------------------------------------ SE-ResNet bottleneck tail (csrc/se_res.hip): the end of
+ * SEResNetBottleneck.forward of the public pretrainedmodels senet.py (reached through architectures/encoders.py:48-83), restated:
+ *   z[b,h,w,c]  = in_scale[c] x + in_shift[c]                (x: the raw conv3 output; both NULL: z = x, BatchNorm already applied)
+ *   gap[b,c]    = mean_hw z = in_scale[c] mean_hw(x) + in_shift[c]   (the pooling pass reads raw x only)
+ *   hidden[b,r] = relu(b1[r] + sum_c w1[r][c] gap[b,c]),   gate[b,c] = sigmoid(b2[c] + sum_r w2[c][r] hidden[b,r])
+ *   y           = relu(gate[b,c] z + res)
+ * Three launches: pooling (per-workgroup sums -> ONE fp64 atomic per channel into gap_acc, or one partial row per workgroup), the FC
+ * (one workgroup per image, w1 / w2 streamed from global memory), the apply pass.  C a multiple of 64 up to 2048, R = C / 16, any
+ * B, H, W >= 1; x / res / y 16-byte aligned with cs a multiple of 4 (f32) / 8 (bf16), fewer than 2^31 elements per view: anything
+ * else is SALT_E_UNSUPPORTED.
+ * Sums: gap_acc != NULL: [B][C] fp64, zeroed by the caller before the call (the statistics arena); else gap_partials
+ * [B][nparts][C] fp32, added in ascending part order by the FC launch (the same bits on every run). */
+typedef struct {
+    int dtype;
+    salt_view x;              /* [B,H,W,C] raw convolution output (or the stored BatchNorm output when in_scale == NULL) */
+    const float* in_scale;    /* [C] or NULL (with in_shift) */
+    const float* in_shift;
+    /* consumer-side finalize of the train-mode BatchNorm in front (the protocol of salt_scse_args.in_fin): in_fin = the layer's const
+     * salt_bn_finalize_args*, in_fin_acc = the [8][2 C + 1] fp64 shards the convolution launch added x's statistics to.  The FC launch
+     * finalizes them (workgroup 0 stores mean / invstd / scale / shift / running statistics) and in_scale / in_shift are ignored:
+     * the apply pass and salt_se_res_bwd read the stored scale / shift. */
+    const void* in_fin;
+    const double* in_fin_acc;
+    salt_view res;            /* shortcut [B,H,W,C] */
+    const float* w1;          /* [R][C]  (se_module.fc1.weight, a [R,C,1,1] convolution weight in place) */
+    const float* b1;          /* [R] */
+    const float* w2;          /* [C][R]  (se_module.fc2.weight) */
+    const float* b2;          /* [C] */
+    int R;                    /* C / 16 */
+    float* gap_partials;      /* [B][nparts][C] workspace, or NULL with gap_acc */
+    int nparts;               /* as returned by salt_se_res_parts */
+    double* gap_acc;          /* [B][C] zeroed fp64 sums, or NULL */
+    float* gap;               /* out [B][C]  (kept for salt_se_res_bwd / salt_se_res_fc_grads) */
+    float* hidden;            /* out [B][R] */
+    float* gate;              /* out [B][C] */
+    salt_view y;              /* out [B,H,W,C] */
+} salt_se_res_args;
+int salt_se_res(const salt_se_res_args*, void* stream);
+int salt_se_res_parts(const salt_se_res_args*);      /* pixel parts per image (x's shape and dtype are read); < 0: unsupported shape */
+
+/* Backward of the tail.  m = dy [y > 0]:
+ *   dres (+)= m;   dgate[b,c] = sum_hw m z   (z recomputed from x as above; per-workgroup sums -> `acc` [B][C] zeroed fp64, or
+ *   `partials` [B][nparts][C] added in ascending order: two runs are then bit-identical)
+ *   du = dgate gate (1 - gate);  dh[b,r] = [hidden > 0] sum_c du[b,c] w2[c][r];  dgap[b,c] = (1 / HW) sum_r dh[b,r] w1[r][c]
+ *   dx = m gate[b,c] + dgap[b,c]          (dL/dz: the BatchNorm backward of the layer in front runs on it; dx may alias dy)
+ * du, dh and dgap are stored ([B][C], [B][R], [B][C] fp32) and salt_se_res_fc_grads (same struct, any stream ordered behind this
+ * call) OVERWRITES g_w2 = du^T hidden, g_b2 = sum_b du, g_w1 = dh^T gap, g_b1 = sum_b dh, images in ascending order.
+ * defer_param_grads = 0: salt_se_res_bwd runs that launch itself. */
+typedef struct {
+    int dtype;
+    salt_view x;              /* as in the forward call */
+    const float* in_scale;    /* [C] scale / shift the forward call used (in_fin: the layer's stored scale / shift), or both NULL */
+    const float* in_shift;
+    salt_view y;              /* forward output (ReLU mask) */
+    salt_view dy;             /* dL/dy */
+    const float* w1;
+    const float* w2;
+    int R;
+    const float* gap;         /* from the forward call */
+    const float* hidden;
+    const float* gate;
+    float* partials;          /* [B][nparts][C] workspace, or NULL with acc */
+    int nparts;
+    double* acc;              /* [B][C] zeroed fp64 sums, or NULL */
+    float* du;                /* workspace / out [B][C] */
+    float* dh;                /* workspace / out [B][R] */
+    float* dgap;              /* workspace / out [B][C] */
+    salt_view dx;             /* out dL/dz [B,H,W,C] */
+    salt_view dres;           /* dL/dres */
+    int accumulate_dres;      /* dres += */
+    float* g_w1;              /* out [R][C] */
+    float* g_b1;              /* out [R] */
+    float* g_w2;              /* out [C][R] */
+    float* g_b2;              /* out [C] */
+    int defer_param_grads;    /* 1: g_* are left to salt_se_res_fc_grads */
+} salt_se_res_bwd_args;
+int salt_se_res_bwd(const salt_se_res_bwd_args*, void* stream);
+int salt_se_res_fc_grads(const salt_se_res_bwd_args*, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

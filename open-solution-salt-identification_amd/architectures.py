@@ -14,6 +14,9 @@ Reference classes mirrored (paths relative to the reference's common_blocks/):
   :89-104 ChannelSELayer · :107-117 SpatialSELayer
   architectures/encoders.py:6-45 ResNetEncoders;  architectures/unet.py:22-109 UNetResNet
   architectures/misc.py:39-81 EmptinessClassifier
+  architectures/encoders.py:48-83 SeResNetEncoders;  architectures/unet.py:112-172 UNetSeResNet
+  pretrainedmodels senet.py (un-vendored dependency, layout RESTATED from its public source, not executed): SENet / SEResNetBottleneck /
+  SEModule as se_resnet50 / 101 / 152 build them
   torchvision 0.2.0 models/resnet.py (un-vendored dependency): ResNet / BasicBlock / Bottleneck layout
 """
 import math
@@ -279,6 +282,105 @@ class ResNetEncoders(EmitOnly):
         self.encoder5 = self.encoder.layer4
 
 
+# ----------------------------------------------------------------------------- pretrainedmodels-layout SE-ResNet (parameter layout only)
+class SEModule(EmitOnly):
+    """senet.py SEModule: x * sigmoid(fc2(relu(fc1(avg_pool(x))))), fc1 / fc2 1x1 convolutions with bias."""
+
+    def __init__(self, channels, reduction):
+        super().__init__()
+        self.avg_pool = nn.AdaptiveAvgPool2d(1)
+        self.fc1 = nn.Conv2d(channels, channels // reduction, kernel_size=1, padding=0)
+        self.relu = nn.ReLU(inplace=True)
+        self.fc2 = nn.Conv2d(channels // reduction, channels, kernel_size=1, padding=0)
+        self.sigmoid = nn.Sigmoid()
+
+
+class SEResNetBottleneck(EmitOnly):
+    """senet.py SEResNetBottleneck: the Caffe-style bottleneck - the 1x1 conv1 carries the stride - with an SEModule on bn3's output
+    before the shortcut add.  conv3 -> bn3 is emitted without ReLU and Graph.se_res (csrc/se_res.hip) is its only reader."""
+    expansion = 4
+
+    def __init__(self, inplanes, planes, groups, reduction, stride=1, downsample=None):
+        super().__init__()
+        if groups != 1:
+            raise SaltError('SEResNetBottleneck: grouped convolutions (SE-ResNeXt) are not built')
+        self.conv1 = nn.Conv2d(inplanes, planes, kernel_size=1, bias=False, stride=stride)
+        self.bn1 = nn.BatchNorm2d(planes)
+        self.conv2 = nn.Conv2d(planes, planes, kernel_size=3, padding=1, groups=groups, bias=False)
+        self.bn2 = nn.BatchNorm2d(planes)
+        self.conv3 = nn.Conv2d(planes, planes * 4, kernel_size=1, bias=False)
+        self.bn3 = nn.BatchNorm2d(planes * 4)
+        self.relu = nn.ReLU(inplace=True)
+        self.se_module = SEModule(planes * 4, reduction=reduction)
+        self.downsample = downsample
+        self.stride = stride
+
+    def emit(self, g, x, out=None):
+        idt = x
+        if self.downsample is not None:          # the projection shortcut stays on the side stream, joined at the SE tail
+            with g.side():
+                idt = g.conv(x, self.downsample[0], self.downsample[1], relu=False, name='down')
+        n0 = len(g.tape)
+        a = g.conv(x, self.conv1, self.bn1, relu=True, name='sebneck.conv1')
+        a = g.conv(a, self.conv2, self.bn2, relu=True, name='sebneck.conv2')
+        z = g.conv(a, self.conv3, self.bn3, relu=False, name='sebneck.conv3')
+        y = g.se_res(z, self.bn3, self.se_module, idt, out=out, name='sebneck.se')
+        _shortcut_gradient_first(g, n0, self.downsample)
+        return y
+
+
+class SENet(EmitOnly):
+    """senet.py SENet as se_resnet50 / 101 / 152 configure it (groups 1, reduction 16, inplanes 64, input_3x3 False, 1x1 downsample
+    without padding, no dropout): layer0 = Sequential(conv1 7x7 s2 p3, bn1, relu1, pool), layer1 .. layer4, avg_pool, last_linear."""
+    CFG = {50: [3, 4, 6, 3], 101: [3, 4, 23, 3], 152: [3, 8, 36, 3]}
+
+    def __init__(self, depth, num_classes=1000):
+        super().__init__()
+        from collections import OrderedDict
+        counts = self.CFG[depth]
+        self.inplanes = 64
+        self.layer0 = nn.Sequential(OrderedDict([('conv1', nn.Conv2d(3, 64, kernel_size=7, stride=2, padding=3, bias=False)),
+                                                 ('bn1', nn.BatchNorm2d(64)), ('relu1', nn.ReLU(inplace=True)),
+                                                 ('pool', nn.MaxPool2d(3, stride=2, ceil_mode=True))]))
+        self.layer1 = self._make(64, counts[0], 1)
+        self.layer2 = self._make(128, counts[1], 2)
+        self.layer3 = self._make(256, counts[2], 2)
+        self.layer4 = self._make(512, counts[3], 2)
+        self.avg_pool = nn.AvgPool2d(7, stride=1)
+        self.dropout = None
+        self.last_linear = nn.Linear(512 * SEResNetBottleneck.expansion, num_classes)      # present in the state_dict, never used
+
+    def _make(self, planes, n, stride):
+        exp = SEResNetBottleneck.expansion
+        down = None
+        if stride != 1 or self.inplanes != planes * exp:
+            down = nn.Sequential(nn.Conv2d(self.inplanes, planes * exp, kernel_size=1, stride=stride, padding=0, bias=False),
+                                 nn.BatchNorm2d(planes * exp))
+        layers = [SEResNetBottleneck(self.inplanes, planes, 1, 16, stride, down)]
+        self.inplanes = planes * exp
+        layers += [SEResNetBottleneck(self.inplanes, planes, 1, 16) for _ in range(1, n)]
+        return nn.Sequential(*layers)
+
+
+class SeResNetEncoders(EmitOnly):
+    def __init__(self, encoder_depth, pretrained=False, pool0=False):
+        super().__init__()
+        if encoder_depth not in SENet.CFG:
+            raise NotImplementedError('only 50, 101, 152 version of Resnet are implemented')
+        if pretrained:
+            raise SaltError('pretrained ImageNet weights need a download; load a state_dict instead')
+        if pool0:
+            # encoders.py:61-65 reads layer0.pool0 for it; the ceil_mode pool changes every map size downstream - out of scope
+            raise SaltError('SeResNetEncoders: pool0=True is not built')
+        self.pool0 = False
+        self.encoder = SENet(encoder_depth)
+        self.conv1 = nn.Sequential(self.encoder.layer0.conv1, self.encoder.layer0.bn1, self.encoder.layer0.relu1)
+        self.encoder2 = self.encoder.layer1
+        self.encoder3 = self.encoder.layer2
+        self.encoder4 = self.encoder.layer3
+        self.encoder5 = self.encoder.layer4
+
+
 # ----------------------------------------------------------------------------- whole networks
 class HipNetwork(nn.Module):
     """Base of the callable networks: owns the Engine, dispatches forward to the compiled HIP program."""
@@ -377,8 +479,7 @@ class UNetResNet(HipNetwork):
         # F.dropout2d(encoder5, p=self.dropout_2d) (unet.py:91): the reference environment pins torch==0.3.1 (environment.yml:17), whose
         # F.dropout2d defaults to training=False - the call is an identity for every p there, and the registry passes p = 0 anyway
         self.num_classes, self.dropout_2d, self.use_hypercolumn = num_classes, dropout_2d, use_hypercolumn
-        self.encoders = ResNetEncoders(encoder_depth, pretrained=pretrained, pool0=pool0)
-        b = 512 if encoder_depth in (18, 34) else 2048
+        self.encoders, b = self._make_encoders(encoder_depth, pretrained, pool0)
         self.center = nn.Sequential(Conv2dBnRelu(b, b), Conv2dBnRelu(b, b // 2), nn.AvgPool2d(kernel_size=2, stride=2))
         self.dec5 = DecoderBlock(b + b // 2, b, b // 8)
         self.dec4 = DecoderBlock(b // 2 + b // 8, b // 2, b // 8)
@@ -388,6 +489,14 @@ class UNetResNet(HipNetwork):
         self.final = nn.Sequential(Conv2dBnRelu((5 if use_hypercolumn else 1) * b // 8, b // 8),
                                    nn.Conv2d(b // 8, num_classes, kernel_size=1, padding=0))
         self.bottom = b
+
+    def _make_encoders(self, encoder_depth, pretrained, pool0):
+        """Hook: -> (the encoders module, bottom_channel_nr).  UNetSeResNet builds SeResNetEncoders here."""
+        return ResNetEncoders(encoder_depth, pretrained=pretrained, pool0=pool0), 512 if encoder_depth in (18, 34) else 2048
+
+    def _stem(self):
+        """Hook: the stem's (convolution, BatchNorm) inside ``self.encoders.encoder``."""
+        return self.encoders.encoder.conv1, self.encoders.encoder.bn1
 
     def dead_parameter_names(self):
         return ['encoders.encoder.fc.weight', 'encoders.encoder.fc.bias']
@@ -407,7 +516,7 @@ class UNetResNet(HipNetwork):
         B, _, H, W = x_nchw.shape
         b, d = self.bottom, self.bottom // 8
         exp = 1 if b == 512 else 4
-        c1 = g.conv_first(x_nchw, enc.conv1, enc.bn1, relu=True, name='stem')
+        c1 = g.conv_first(x_nchw, *self._stem(), relu=True, name='stem')
         if self.encoders.pool0:
             c1 = g.maxpool3s2(c1, name='stem.pool')
             H, W = H // 2, W // 2                    # everything downstream runs at half the resolution
@@ -477,6 +586,20 @@ class UNetResNet(HipNetwork):
             d1 = self._hyper_in(g, self.dec1.emit(g, d2, None), 0, last=True)
             f = self.final[0].emit(g, d1)
         g.head(f, self.final[1], logits)
+
+
+class UNetSeResNet(UNetResNet):
+    """architectures.unet.UNetSeResNet (unet.py:112-172): UNetResNet's decoder, hypercolumn and head (the two classes differ in the
+    ``encoders`` line and nothing else) on SE-ResNet50 / 101 / 152 encoders with 2048 bottom channels."""
+
+    def _make_encoders(self, encoder_depth, pretrained, pool0):
+        return SeResNetEncoders(encoder_depth, pretrained=pretrained, pool0=pool0), 2048
+
+    def _stem(self):
+        return self.encoders.encoder.layer0.conv1, self.encoders.encoder.layer0.bn1
+
+    def dead_parameter_names(self):
+        return ['encoders.encoder.last_linear.weight', 'encoders.encoder.last_linear.bias']
 
 
 class DepthChannelExcitation(EmitOnly):

@@ -1590,6 +1590,72 @@ class Graph:
             self.tape.append(backward)
         return out
 
+    # ------------------------------------------------------------------ SE-ResNet bottleneck tail (csrc/se_res.hip)
+    @staticmethod
+    def se_res_ok(C, R):
+        """The shapes salt_se_res runs (saltnet.h): C a multiple of 64 up to 2048, R = C / 16."""
+        return C % 64 == 0 and C <= 2048 and R * 16 == C
+
+    def se_res(self, x, bn, se, res, out=None, name=''):
+        """relu(x * gate(x) + res) with gate = sigmoid(fc2(relu(fc1(mean_hw x)))) (SEModule + the residual tail of SEResNetBottleneck).
+        ``x`` is what ``Graph.conv(a, conv3, bn, relu=False)`` returned.  Training with consumer-side BatchNorm shards: this operator is
+        the only reader of that activation, so the affine_act that would store it is taken back out of the program (_take_act_op) and
+        the kernels apply ``bn``'s scale / shift to the raw convolution output themselves (salt_se_res_args.in_fin); otherwise (eval:
+        BatchNorm folded into the convolution; the partials protocols) x is read as stored.  Backward: dL/dres with the accumulate
+        convention of Graph.conv(.., res=), dL/dx into x's gradient - the closure of the convolution in front runs bn's backward on it."""
+        fc1, fc2 = se.fc1, se.fc2
+        B, C, R = x.B, x.C, fc1.weight.shape[0]
+        if bn.num_features != C or tuple(fc1.weight.shape) != (R, C, 1, 1) or tuple(fc2.weight.shape) != (C, R, 1, 1) or not self.se_res_ok(C, R):
+            raise SaltError('se_res %s: %d channels with fc1 %s / fc2 %s (C a multiple of 64 up to 2048 and C / 16 hidden units are supported)'
+                            % (name, C, tuple(fc1.weight.shape), tuple(fc2.weight.shape)))
+        if (res.B, res.H, res.W, res.C) != (x.B, x.H, x.W, C):
+            raise SaltError('se_res %s: shortcut %s does not fit %s' % (name, (res.B, res.H, res.W, res.C), (x.B, x.H, x.W, C)))
+        if out is None:
+            out = self.new_act(x.B, x.H, x.W, C, name)
+        shards = bool(self.train and self._fin_mode() == 2 and switches.get('SALT_SE_SHARDS'))   # per-image sums through the zeroed fp64 arena
+        taken = self._take_act_op(x) if (self.train and switches.get('SALT_SE_RES_IN_BN')) else None
+        if taken is not None:
+            sa, Fbn = taken
+            xv_ = sa.y                                   # the raw convolution output; never x.view(): the activation has no storage
+            in_kw, in_bwd = dict(in_fin=ctypes.addressof(Fbn)), dict(in_scale=Fbn.scale, in_shift=Fbn.shift)
+        else:
+            xv_, in_kw, in_bwd = None, {}, {}
+        xview = (lambda: xv_) if taken is not None else x.view
+        nparts = lib.salt_se_res_parts(ctypes.byref(fill(STRUCTS['salt_se_res_args'](), dtype=self.dt, x=xview())))
+        if nparts < 1:
+            raise SaltError('se_res plan failed: ' + lib.salt_last_error().decode(errors='replace'))
+        gap, hid, gate = self.f32(B * C), self.f32(B * R), self.f32(B * C)
+        # (one workspace name for both programs: the operator is the main branch's and is never emitted inside Graph.side())
+        ws = Scratch('se_res', B * nparts * C * 4)
+        if res.on_side:
+            self.join()                                  # the projection shortcut ran on the side stream
+        sf = self.fwd.add('se_res', dtype=self.dt, x=xview(), res=res.view(), w1=fc1.weight.data_ptr(), b1=fc1.bias.data_ptr(), w2=fc2.weight.data_ptr(),
+                          b2=fc2.bias.data_ptr(), R=R, gap_partials=None if shards else ws, nparts=nparts, gap=gap.data_ptr(), hidden=hid.data_ptr(),
+                          gate=gate.data_ptr(), y=out.view(), **in_kw)
+        if taken is not None:
+            self._retarget_fin_acc(sa, sf, 'in_fin_acc')
+        if shards:
+            self._fin_slot('fwd', B * C, (sf, 'gap_acc'))
+        out.on_side = self.fwd.default_stream == 1
+        if self.train:
+            def backward():
+                acc_res = res.grad_state()
+                assert x.grad_state() == 0, 'the BatchNorm output in front of se_res has a single consumer'
+                gp = self._gp
+                du, dh, dgap = self.f32(B * C), self.f32(B * R), self.f32(B * C)
+                kw = dict(dtype=self.dt, x=xview(), y=out.view(), dy=out.gview(), w1=fc1.weight.data_ptr(), w2=fc2.weight.data_ptr(), R=R,
+                          gap=gap.data_ptr(), hidden=hid.data_ptr(), gate=gate.data_ptr(), partials=None if shards else ws,
+                          nparts=nparts, du=du.data_ptr(), dh=dh.data_ptr(), dgap=dgap.data_ptr(), dx=x.gview(), dres=res.gview(),
+                          accumulate_dres=acc_res, g_w1=gp(fc1.weight), g_b1=gp(fc1.bias), g_w2=gp(fc2.weight), g_b2=gp(fc2.bias),
+                          defer_param_grads=1, **in_bwd)
+                sb = self.bwd.add('se_res_bwd', **kw)
+                # the four parameter gradients are nobody's input before the optimizer: their launch goes to the weight-gradient queue
+                self.bwd.add('se_res_fc_grads', stream=1, **kw)
+                if shards:
+                    self._fin_slot('bwd', B * C, (sb, 'acc'))
+            self.tape.append(backward)
+        return out
+
     # ------------------------------------------------------------------ depth-conditioned channel gate (csrc/depth.hip)
     def _gate_shards(self):
         """dL/ds travels like the cSE pooled sums (Graph.scse): fp64 atomics into the zeroed arena, or fixed-order partials."""

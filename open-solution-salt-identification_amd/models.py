@@ -30,6 +30,10 @@ ARCHITECTURES = {
     'UNetResNetWithDepth': {'model': A.UNetResNetWithDepth,
                             'model_config': {'encoder_depth': 34, 'use_hypercolumn': True, 'dropout_2d': 0.0, 'pretrained': False},
                             'init_weights': False},
+    # models.py:20-24 with `pretrained` off, like the other entries here: SE-ResNet50 encoders (csrc/se_res.hip)
+    'UNetSeResNet': {'model': A.UNetSeResNet,
+                     'model_config': {'encoder_depth': 50, 'use_hypercolumn': True, 'dropout_2d': 0.0, 'pretrained': False, 'pool0': False},
+                     'init_weights': False},
     # unet_models.py zoo (named by BASELINE.json's north_star; not wired into the reference's registry)
     'TernausUNetResNet': {'model': A.TernausUNetResNet,
                           'model_config': {'encoder_depth': 34, 'num_filters': 32, 'dropout_2d': 0.0, 'pretrained': False, 'is_deconv': True},

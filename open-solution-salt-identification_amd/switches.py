@@ -38,6 +38,7 @@ SWITCHES = {
     'SALT_SE_IN_BN': (True, _not0, '0: scSE reads a materialised activation instead of applying BatchNorm + ReLU itself'),
     'SALT_SE_FC_SIDE': (True, _not0, '0: scSE backward\'s FC weight gradients on the main stream'),
     'SALT_SE_BNB': (True, _not0, '0: scSE backward does not carry the BatchNorm-backward sums of its input\'s producer'),
+    'SALT_SE_RES_IN_BN': (True, _not0, '0: the SE-ResNet block tail reads the materialised BatchNorm output instead of applying scale / shift itself (measured 0.2 ms per step slower, DESIGN 16; tools/seresnet_bench.py)'),
     'SALT_RCCL_MAX_NCHANNELS': (0, int, '> 0: export NCCL_MAX_NCHANNELS=<n> before the process group is created'),
     'SALT_NO_PIN': (False, _nonempty, 'leave the process\'s CPU affinity alone'),
     'SALT_FORCE_DP_PATH': (False, _nonempty, 'one rank runs the bucketed all-reduce backward (bench.py, tools/dp_overhead.py)'),
