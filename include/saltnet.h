@@ -1274,6 +1274,69 @@ typedef struct {
 int salt_se_res_bwd(const salt_se_res_bwd_args*, void* stream);
 int salt_se_res_fc_grads(const salt_se_res_bwd_args*, void* stream);
 
+/* ------------------------------------------------------------------ grouped 3x3 convolution (csrc/conv_group.hip): conv2 of
+ * SEResNeXtBottleneck in the public pretrainedmodels senet.py (reached through architectures/encoders.py:86-118), restated:
+ * nn.Conv2d(C, C, 3, stride, padding 1, groups 32, bias=False).  With Cg = C / 32, g = n / Cg:
+ *   conv[b,oy,ox,n] = sum_{k < Cg, kh, kw} w[n][k][kh][kw] x[b, oy stride + kh - 1, ox stride + kw - 1, g Cg + k]   (zero outside x)
+ * on [B,OH,OW,C], OH = (H - 1) / stride + 1 (floor; odd maps are legal).  The kernels read the fp32 master weight [C][Cg][3][3]
+ * directly - there is no packed copy - and contract in fp32 on the vector ALU with the true Cg (36 .. 288 multiply-adds per output).
+ * C in {128, 256, 512, 1024}, groups 32, stride 1 | 2, any B, H, W >= 1; views 16-byte aligned with cs a multiple of 4 (f32) / 8
+ * (bf16); anything else is SALT_E_UNSUPPORTED / SALT_E_BADARG with a salt_last_error text (the shape rule needs no GPU).
+ *   eval  (stats == NULL and fin_acc == NULL):  y = relu?(conv scale[n] + shift[n])      (scale / shift both NULL: y = relu?(conv))
+ *   train (stats or fin_acc, never both; scale / shift NULL, relu 0):  y = conv, and the BatchNorm statistics of the STORED y:
+ *       stats / stats_cnt: per-tile (sum, M2 about the tile's own mean, count), tile < salt_gconv_stats_parts, fixed order, no
+ *           atomics (salt_bn_finalize's protocol);
+ *       fin_acc: [8][2 C + 1] fp64 shards (sum, sum of squares, count), shard = workgroup id % 8, added with fp64 atomics and NO
+ *           ticket: the consumer finalizes (salt_conv_args.fin_acc without fin_ticket).  Zero before the launch (salt_zero). */
+typedef struct {
+    int dtype;
+    salt_view x;              /* [B,H,W,C], may be a channel slice */
+    const float* w;           /* fp32 master weight [C][C / groups][3][3] */
+    int groups;               /* 32 */
+    int stride;               /* 1 | 2 */
+    salt_view y;              /* out [B,OH,OW,C] */
+    const float* scale;       /* eval: folded BatchNorm [C], or both NULL */
+    const float* shift;
+    int relu;
+    float* stats;             /* train, partials: [nparts][2][C] (sized by salt_bn_stats_floats) */
+    float* stats_cnt;         /* [nparts] */
+    double* fin_acc;          /* train, shards: [8][2 C + 1] */
+} salt_gconv_args;
+int salt_gconv(const salt_gconv_args*, void* stream);
+int salt_gconv_stats_parts(const salt_gconv_args*);   /* x's shape, groups and stride are read; < 0: unsupported shape */
+
+/* dx[b,iy,ix,g Cg + k] (+)= sum_{n in group g, kh, kw} w[n][k][kh][kw] dy[b,oy,ox,n] over the (oy, ox) with oy stride + kh - 1 = iy,
+ * ox stride + kw - 1 = ix: the gather form - with stride 2 an input pixel takes only the taps of its own parity, in ONE launch.
+ * accumulate follows Act.grad_state(): 0 overwrites every element of dx, 1 adds to the stored value (one more storage rounding). */
+typedef struct {
+    int dtype;
+    salt_view dy;             /* [B,OH,OW,C] */
+    const float* w;           /* [C][C / groups][3][3] */
+    int groups;
+    int stride;
+    salt_view dx;             /* out [B,H,W,C]; OH = (H - 1) / stride + 1 is checked against dy */
+    int accumulate;
+} salt_gconv_dgrad_args;
+int salt_gconv_dgrad(const salt_gconv_dgrad_args*, void* stream);
+
+/* grad[n][k][kh][kw] (+)= sum_{b,oy,ox} dy[b,oy,ox,n] x[b, oy stride + kh - 1, ox stride + kw - 1, g Cg + k]: the reference layout
+ * [C][Cg][3][3].  Two launches of one entry point: nsplit = salt_gconv_wgrad_parts pixel splits write partial slabs
+ * [nsplit][C][Cg][3][3] (fixed summation order inside a split), the second launch adds them in ascending split order - no atomics,
+ * the same bits on every run. */
+typedef struct {
+    int dtype;
+    salt_view x;              /* [B,H,W,C] forward input */
+    salt_view dy;             /* [B,OH,OW,C] */
+    int groups;
+    int stride;
+    float* partials;          /* workspace [nsplit][C][Cg][3][3] fp32 */
+    int nsplit;               /* as returned by salt_gconv_wgrad_parts */
+    float* grad;              /* out [C][Cg][3][3] */
+    int accumulate;           /* grad += */
+} salt_gconv_wgrad_args;
+int salt_gconv_wgrad(const salt_gconv_wgrad_args*, void* stream);
+int salt_gconv_wgrad_parts(const salt_gconv_wgrad_args*);   /* x's shape, groups and stride are read; < 0: unsupported shape */
+
 #ifdef __cplusplus
 }
 #endif

@@ -16,7 +16,8 @@ Reference classes mirrored (paths relative to the reference's common_blocks/):
   architectures/misc.py:39-81 EmptinessClassifier
   architectures/encoders.py:48-83 SeResNetEncoders;  architectures/unet.py:112-172 UNetSeResNet
   pretrainedmodels senet.py (un-vendored dependency, layout RESTATED from its public source, not executed): SENet / SEResNetBottleneck /
-  SEModule as se_resnet50 / 101 / 152 build them
+  SEModule as se_resnet50 / 101 / 152 build them; SEResNeXtBottleneck as se_resnext50_32x4d / se_resnext101_32x4d build it
+  architectures/encoders.py:86-118 SeResNetXtEncoders;  architectures/unet.py:175-235 UNetSeResNetXt
   torchvision 0.2.0 models/resnet.py (un-vendored dependency): ResNet / BasicBlock / Bottleneck layout
 """
 import math
@@ -329,15 +330,50 @@ class SEResNetBottleneck(EmitOnly):
         return y
 
 
+class SEResNeXtBottleneck(EmitOnly):
+    """senet.py SEResNeXtBottleneck: the ResNeXt type-C bottleneck with an SEModule - conv1 is a plain 1x1, the grouped 3x3 conv2
+    carries the stride.  conv2 -> bn2 runs on Graph.gconv (csrc/conv_group.hip); everything else is SEResNetBottleneck.emit."""
+    expansion = 4
+
+    def __init__(self, inplanes, planes, groups, reduction, stride=1, downsample=None, base_width=4):
+        super().__init__()
+        width = math.floor(planes * (base_width / 64)) * groups
+        self.conv1 = nn.Conv2d(inplanes, width, kernel_size=1, bias=False, stride=1)
+        self.bn1 = nn.BatchNorm2d(width)
+        self.conv2 = nn.Conv2d(width, width, kernel_size=3, stride=stride, padding=1, groups=groups, bias=False)
+        self.bn2 = nn.BatchNorm2d(width)
+        self.conv3 = nn.Conv2d(width, planes * 4, kernel_size=1, bias=False)
+        self.bn3 = nn.BatchNorm2d(planes * 4)
+        self.relu = nn.ReLU(inplace=True)
+        self.se_module = SEModule(planes * 4, reduction=reduction)
+        self.downsample = downsample
+        self.stride = stride
+
+    def emit(self, g, x, out=None):
+        idt = x
+        if self.downsample is not None:          # the projection shortcut stays on the side stream, joined at the SE tail
+            with g.side():
+                idt = g.conv(x, self.downsample[0], self.downsample[1], relu=False, name='down')
+        n0 = len(g.tape)
+        a = g.conv(x, self.conv1, self.bn1, relu=True, name='sxbneck.conv1')
+        a = g.gconv(a, self.conv2, self.bn2, relu=True, name='sxbneck.conv2')
+        z = g.conv(a, self.conv3, self.bn3, relu=False, name='sxbneck.conv3')
+        y = g.se_res(z, self.bn3, self.se_module, idt, out=out, name='sxbneck.se')
+        _shortcut_gradient_first(g, n0, self.downsample)
+        return y
+
+
 class SENet(EmitOnly):
-    """senet.py SENet as se_resnet50 / 101 / 152 configure it (groups 1, reduction 16, inplanes 64, input_3x3 False, 1x1 downsample
-    without padding, no dropout): layer0 = Sequential(conv1 7x7 s2 p3, bn1, relu1, pool), layer1 .. layer4, avg_pool, last_linear."""
+    """senet.py SENet as se_resnet50 / 101 / 152 (SEResNetBottleneck, groups 1) and se_resnext50_32x4d / se_resnext101_32x4d
+    (``block`` = SEResNeXtBottleneck, groups 32) configure it - reduction 16, inplanes 64, input_3x3 False, 1x1 downsample without
+    padding, no dropout: layer0 = Sequential(conv1 7x7 s2 p3, bn1, relu1, pool), layer1 .. layer4, avg_pool, last_linear."""
     CFG = {50: [3, 4, 6, 3], 101: [3, 4, 23, 3], 152: [3, 8, 36, 3]}
 
-    def __init__(self, depth, num_classes=1000):
+    def __init__(self, depth, num_classes=1000, block=SEResNetBottleneck, groups=1):
         super().__init__()
         from collections import OrderedDict
         counts = self.CFG[depth]
+        self.block, self.groups = block, groups
         self.inplanes = 64
         self.layer0 = nn.Sequential(OrderedDict([('conv1', nn.Conv2d(3, 64, kernel_size=7, stride=2, padding=3, bias=False)),
                                                  ('bn1', nn.BatchNorm2d(64)), ('relu1', nn.ReLU(inplace=True)),
@@ -348,17 +384,17 @@ class SENet(EmitOnly):
         self.layer4 = self._make(512, counts[3], 2)
         self.avg_pool = nn.AvgPool2d(7, stride=1)
         self.dropout = None
-        self.last_linear = nn.Linear(512 * SEResNetBottleneck.expansion, num_classes)      # present in the state_dict, never used
+        self.last_linear = nn.Linear(512 * block.expansion, num_classes)      # present in the state_dict, never used
 
     def _make(self, planes, n, stride):
-        exp = SEResNetBottleneck.expansion
+        exp = self.block.expansion
         down = None
         if stride != 1 or self.inplanes != planes * exp:
             down = nn.Sequential(nn.Conv2d(self.inplanes, planes * exp, kernel_size=1, stride=stride, padding=0, bias=False),
                                  nn.BatchNorm2d(planes * exp))
-        layers = [SEResNetBottleneck(self.inplanes, planes, 1, 16, stride, down)]
+        layers = [self.block(self.inplanes, planes, self.groups, 16, stride, down)]
         self.inplanes = planes * exp
-        layers += [SEResNetBottleneck(self.inplanes, planes, 1, 16) for _ in range(1, n)]
+        layers += [self.block(self.inplanes, planes, self.groups, 16) for _ in range(1, n)]
         return nn.Sequential(*layers)
 
 
@@ -374,6 +410,25 @@ class SeResNetEncoders(EmitOnly):
             raise SaltError('SeResNetEncoders: pool0=True is not built')
         self.pool0 = False
         self.encoder = SENet(encoder_depth)
+        self.conv1 = nn.Sequential(self.encoder.layer0.conv1, self.encoder.layer0.bn1, self.encoder.layer0.relu1)
+        self.encoder2 = self.encoder.layer1
+        self.encoder3 = self.encoder.layer2
+        self.encoder4 = self.encoder.layer3
+        self.encoder5 = self.encoder.layer4
+
+
+class SeResNetXtEncoders(EmitOnly):
+    def __init__(self, encoder_depth, pretrained=False, pool0=False):
+        super().__init__()
+        if encoder_depth not in (50, 101):
+            raise NotImplementedError('only 50, 101 version of Resnet are implemented')
+        if pretrained:
+            raise SaltError('pretrained ImageNet weights need a download; load a state_dict instead')
+        if pool0:
+            # encoders.py:97-101 reads layer0.pool0 for it, as SeResNetEncoders does - out of scope in the same way
+            raise SaltError('SeResNetXtEncoders: pool0=True is not built')
+        self.pool0 = False
+        self.encoder = SENet(encoder_depth, block=SEResNeXtBottleneck, groups=32)
         self.conv1 = nn.Sequential(self.encoder.layer0.conv1, self.encoder.layer0.bn1, self.encoder.layer0.relu1)
         self.encoder2 = self.encoder.layer1
         self.encoder3 = self.encoder.layer2
@@ -600,6 +655,14 @@ class UNetSeResNet(UNetResNet):
 
     def dead_parameter_names(self):
         return ['encoders.encoder.last_linear.weight', 'encoders.encoder.last_linear.bias']
+
+
+class UNetSeResNetXt(UNetSeResNet):
+    """architectures.unet.UNetSeResNetXt (unet.py:175-235): the same decoder, hypercolumn and head once more, on SE-ResNeXt50 / 101
+    (32x4d) encoders - the grouped 3x3 of every bottleneck runs on csrc/conv_group.hip."""
+
+    def _make_encoders(self, encoder_depth, pretrained, pool0):
+        return SeResNetXtEncoders(encoder_depth, pretrained=pretrained, pool0=pool0), 2048
 
 
 class DepthChannelExcitation(EmitOnly):

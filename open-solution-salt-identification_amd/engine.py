@@ -1374,6 +1374,56 @@ class Graph:
         self.tape.append(backward)
         return out
 
+    # ------------------------------------------------------------------ grouped 3x3 convolution (csrc/conv_group.hip)
+    def gconv(self, x, conv, bn, relu=True, out=None, name=''):
+        """nn.Conv2d(C, C, 3, stride 1|2, padding 1, groups 32, bias=False) + BatchNorm2d (+ReLU): conv2 of SEResNeXtBottleneck
+        (salt_gconv, from the fp32 master weight - nothing to pack or refresh).
+        eval: ONE launch with the folded scale / shift.  train: the raw output with its statistics - the fp64 shards under consumer
+        finalize (SALT_BN_FIN=2), per-tile partials + bn_finalize otherwise - and the usual affine_act behind it.
+        Backward: BatchNorm backward, the weight gradient on the weight-gradient stream, the data gradient into x's gradient.  The data
+        gradient offers no BatchNorm-backward carrier: the bn_bwd of the layer in front keeps its own reduction pass."""
+        eng = self.engine
+        C = x.C
+        stride, groups = conv.stride[0], conv.groups
+        if tuple(conv.weight.shape) != (C, C // max(groups, 1), 3, 3) or tuple(conv.padding) != (1, 1) or conv.stride[0] != conv.stride[1] \
+                or conv.bias is not None or bn is None or bn.num_features != C:
+            raise SaltError('gconv %s: weight %s, padding %s, stride %s on %d channels (a bias-free 3x3, padding 1, with BatchNorm is expected)'
+                            % (name, tuple(conv.weight.shape), tuple(conv.padding), tuple(conv.stride), C))
+        S = fill(STRUCTS['salt_gconv_args'](), dtype=self.dt, x=shaped_view(1, x.B, x.H, x.W, C), groups=groups, stride=stride)
+        nparts = lib.salt_gconv_stats_parts(ctypes.byref(S))
+        if nparts < 1:
+            raise SaltError('gconv %s: %s' % (name, lib.salt_last_error().decode(errors='replace')))
+        OH, OW = (x.H - 1) // stride + 1, (x.W - 1) // stride + 1
+        if out is None:
+            out = self.new_act(x.B, OH, OW, C, name)
+        if (out.B, out.H, out.W, out.C) != (x.B, OH, OW, C):
+            raise SaltError('gconv %s: output %s does not fit %s' % (name, (out.B, out.H, out.W, out.C), (x.B, OH, OW, C)))
+        common = dict(dtype=self.dt, w=conv.weight.data_ptr(), groups=groups, stride=stride)
+        if x.on_side and self.fwd.default_stream == 0:
+            self.join()
+        if not self.train:
+            w = eng.bn_work(bn)
+            self.fwd.add('gconv', x=x.view(), y=out.view(), scale=w['scale'].data_ptr(), shift=w['shift'].data_ptr(), relu=int(relu), **common)
+            out.on_side = self.fwd.default_stream == 1
+            return out
+        y = self.new_act(x.B, OH, OW, C, name + '.y')
+        w, _ = self._bn_behind(lambda **st: self.fwd.add('gconv', x=x.view(), y=y.view(), **st, **common), self._fin_mode() == 2, nparts, y, bn, relu,
+                               None, out, self._scratch_sfx)
+        out.on_side = self.fwd.default_stream == 1
+
+        def backward():
+            self._bn_train_bwd(y, bn, relu, None, out, w)
+            wg = dict(dtype=self.dt, x=x.view(), dy=y.gview(), groups=groups, stride=stride)
+            ns = lib.salt_gconv_wgrad_parts(ctypes.byref(fill(STRUCTS['salt_gconv_wgrad_args'](), **wg)))
+            if ns < 1:
+                raise SaltError('gconv %s: weight-gradient plan failed: %s' % (name, lib.salt_last_error().decode(errors='replace')))
+            self.bwd.add('gconv_wgrad', stream=1, partials=Scratch('gconv_wgrad', ns * conv.weight.numel() * 4), nsplit=ns,
+                         grad=self._gp(conv.weight), accumulate=0, **wg)
+            acc = x.grad_state()
+            self.bwd.add('gconv_dgrad', dy=y.gview(), dx=x.gview(), accumulate=acc, **common)
+        self.tape.append(backward)
+        return out
+
     # ------------------------------------------------------------------ logit head: 1x1 conv to <= 4 channels, fp32 NCHW out
     def head(self, x, conv, logits_nchw):
         Cout = conv.weight.shape[0]

@@ -34,6 +34,10 @@ ARCHITECTURES = {
     'UNetSeResNet': {'model': A.UNetSeResNet,
                      'model_config': {'encoder_depth': 50, 'use_hypercolumn': True, 'dropout_2d': 0.0, 'pretrained': False, 'pool0': False},
                      'init_weights': False},
+    # models.py:25-29 with `pretrained` off: SE-ResNeXt50 (32x4d) encoders (csrc/conv_group.hip + csrc/se_res.hip)
+    'UNetSeResNetXt': {'model': A.UNetSeResNetXt,
+                       'model_config': {'encoder_depth': 50, 'use_hypercolumn': True, 'dropout_2d': 0.0, 'pretrained': False, 'pool0': False},
+                       'init_weights': False},
     # unet_models.py zoo (named by BASELINE.json's north_star; not wired into the reference's registry)
     'TernausUNetResNet': {'model': A.TernausUNetResNet,
                           'model_config': {'encoder_depth': 34, 'num_filters': 32, 'dropout_2d': 0.0, 'pretrained': False, 'is_deconv': True},
