@@ -295,8 +295,10 @@ typedef struct {
     const float* scale;
     const float* shift;
     int relu;
-    float* stats;
-    float* stats_cnt;
+    float* stats;             /* NULL or [tiles][2][Cout] fp32, tiles = salt_conv_first_stats_parts: per 16 x 16 output tile (image-major, then tile row,
+                               * tile column) the sum over the tile's pixels inside the image, then M2 = sum (v - tile mean)^2 of the same pixels;
+                               * v is the epilogue value before its storage rounding (the salt_bn_finalize partial layout) */
+    float* stats_cnt;         /* [tiles] fp32: the tile's count of pixels inside the image (required with stats) */
 } salt_conv_first_args;
 int salt_conv_first(const salt_conv_first_args*, void* stream);
 int salt_conv_first_stats_parts(const salt_conv_first_args*);
@@ -319,6 +321,10 @@ typedef struct {
 } salt_conv_first_wgrad_args;
 int salt_conv_first_wgrad(const salt_conv_first_wgrad_args*, void* stream);
 int salt_conv_first_wgrad_parts(const salt_conv_first_wgrad_args*);
+/* which instantiation salt_conv_first_wgrad runs these arguments on (host only, no launch; tests): low byte 0 = the MFMA path of
+ * conv_first_wgrad_kernel (Cout % 16 == 0, K K Cin <= 16), else its scalar loop's PER (1, 4, 12 or 40 taps per thread); + 256 when
+ * partial_sum_wide_kernel reduces the partials (nparts >= 64 and Cout Cin K K <= 4096), else partial_sum_kernel; < 0: refused */
+int salt_conv_first_wgrad_kernel_id(const salt_conv_first_wgrad_args*);
 
 /* ResNet stem on the matrix cores: conv KxK stride 2 (K odd, pad K/2; 7x7 s2 p3 in torchvision) over Cin <= 4 channels
  * == a ((K+1)/2)^2-tap stride-1 convolution over the 2x2 space-to-depth image z[b,Y,X,(ph*2+pw)*Cin+c] = x[b,c,2Y+ph,2X+pw]
@@ -365,6 +371,9 @@ typedef struct {
     salt_view y;              /* NHWC output (used when y_nchw == NULL) */
 } salt_head1x1_args;
 int salt_head1x1(const salt_head1x1_args*, void* stream);
+/* which kernel salt_head1x1 runs these arguments on (host only, no launch; tests): 1 head1x1_kernel (scalar), 2 head1x1_vec_kernel,
+ * 3 head1x1_vec_co_kernel<2>; < 0: refused */
+int salt_head1x1_kernel_id(const salt_head1x1_args*);
 
 typedef struct {
     int dtype;
@@ -381,6 +390,8 @@ typedef struct {
 } salt_head1x1_bwd_args;
 int salt_head1x1_bwd(const salt_head1x1_bwd_args*, void* stream);
 int salt_head1x1_bwd_parts(const salt_head1x1_bwd_args*);
+/* 1 head1x1_bwd_kernel (scalar), 2 head1x1_bwd_vec_kernel; < 0: refused (host only, no launch; tests) */
+int salt_head1x1_bwd_kernel_id(const salt_head1x1_bwd_args*);
 
 /* ------------------------------------------------------------------ BatchNorm2d (+ReLU, +residual)
  * torch semantics (eps 1e-5, momentum 0.1, biased batch variance for normalisation, unbiased for the

@@ -625,10 +625,16 @@ extern "C" int salt_conv_first_wgrad_parts(const salt_conv_first_wgrad_args* a) 
     return a->B * cdiv(OH, FT) * cdiv(OW, FT);
 }
 
-extern "C" int salt_conv_first_wgrad(const salt_conv_first_wgrad_args* a, void* stream) {
-    if (!a || !a->x || !view_ok(a->dy) || !a->partials || !a->grad || a->Cin < 1 || a->Cin > 4 || a->K < 1 || a->K > 7)
+namespace {
+
+// everything salt_conv_first_wgrad decides on the host, for the launch and for salt_conv_first_wgrad_kernel_id alike
+struct FirstWgPlan { FirstWgKP p; int nparts; size_t lds; int per_inst; bool wide; int64_t n; };
+
+int first_wgrad_plan(const salt_conv_first_wgrad_args* a, FirstWgPlan* pl) {
+    if (!a || !a->x || !view_ok(a->dy) || !a->partials || !a->grad || a->Cin < 1 || a->Cin > 4 || a->K < 1 || a->K > 7 || a->stride < 1 || a->stride > 2)
         SALT_FAIL(SALT_E_BADARG, "conv_first_wgrad: bad args");
-    FirstWgKP p;
+    if (a->dtype != SALT_F32 && a->dtype != SALT_BF16) SALT_FAIL(SALT_E_BADARG, "bad dtype %d", (int)a->dtype);
+    FirstWgKP& p = pl->p;
     int OH, OW;
     p.halo = first_geom(a->H, a->W, a->K, a->stride, a->pad, &OH, &OW);
     if (a->dy.H != OH || a->dy.W != OW || a->dy.B != a->B) SALT_FAIL(SALT_E_BADARG, "conv_first_wgrad: dy view shape");
@@ -641,20 +647,38 @@ extern "C" int salt_conv_first_wgrad(const salt_conv_first_wgrad_args* a, void* 
     p.groups = 256 / Cout;
     p.per = cdiv(KKC, p.groups);
     if (p.per > MAXKK) SALT_FAIL(SALT_E_UNSUPPORTED, "conv_first_wgrad: %d taps per thread > %d", p.per, MAXKK);
-    const int nparts = a->B * p.tiles_y * p.tiles_x;
-    if (a->nparts != nparts) SALT_FAIL(SALT_E_BADARG, "conv_first_wgrad: nparts %d, expected %d", a->nparts, nparts);
+    pl->nparts = a->B * p.tiles_y * p.tiles_x;
+    if (a->nparts != pl->nparts) SALT_FAIL(SALT_E_BADARG, "conv_first_wgrad: nparts %d, expected %d", a->nparts, pl->nparts);
     p.mfma = (Cout % 16 == 0 && KKC <= 16) ? 1 : 0;
-    const size_t lds = sizeof(float) * ((size_t)p.Cin * p.halo * p.halo + (size_t)256 * Cout + (p.mfma ? 1024 : 0));
-    if (lds > 160 * 1024) SALT_FAIL(SALT_E_LDS, "conv_first_wgrad: needs %zu bytes of LDS", lds);
-    SALT_DISPATCH_DTYPE(a->dtype, T, {
-        auto kern = p.per <= 1 ? conv_first_wgrad_kernel<T, 1> : p.per <= 4 ? conv_first_wgrad_kernel<T, 4> : p.per <= 12 ? conv_first_wgrad_kernel<T, 12>
-                                                                                                                 : conv_first_wgrad_kernel<T, MAXKK>;
-        const int rc = salt_launch(kern, dim3(nparts), dim3(256), lds, (hipStream_t)stream, p);
-        if (rc) return rc;
-    })
-    const int64_t n = (int64_t)Cout * KKC;
-    if (nparts >= 64 && n <= 4096) hipLaunchKernelGGL(partial_sum_wide_kernel, dim3((unsigned)n), dim3(256), 0, (hipStream_t)stream, a->partials, nparts, n, a->grad, a->accumulate);
-    else hipLaunchKernelGGL(partial_sum_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a->partials, nparts, n, a->grad, a->accumulate);
+    pl->lds = sizeof(float) * ((size_t)p.Cin * p.halo * p.halo + (size_t)256 * Cout + (p.mfma ? 1024 : 0));
+    if (pl->lds > 160 * 1024) SALT_FAIL(SALT_E_LDS, "conv_first_wgrad: needs %zu bytes of LDS", pl->lds);
+    pl->per_inst = p.per <= 1 ? 1 : p.per <= 4 ? 4 : p.per <= 12 ? 12 : MAXKK;
+    pl->n = (int64_t)Cout * KKC;
+    pl->wide = pl->nparts >= 64 && pl->n <= 4096;
+    return SALT_OK;
+}
+
+template <typename T>
+int first_wgrad_launch(const FirstWgPlan& pl, hipStream_t st) {
+    auto kern = pl.per_inst == 1 ? conv_first_wgrad_kernel<T, 1> : pl.per_inst == 4 ? conv_first_wgrad_kernel<T, 4>
+              : pl.per_inst == 12 ? conv_first_wgrad_kernel<T, 12> : conv_first_wgrad_kernel<T, MAXKK>;
+    return salt_launch(kern, dim3(pl.nparts), dim3(256), pl.lds, st, pl.p);
+}
+
+}  // namespace
+
+extern "C" int salt_conv_first_wgrad_kernel_id(const salt_conv_first_wgrad_args* a) {
+    FirstWgPlan pl;
+    if (first_wgrad_plan(a, &pl)) return -1;
+    return (pl.p.mfma ? 0 : pl.per_inst) | (pl.wide ? 256 : 0);
+}
+
+extern "C" int salt_conv_first_wgrad(const salt_conv_first_wgrad_args* a, void* stream) {
+    FirstWgPlan pl;
+    if (const int rc = first_wgrad_plan(a, &pl)) return rc;
+    if (const int rc = a->dtype == SALT_F32 ? first_wgrad_launch<float>(pl, (hipStream_t)stream) : first_wgrad_launch<bf16_t>(pl, (hipStream_t)stream)) return rc;
+    if (pl.wide) hipLaunchKernelGGL(partial_sum_wide_kernel, dim3((unsigned)pl.n), dim3(256), 0, (hipStream_t)stream, a->partials, pl.nparts, pl.n, a->grad, a->accumulate);
+    else hipLaunchKernelGGL(partial_sum_kernel, dim3((unsigned)((pl.n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a->partials, pl.nparts, pl.n, a->grad, a->accumulate);
     SALT_CHECK_LAUNCH();
     return SALT_OK;
 }
@@ -687,20 +711,57 @@ extern "C" int salt_stem_grad_unfold(const salt_stem_grad_unfold_args* a, void* 
     return SALT_OK;
 }
 
-extern "C" int salt_head1x1(const salt_head1x1_args* a, void* stream) {
+namespace {
+
+enum { HEAD_SCALAR = 1, HEAD_VEC = 2, HEAD_VEC_CO2 = 3 };
+
+// which forward head kernel these arguments run on (the launch and salt_head1x1_kernel_id): whole aligned 16-byte pieces of VE channels
+// and a power-of-two count of them (<= 64) per pixel -> the vector kernels, Cout == 2 -> the two-output one
+int head_select(const salt_head1x1_args* a) {
     if (!a || !view_ok(a->x) || !a->w || a->Cout < 1 || a->Cout > 4) SALT_FAIL(SALT_E_BADARG, "head1x1: bad args");
     if (!a->y_nchw && (!view_ok(a->y) || a->y.C != a->Cout)) SALT_FAIL(SALT_E_BADARG, "head1x1: no output");
+    if (a->dtype != SALT_F32 && a->dtype != SALT_BF16) SALT_FAIL(SALT_E_BADARG, "bad dtype %d", (int)a->dtype);
+    const int VE = a->dtype == SALT_F32 ? Elem<float>::VE : Elem<bf16_t>::VE;
+    const int cpv = a->x.C / VE;
+    const bool vec = (a->x.C % VE) == 0 && (a->x.cs % VE) == 0 && ((reinterpret_cast<uintptr_t>(a->x.p) & 15) == 0) && cpv >= 1 && cpv <= 64 && (cpv & (cpv - 1)) == 0;
+    if (!vec) return HEAD_SCALAR;
+    const int64_t hw = (int64_t)a->x.H * a->x.W;
+    return a->Cout == 2 && hw < (1ll << 30) ? HEAD_VEC_CO2 : HEAD_VEC;
+}
+
+// 1: head1x1_bwd_kernel, 2: head1x1_bwd_vec_kernel (salt_head1x1_bwd and salt_head1x1_bwd_kernel_id)
+int head_bwd_select(const salt_head1x1_bwd_args* a, int* nparts, int64_t* per) {
+    if (!a || !view_ok(a->x) || !view_ok(a->dx) || !a->w || !a->dy_nchw || !a->partials || !a->gw || a->Cout < 1 || a->Cout > 4)
+        SALT_FAIL(SALT_E_BADARG, "head1x1_bwd: bad args");
+    if (a->dtype != SALT_F32 && a->dtype != SALT_BF16) SALT_FAIL(SALT_E_BADARG, "bad dtype %d", (int)a->dtype);
+    *nparts = head_parts(a->x, per);
+    if (a->nparts != *nparts) SALT_FAIL(SALT_E_BADARG, "head1x1_bwd: nparts %d, expected %d", a->nparts, *nparts);
+    const int VE = a->dtype == SALT_F32 ? Elem<float>::VE : Elem<bf16_t>::VE;
+    const bool v = a->x.C % VE == 0 && a->x.cs % VE == 0 && a->dx.cs % VE == 0 && a->x.C / VE <= 256 &&
+                   ((reinterpret_cast<uintptr_t>(a->x.p) | reinterpret_cast<uintptr_t>(a->dx.p)) & 15) == 0;
+    return v ? HEAD_VEC : HEAD_SCALAR;
+}
+
+}  // namespace
+
+extern "C" int salt_head1x1_kernel_id(const salt_head1x1_args* a) {
+    const int k = head_select(a);
+    return k >= HEAD_SCALAR ? k : -1;
+}
+
+extern "C" int salt_head1x1(const salt_head1x1_args* a, void* stream) {
+    const int kern = head_select(a);
+    if (kern < HEAD_SCALAR) return kern;
     const int64_t npix = view_pixels(a->x);
     SALT_DISPATCH_DTYPE(a->dtype, T, {
         constexpr int VE = Elem<T>::VE;
         const int cpv = a->x.C / VE;
-        const bool vec = (a->x.C % VE) == 0 && (a->x.cs % VE) == 0 && ((reinterpret_cast<uintptr_t>(a->x.p) & 15) == 0) && cpv >= 1 && cpv <= 64 && (cpv & (cpv - 1)) == 0;
-        if (vec) {
+        if (kern != HEAD_SCALAR) {
             const int64_t units = npix * cpv;
             const int blocks = (int)((units + 255) / 256 < 4096 ? (units + 255) / 256 : 4096);
             const int64_t hw = (int64_t)a->x.H * a->x.W;
             const int hw_shift = (hw & (hw - 1)) == 0 ? ilog2_ceil((int)hw) : -1;
-            if (a->Cout == 2 && hw < (1ll << 30))
+            if (kern == HEAD_VEC_CO2)
                 hipLaunchKernelGGL((head1x1_vec_co_kernel<T, 2>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, a->x, a->w, a->bias, a->y_nchw, a->y, ilog2_ceil(cpv), hw_shift);
             else
                 hipLaunchKernelGGL(head1x1_vec_kernel<T>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, a->x, a->w, a->bias, a->Cout, a->y_nchw, a->y, ilog2_ceil(cpv));
@@ -718,19 +779,21 @@ extern "C" int salt_head1x1_bwd_parts(const salt_head1x1_bwd_args* a) {
     return head_parts(a->x, nullptr);
 }
 
+extern "C" int salt_head1x1_bwd_kernel_id(const salt_head1x1_bwd_args* a) {
+    int nparts = 0; int64_t per = 0;
+    const int k = head_bwd_select(a, &nparts, &per);
+    return k >= HEAD_SCALAR ? k : -1;
+}
+
 extern "C" int salt_head1x1_bwd(const salt_head1x1_bwd_args* a, void* stream) {
-    if (!a || !view_ok(a->x) || !view_ok(a->dx) || !a->w || !a->dy_nchw || !a->partials || !a->gw || a->Cout < 1 || a->Cout > 4)
-        SALT_FAIL(SALT_E_BADARG, "head1x1_bwd: bad args");
-    int64_t per = 0;
-    const int nparts = head_parts(a->x, &per);
-    if (a->nparts != nparts) SALT_FAIL(SALT_E_BADARG, "head1x1_bwd: nparts %d, expected %d", a->nparts, nparts);
+    int nparts = 0; int64_t per = 0;
+    const int kern = head_bwd_select(a, &nparts, &per);
+    if (kern < HEAD_SCALAR) return kern;
     const int PW = a->Cout * (a->x.C + 1);
     SALT_DISPATCH_DTYPE(a->dtype, T, {
         constexpr int VE = Elem<T>::VE;
-        const bool v = a->x.C % VE == 0 && a->x.cs % VE == 0 && a->dx.cs % VE == 0 && a->x.C / VE <= 256 &&
-                       ((reinterpret_cast<uintptr_t>(a->x.p) | reinterpret_cast<uintptr_t>(a->dx.p)) & 15) == 0;
-        if (v) hipLaunchKernelGGL(head1x1_bwd_vec_kernel<T>, dim3(nparts), dim3(256), 256 * VE * 4 * sizeof(float), (hipStream_t)stream,
-                                  a->x, a->w, a->Cout, a->dy_nchw, a->dx, a->accumulate, a->partials, per);
+        if (kern == HEAD_VEC) hipLaunchKernelGGL(head1x1_bwd_vec_kernel<T>, dim3(nparts), dim3(256), 256 * VE * 4 * sizeof(float), (hipStream_t)stream,
+                                                 a->x, a->w, a->Cout, a->dy_nchw, a->dx, a->accumulate, a->partials, per);
         else hipLaunchKernelGGL(head1x1_bwd_kernel<T>, dim3(nparts), dim3(256), 256 * 5 * sizeof(float), (hipStream_t)stream,
                                 a->x, a->w, a->Cout, a->dy_nchw, a->dx, a->accumulate, a->partials, per);
     })
