@@ -1348,6 +1348,133 @@ typedef struct {
 int salt_gconv_wgrad(const salt_gconv_wgrad_args*, void* stream);
 int salt_gconv_wgrad_parts(const salt_gconv_wgrad_args*);   /* x's shape, groups and stride are read; < 0: unsupported shape */
 
+/* ------------------------------------------------------------------ pre-activated 1x1 convolution (csrc/dense.hip): conv1 of a
+ * DenseNet layer and the convolution of a transition in the public torchvision / pretrainedmodels densenet.py (reached through
+ * architectures/encoders.py:121-164), restated: conv(relu(norm(x))) with nn.Conv2d(Cin, Cout, 1, bias=False), where x is a channel
+ * prefix of the block's concatenation buffer and norm is a BatchNorm the CONSUMER owns.  The normalised copy of x is never stored:
+ * the loader applies the transform between the global load and the matrix-core operand.
+ *
+ * THE INPUT TRANSFORM IS PINNED, bit for bit, for all three operators:
+ *     t(x)  = fmaf(x, in_scale[c], in_shift[c])        one fused multiply-add in fp32 (x widened exactly from its storage type)
+ *     a(x)  = round_to_dtype(max(0, t(x)))             one rounding to nearest even to the storage type (identity for SALT_F32)
+ *     m(x)  = [t(x) > 0]
+ * A float64 multiply-add of bf16-representable operands, rounded once to fp32, reproduces t exactly; a mask that flipped on a
+ * near-zero t would change the data gradient by a whole value, so reference and kernel must agree on this rule.
+ *
+ * Shapes: Cin a multiple of 32 in [32, 2048], Cout a multiple of 64 in [64, 1024], any B, H, W >= 1 (the GEMM is M = B H W pixels,
+ * K = Cin, N = Cout); anything else is SALT_E_UNSUPPORTED with a salt_last_error text, nothing is launched, and a *_parts query
+ * returns < 0.  Views are 16-byte aligned with cs a multiple of 4 (f32) / 8 (bf16) and C <= cs; w, in_scale and in_shift are 16-byte
+ * aligned (SALT_E_BADARG otherwise).
+ * Weights: the kernels read the fp32 MASTER weight [Cout][Cin] directly - no packed copy, nothing to refresh after an optimizer step.
+ * SALT_BF16 rounds it to bf16 (nearest even) on the way into LDS and contracts with v_mfma_f32_32x32x16_bf16, fp32 accumulation;
+ * SALT_F32 contracts with the exact-f32 v_mfma_f32_32x32x2_f32, as salt_conv does.
+ *
+ *   v[p,n] = sum_c W[n][c] a(x[p,c])
+ *   eval  (stats == NULL):  y = relu?(v scale[n] + shift[n])     (scale / shift both NULL: y = relu?(v); a transition passes neither)
+ *   train (stats != NULL; scale / shift NULL, relu 0):  y = v and the BatchNorm statistics of the STORED y as per-tile partials
+ *       (sum, M2 about the tile's own mean, count), tile < salt_dense_conv_stats_parts, fixed order, no atomics: salt_bn_finalize's
+ *       protocol, the same bits on every run. */
+typedef struct {
+    int dtype;
+    salt_view x;              /* [B,H,W,Cin] raw input, may be a channel prefix / slice of a wider buffer */
+    const float* in_scale;    /* [Cin] */
+    const float* in_shift;    /* [Cin] */
+    const float* w;           /* fp32 master weight [Cout][Cin] */
+    salt_view y;              /* out [B,H,W,Cout] */
+    const float* scale;       /* eval: folded BatchNorm of the OUTPUT [Cout], or both NULL */
+    const float* shift;
+    int relu;
+    float* stats;             /* train: [nparts][2][Cout] (sized by salt_bn_stats_floats) */
+    float* stats_cnt;         /* [nparts] */
+} salt_dense_conv_args;
+int salt_dense_conv(const salt_dense_conv_args*, void* stream);
+int salt_dense_conv_stats_parts(const salt_dense_conv_args*);   /* x's shape and y.C are read; < 0: unsupported shape */
+
+/* Data gradient of the operator above INCLUDING the backward of the train-mode BatchNorm in front of it (norm, with batch statistics
+ * mean / invstd of x and weight gamma).  With g[p,c] = m(x[p,c]) sum_n W[n][c] dy[p,n], N = B H W, xhat = (x - mean[c]) invstd[c]:
+ *     dbeta[c]  = sum_p g[p,c]            dgamma[c] = sum_p g[p,c] xhat[p,c]
+ *     dx[p,c] (+)= gamma[c] invstd[c] (g - dbeta[c] / N - xhat dgamma[c] / N)
+ * Three launches of one entry point: the contraction with the two sums reduced per 128-pixel tile into `partials` (fixed order), a
+ * finalize launch that adds the tiles in ascending order (fp64, rounded once) into `sums` and dgamma / dbeta, and the contraction
+ * again with the apply in its epilogue.  g is RECOMPUTED, not stored: the second pass reads dy once more (M Cout elements) where a
+ * stash would write and read M Cin elements, Cin >= Cout / 2 ... 8 Cout in a DenseNet; both passes run the same instructions, so
+ * they see the same g.  accumulate: 0 overwrites dx, 1 adds to the stored value (one more storage rounding). */
+typedef struct {
+    int dtype;
+    salt_view dy;             /* [B,H,W,Cout] */
+    const float* w;           /* fp32 master weight [Cout][Cin] */
+    salt_view x;              /* [B,H,W,Cin] forward input */
+    const float* in_scale;    /* [Cin] forward transform (mask) */
+    const float* in_shift;
+    const float* mean;        /* [Cin] batch statistics of x */
+    const float* invstd;
+    const float* gamma;       /* [Cin] weight of norm */
+    float* partials;          /* workspace [nparts][2][Cin] fp32 */
+    int nparts;               /* as returned by salt_dense_conv_dgrad_parts */
+    float* sums;              /* workspace [2][Cin]: this launch's dbeta, dgamma */
+    float* dgamma;            /* out [Cin] */
+    float* dbeta;             /* out [Cin] */
+    int accumulate_param_grads;   /* dgamma / dbeta += */
+    salt_view dx;             /* out [B,H,W,Cin] */
+    int accumulate;           /* dx += */
+} salt_dense_conv_dgrad_args;
+int salt_dense_conv_dgrad(const salt_dense_conv_dgrad_args*, void* stream);
+int salt_dense_conv_dgrad_parts(const salt_dense_conv_dgrad_args*);   /* x's shape and dy.C are read; < 0: unsupported shape */
+
+/* grad[n][c] (+)= sum_p dy[p,n] a(x[p,c]) in the master weight's layout [Cout][Cin], the same pinned transform in the loader.
+ * nsplit = salt_dense_conv_wgrad_parts pixel splits write partial slabs [nsplit][Cout][Cin] (fixed order inside a split), a second
+ * launch adds them in ascending split order - no atomics, the same bits on every run. */
+typedef struct {
+    int dtype;
+    salt_view x;              /* [B,H,W,Cin] forward input */
+    const float* in_scale;    /* [Cin] */
+    const float* in_shift;
+    salt_view dy;             /* [B,H,W,Cout] */
+    float* partials;          /* workspace [nsplit][Cout][Cin] fp32 */
+    int nsplit;               /* as returned by salt_dense_conv_wgrad_parts */
+    float* grad;              /* out [Cout][Cin] */
+    int accumulate;           /* grad += */
+} salt_dense_conv_wgrad_args;
+int salt_dense_conv_wgrad(const salt_dense_conv_wgrad_args*, void* stream);
+int salt_dense_conv_wgrad_parts(const salt_dense_conv_wgrad_args*);   /* x's shape and dy.C are read; < 0: unsupported shape */
+
+/* Per-channel moments of a STORED view (the stem output or a pooled transition output that opens a dense block): per-tile partials
+ * (sum, M2 about the tile's own mean, count) over 128-pixel tiles in salt_bn_finalize's protocol, fixed order, no atomics.  No other
+ * operator can supply them: salt_conv reports the statistics of a raw convolution output only, and these channels are the output of
+ * an activation / a pooling pass.  Any C >= 1, any view. */
+typedef struct {
+    int dtype;
+    salt_view x;              /* [B,H,W,C], may be a channel slice */
+    float* stats;             /* [nparts][2][C] (sized by salt_bn_stats_floats) */
+    float* stats_cnt;         /* [nparts] */
+} salt_dense_moments_args;
+int salt_dense_moments(const salt_dense_moments_args*, void* stream);
+int salt_dense_moments_parts(const salt_dense_moments_args*);   /* x's shape is read; < 0: unsupported shape */
+
+/* One statistics table per dense block: channel c of the concatenation buffer has ONE batch mean / variance, whichever later layer
+ * normalises it (the data is identical, only gamma / beta differ).  The table (mean, invstd, unbiased variance per channel) is filled
+ * once, when the channels are produced (salt_bn_finalize with gamma 1, beta 0, momentum 1 on the producer's partials); every layer
+ * then derives its own coefficients for its channel prefix and updates its own running statistics, with salt_bn_finalize's arithmetic:
+ *     in_scale = gamma invstd      in_shift = beta - mean in_scale
+ *     running_mean = (1 - momentum) running_mean + momentum mean      running_var likewise with the unbiased variance
+ *     num_batches_tracked += 1
+ * so that a layer's state_dict comes out as if it had computed the statistics itself. */
+typedef struct {
+    int C;
+    const float* mean;        /* [C] the block's table */
+    const float* invstd;
+    const float* unbiased_var;
+    const float* gamma;       /* [C] the layer's BatchNorm */
+    const float* beta;
+    float* running_mean;      /* [C] or both NULL */
+    float* running_var;
+    int64_t* num_batches_tracked;   /* or NULL */
+    float momentum;
+    float* in_scale;          /* out [C] */
+    float* in_shift;          /* out [C] */
+} salt_dense_bn_prep_args;
+int salt_dense_bn_prep(const salt_dense_bn_prep_args*, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

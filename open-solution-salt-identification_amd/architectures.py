@@ -19,6 +19,9 @@ Reference classes mirrored (paths relative to the reference's common_blocks/):
   SEModule as se_resnet50 / 101 / 152 build them; SEResNeXtBottleneck as se_resnext50_32x4d / se_resnext101_32x4d build it
   architectures/encoders.py:86-118 SeResNetXtEncoders;  architectures/unet.py:175-235 UNetSeResNetXt
   torchvision 0.2.0 models/resnet.py (un-vendored dependency): ResNet / BasicBlock / Bottleneck layout
+  torchvision / pretrainedmodels densenet.py (un-vendored dependency, layout RESTATED from the public source, not executed): DenseNet /
+  _DenseBlock / _DenseLayer / _Transition as densenet121 / 169 / 201 build them
+  architectures/encoders.py:121-164 DenseNetEncoders;  architectures/unet.py:238-307 UNetDenseNet
 """
 import math
 
@@ -436,6 +439,113 @@ class SeResNetXtEncoders(EmitOnly):
         self.encoder5 = self.encoder.layer4
 
 
+
+# ----------------------------------------------------------------------------- DenseNet (public torchvision / pretrainedmodels layout, restated)
+class _DenseLayer(EmitOnly):
+    """norm1 -> relu1 -> conv1 (1x1, bn_size * growth) -> norm2 -> relu2 -> conv2 (3x3, growth); the output is concatenated behind the
+    input.  Module names are the modern ones (torchvision 0.2.0 registered 'norm.1' ...; UNetDenseNet.load_state_dict translates)."""
+
+    def __init__(self, num_input_features, growth_rate, bn_size, drop_rate):
+        super().__init__()
+        if drop_rate:
+            raise SaltError('_DenseLayer: drop_rate > 0 is not built')
+        self.norm1 = nn.BatchNorm2d(num_input_features)
+        self.relu1 = nn.ReLU(inplace=True)
+        self.conv1 = nn.Conv2d(num_input_features, bn_size * growth_rate, kernel_size=1, stride=1, bias=False)
+        self.norm2 = nn.BatchNorm2d(bn_size * growth_rate)
+        self.relu2 = nn.ReLU(inplace=True)
+        self.conv2 = nn.Conv2d(bn_size * growth_rate, growth_rate, kernel_size=3, stride=1, padding=1, bias=False)
+        self.growth_rate = growth_rate
+
+    def emit(self, g, block, c, table):
+        """``block``: the concatenation buffer; reads its prefix [0, c), writes the slice [c, c + growth) - no copy.  conv2's launch
+        also reports the statistics of its 32 raw channels, which every later norm1 of the block shares (``table``)."""
+        a = g.dense_conv(block.slice(0, c), self.norm1, self.conv1, self.norm2, relu=True, table=table, name='denselayer.conv1')
+        fill = (lambda st, cnt, n: g.dense_table_fill(table, c, self.growth_rate, st, cnt, n)) if g.train else None
+        return g.conv(a, self.conv2, None, relu=False, out=block.slice(c, self.growth_rate), name='denselayer.conv2', raw_stats=fill)
+
+
+class _DenseBlock(nn.Sequential):
+    def __init__(self, num_layers, num_input_features, bn_size, growth_rate, drop_rate):
+        super().__init__()
+        for i in range(num_layers):
+            self.add_module('denselayer%d' % (i + 1), _DenseLayer(num_input_features + i * growth_rate, growth_rate, bn_size, drop_rate))
+
+    def forward(self, *a, **k):
+        return EmitOnly.forward(self, *a, **k)
+
+
+class _Transition(EmitOnly):
+    def __init__(self, num_input_features, num_output_features):
+        super().__init__()
+        self.norm = nn.BatchNorm2d(num_input_features)
+        self.relu = nn.ReLU(inplace=True)
+        self.conv = nn.Conv2d(num_input_features, num_output_features, kernel_size=1, stride=1, bias=False)
+        self.pool = nn.AvgPool2d(kernel_size=2, stride=2)
+
+    def emit(self, g, block, table, out):
+        return g.avgpool2(g.dense_conv(block, self.norm, self.conv, None, relu=False, table=table, name='transition.conv'), out=out, name='transition.pool')
+
+
+class DenseNet(EmitOnly):
+    """densenet121 / 169 / 201: growth 32, bn_size 4, 64 initial features, bias-free convolutions, BatchNorm eps 1e-5, AvgPool2d(2, 2) in
+    the transitions, drop rate 0.  features = conv0, norm0, relu0, pool0, denseblock1, transition1, ..., denseblock4, norm5; the
+    classifier is pretrainedmodels' ``last_linear``.  norm5 and last_linear are in the state_dict and never used by the U-Net."""
+    CFG = {121: (6, 12, 24, 16), 169: (6, 12, 32, 32), 201: (6, 12, 48, 32)}
+    GROWTH, BN_SIZE, INIT = 32, 4, 64
+
+    def __init__(self, depth, num_classes=1000):
+        super().__init__()
+        from collections import OrderedDict
+        cfg = self.CFG[depth]
+        self.features = nn.Sequential(OrderedDict([('conv0', nn.Conv2d(3, self.INIT, kernel_size=7, stride=2, padding=3, bias=False)),
+                                                   ('norm0', nn.BatchNorm2d(self.INIT)), ('relu0', nn.ReLU(inplace=True)),
+                                                   ('pool0', nn.MaxPool2d(kernel_size=3, stride=2, padding=1))]))
+        n = self.INIT
+        self.widths = []
+        for i, layers in enumerate(cfg):
+            self.features.add_module('denseblock%d' % (i + 1), _DenseBlock(layers, n, self.BN_SIZE, self.GROWTH, 0))
+            n += layers * self.GROWTH
+            self.widths.append(n)
+            if i != len(cfg) - 1:
+                self.features.add_module('transition%d' % (i + 1), _Transition(n, n // 2))
+                n //= 2
+        self.features.add_module('norm5', nn.BatchNorm2d(n))
+        self.last_linear = nn.Linear(n, num_classes)
+
+
+class DenseNetEncoders(EmitOnly):
+    BUILT = (121,)
+
+    def __init__(self, encoder_depth, pretrained=False, pool0=False):
+        super().__init__()
+        if encoder_depth == 161:
+            raise NotImplementedError('DenseNetEncoders: depth 161 (growth 48, 96 initial features) is not built; 121 is')
+        if encoder_depth in DenseNet.CFG and encoder_depth not in self.BUILT:
+            # the encoders themselves share every shape class with 121; the U-Net's decoder is enc[3] // 8 = 208 / 240 channels wide, and
+            # the first layer that refuses that is dec5's scSE block: salt_scse takes power-of-two widths only (csrc/se.hip)
+            d = {169: 208, 201: 240}[encoder_depth]
+            raise NotImplementedError('DenseNetEncoders: depth %d is not built: the decoder is %d channels wide and dec5.channel_se / spatial_se '
+                                      '(salt_scse) refuses it: C=%d must be a power of two' % (encoder_depth, d, d))
+        if encoder_depth not in DenseNet.CFG:
+            raise NotImplementedError('only 121, 161, 169, 201 version of Densenet are implemented')
+        if pretrained:
+            raise SaltError('pretrained ImageNet weights need a download; load a state_dict instead')
+        if pool0:
+            raise SaltError('DenseNetEncoders: pool0=True is not built')
+        self.pool0 = False
+        self.encoder = DenseNet(encoder_depth)
+        f = self.encoder.features
+        self.conv1 = nn.Sequential(f.conv0, f.norm0, f.relu0)
+        self.encoder2 = f.denseblock1
+        self.transition1 = f.transition1
+        self.encoder3 = f.denseblock2
+        self.transition2 = f.transition2
+        self.encoder4 = f.denseblock3
+        self.transition3 = f.transition3
+        self.encoder5 = f.denseblock4
+
+
 # ----------------------------------------------------------------------------- whole networks
 class HipNetwork(nn.Module):
     """Base of the callable networks: owns the Engine, dispatches forward to the compiled HIP program."""
@@ -535,11 +645,12 @@ class UNetResNet(HipNetwork):
         # F.dropout2d defaults to training=False - the call is an identity for every p there, and the registry passes p = 0 anyway
         self.num_classes, self.dropout_2d, self.use_hypercolumn = num_classes, dropout_2d, use_hypercolumn
         self.encoders, b = self._make_encoders(encoder_depth, pretrained, pool0)
-        self.center = nn.Sequential(Conv2dBnRelu(b, b), Conv2dBnRelu(b, b // 2), nn.AvgPool2d(kernel_size=2, stride=2))
-        self.dec5 = DecoderBlock(b + b // 2, b, b // 8)
-        self.dec4 = DecoderBlock(b // 2 + b // 8, b // 2, b // 8)
-        self.dec3 = DecoderBlock(b // 4 + b // 8, b // 4, b // 8)
-        self.dec2 = DecoderBlock(b // 8 + b // 8, b // 8, b // 8)
+        e = self._encoder_widths(b)
+        self.center = nn.Sequential(Conv2dBnRelu(b, b), Conv2dBnRelu(b, e[2]), nn.AvgPool2d(kernel_size=2, stride=2))
+        self.dec5 = DecoderBlock(b + e[2], b, b // 8)
+        self.dec4 = DecoderBlock(e[2] + b // 8, b // 2, b // 8)
+        self.dec3 = DecoderBlock(e[1] + b // 8, b // 4, b // 8)
+        self.dec2 = DecoderBlock(e[0] + b // 8, b // 8, b // 8)
         self.dec1 = DecoderBlock(b // 8, b // 16, b // 8)
         self.final = nn.Sequential(Conv2dBnRelu((5 if use_hypercolumn else 1) * b // 8, b // 8),
                                    nn.Conv2d(b // 8, num_classes, kernel_size=1, padding=0))
@@ -548,6 +659,21 @@ class UNetResNet(HipNetwork):
     def _make_encoders(self, encoder_depth, pretrained, pool0):
         """Hook: -> (the encoders module, bottom_channel_nr).  UNetSeResNet builds SeResNetEncoders here."""
         return ResNetEncoders(encoder_depth, pretrained=pretrained, pool0=pool0), 512 if encoder_depth in (18, 34) else 2048
+
+    def _encoder_widths(self, b):
+        """Hook: the channels of encoder2 .. encoder5 (the last one is the bottom width ``b``).  The ResNet families halve them level by
+        level; UNetDenseNet returns the reference's encoder_channel_nr."""
+        return [b // 8, b // 4, b // 2, b]
+
+    def _emit_encoders(self, g, c1, slots):
+        """Hook: emit encoder2 .. encoder5 behind the stem output ``c1``, each straight into its slot of the decoder's concatenation
+        buffers."""
+        enc = self.encoders.encoder
+        e2 = emit_blocks(g, enc.layer1, c1, out=slots[0])
+        e3 = emit_blocks(g, enc.layer2, e2, out=slots[1])
+        e4 = emit_blocks(g, enc.layer3, e3, out=slots[2])
+        e5 = emit_blocks(g, enc.layer4, e4, out=slots[3])
+        return e2, e3, e4, e5
 
     def _stem(self):
         """Hook: the stem's (convolution, BatchNorm) inside ``self.encoders.encoder``."""
@@ -567,23 +693,19 @@ class UNetResNet(HipNetwork):
         return x
 
     def emit(self, g, x_nchw, logits):
-        enc = self.encoders.encoder
         B, _, H, W = x_nchw.shape
         b, d = self.bottom, self.bottom // 8
-        exp = 1 if b == 512 else 4
+        ew = self._encoder_widths(b)
         c1 = g.conv_first(x_nchw, *self._stem(), relu=True, name='stem')
         if self.encoders.pool0:
             c1 = g.maxpool3s2(c1, name='stem.pool')
             H, W = H // 2, W // 2                    # everything downstream runs at half the resolution
         # concat-free skips: the encoder writes each feature map straight into the decoder's input buffer
-        cat5 = g.new_act(B, H // 16, W // 16, b // 2 + b, 'cat5')                   # [up(center) | e5]
-        cat4 = g.new_act(B, H // 8, W // 8, d + 256 * exp, 'cat4')                   # [up(dec5)   | e4]
-        cat3 = g.new_act(B, H // 4, W // 4, d + 128 * exp, 'cat3')                   # [up(dec4)   | e3]
-        cat2 = g.new_act(B, H // 2, W // 2, d + 64 * exp, 'cat2')                    # [up(dec3)   | e2]
-        e2 = emit_blocks(g, enc.layer1, c1, out=cat2.slice(d, 64 * exp))
-        e3 = emit_blocks(g, enc.layer2, e2, out=cat3.slice(d, 128 * exp))
-        e4 = emit_blocks(g, enc.layer3, e3, out=cat4.slice(d, 256 * exp))
-        e5 = emit_blocks(g, enc.layer4, e4, out=cat5.slice(b // 2, 512 * exp))
+        cat5 = g.new_act(B, H // 16, W // 16, ew[2] + b, 'cat5')                    # [up(center) | e5]
+        cat4 = g.new_act(B, H // 8, W // 8, d + ew[2], 'cat4')                       # [up(dec5)   | e4]
+        cat3 = g.new_act(B, H // 4, W // 4, d + ew[1], 'cat3')                       # [up(dec4)   | e3]
+        cat2 = g.new_act(B, H // 2, W // 2, d + ew[0], 'cat2')                       # [up(dec3)   | e2]
+        e2, e3, e4, e5 = self._emit_encoders(g, c1, [cat2.slice(d, ew[0]), cat3.slice(d, ew[1]), cat4.slice(d, ew[2]), cat5.slice(ew[2], b)])
         c = self.center[1].emit(g, self.center[0].emit(g, e5))
         c = g.avgpool2(c, name='center.pool')
         # FACTORED hypercolumn (round 5; DESIGN 4, saltnet.h salt_hyper_stencil): the levels up-sampled by R >= SALT_HYPER_FACTOR (default 4;
@@ -663,6 +785,61 @@ class UNetSeResNetXt(UNetSeResNet):
 
     def _make_encoders(self, encoder_depth, pretrained, pool0):
         return SeResNetXtEncoders(encoder_depth, pretrained=pretrained, pool0=pool0), 2048
+
+
+class UNetDenseNet(UNetResNet):
+    """architectures.unet.UNetDenseNet (unet.py:238-307): UNetResNet's decoder, hypercolumn and head on DenseNet-121 encoders.  The
+    decoder widths come from the four encoder widths [256, 512, 1024, 1024] (center[1] outputs enc[2], dec5 takes enc[3] + enc[2]).
+    A dense block IS its slot of the decoder's concatenation buffer: layer l reads the prefix [0, C0 + 32 l) through Graph.dense_conv
+    (csrc/dense.hip) and its conv2 writes the slice behind it; a transition is dense_conv -> avgpool2 into the next block's first
+    channels.  In training every block keeps ONE table of batch statistics that all of its layers' norm1 and its transition share."""
+    WIDTHS = {121: [256, 512, 1024, 1024], 169: [256, 512, 1280, 1664], 201: [256, 512, 1792, 1920]}
+
+    def _make_encoders(self, encoder_depth, pretrained, pool0):
+        enc = DenseNetEncoders(encoder_depth, pretrained=pretrained, pool0=pool0)
+        self._widths = self.WIDTHS[encoder_depth]
+        assert enc.encoder.widths == self._widths
+        return enc, self._widths[3]
+
+    def _encoder_widths(self, b):
+        return list(self._widths)
+
+    def _stem(self):
+        return self.encoders.encoder.features.conv0, self.encoders.encoder.features.norm0
+
+    def dead_parameter_names(self):
+        return ['encoders.encoder.features.norm5.weight', 'encoders.encoder.features.norm5.bias',
+                'encoders.encoder.last_linear.weight', 'encoders.encoder.last_linear.bias']
+
+    @classmethod
+    def translate_keys(cls, state_dict, dotted=False):
+        """torchvision 0.2.0 (what the reference pins) registered a dense layer's modules as 'norm.1', 'conv.1', 'norm.2', 'conv.2'; current
+        torch forbids dots in module names.  -> the same state_dict under the modern names (``dotted``: the other way round)."""
+        import re
+        if dotted:
+            return {re.sub(r'(denselayer\d+)\.(norm|conv)([12])\.', r'\1.\2.\3.', k): v for k, v in state_dict.items()}
+        return {re.sub(r'(denselayer\d+)\.(norm|conv)\.([12])\.', r'\1.\2\3.', k): v for k, v in state_dict.items()}
+
+    def load_state_dict(self, state_dict, strict=True, **kw):
+        return super().load_state_dict(self.translate_keys(state_dict), strict=strict, **kw)
+
+    def _emit_encoders(self, g, c1, slots):
+        f = self.encoders.encoder.features
+        x = c1
+        for i, block in enumerate(slots):
+            c = x.C
+            if i == 0:
+                g.copy(x, block.slice(0, c))             # the stem output opens denseblock1 (one salt_add launch)
+            table = g.dense_table(block, f.norm0.eps) if g.train else None
+            if g.train:
+                g.dense_moments(block.slice(0, c), table, 0)
+            for layer in getattr(f, 'denseblock%d' % (i + 1)).children():
+                layer.emit(g, block, c, table)
+                c += layer.growth_rate
+            assert c == block.C
+            if i < 3:
+                x = getattr(f, 'transition%d' % (i + 1)).emit(g, block, table, slots[i + 1].slice(0, c // 2))
+        return slots
 
 
 class DepthChannelExcitation(EmitOnly):

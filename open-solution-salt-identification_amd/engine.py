@@ -818,9 +818,10 @@ class Graph:
         # (SUMS_CONV with PARTIALS_FILLED, SUMS_OWN under SALT_BN_FIN=0: per-tile partials in scratch, nothing to wire)
 
     # ------------------------------------------------------------------ dense convolution (+BN +ReLU +residual)
-    def conv(self, x, conv, bn=None, relu=False, res=None, out=None, replicate=False, name=''):
+    def conv(self, x, conv, bn=None, relu=False, res=None, out=None, replicate=False, name='', raw_stats=None):
         """nn.Conv2d (k in {1,3} or (k,1)/(1,k); stride 1|2; zero pad or the reference's replicate top/right pad)
-        optionally followed by BatchNorm2d, residual add and ReLU."""
+        optionally followed by BatchNorm2d, residual add and ReLU.  ``raw_stats`` (train, bn None): callable(stats, stats_cnt, nparts) -
+        the launch also reports the per-tile statistics of its raw output (a dense layer's conv2 feeds the block's statistics table)."""
         eng = self.engine
         Cout, Cin, KH, KW = conv.weight.shape
         assert Cin == x.C, (name, Cin, x.C)
@@ -874,6 +875,12 @@ class Graph:
                 if res.on_side:
                     self.join()
                 self.fwd.add('affine_act', dtype=self.dt, y=out.view(), scale=None, shift=None, res=res.view(), relu=int(relu), a=out.view())
+        elif raw_stats is not None and self.train:
+            assert res is None and not relu
+            nparts = self._conv_parts(x.view(), td, stride, out.view(), OH, OW)
+            st = dict(stats=Scratch('stats' + self._scratch_sfx, 4 * lib.salt_bn_stats_floats(nparts, Cout)), stats_cnt=Scratch('stats_cnt' + self._scratch_sfx, nparts * 4))
+            self._conv_launch(self.fwd, x.view(), pk.data_ptr(), td, stride, pad_mode, out.view(), OH, OW, bias=bias, relu=0, **st)
+            raw_stats(st['stats'], st['stats_cnt'], nparts)
         else:
             assert res is None
             self._conv_launch(self.fwd, x.view(), pk.data_ptr(), td, stride, pad_mode, out.view(), OH, OW, bias=bias, relu=int(relu))
@@ -1421,6 +1428,122 @@ class Graph:
                          grad=self._gp(conv.weight), accumulate=0, **wg)
             acc = x.grad_state()
             self.bwd.add('gconv_dgrad', dy=y.gview(), dx=x.gview(), accumulate=acc, **common)
+        self.tape.append(backward)
+        return out
+
+    # ------------------------------------------------------------------ DenseNet: pre-activated 1x1 convolution on a shared statistics table
+    def dense_table(self, block, eps=1e-5):
+        """The statistics table of a dense block (train mode): batch mean / invstd / unbiased variance of every channel of the
+        concatenation buffer ``block``, filled once when the channels are produced (dense_table_fill) and read by every later layer's
+        norm1 and by the transition's norm (saltnet.h: salt_dense_bn_prep)."""
+        t = {k: self.f32(block.C) for k in ('mean', 'invstd', 'unb', 'rm', 'scale', 'shift', 'zeros', 'ones')}
+        t['ones'].fill_(1.0)
+        t['block'], t['eps'] = block, eps
+        return t
+
+    def dense_table_fill(self, table, c0, C, stats, cnt, nparts):
+        """per-tile partials of channels [c0, c0 + C) of the block -> the table's rows: salt_bn_finalize with gamma 1, beta 0 and
+        momentum 1 (running_var <- the unbiased variance itself)"""
+        o = 4 * c0
+        p = lambda k: table[k].data_ptr() + o
+        self.fwd.add('bn_finalize', stats=stats, stats_cnt=cnt, nparts=nparts, C=C, gamma=p('ones'), beta=p('zeros'), running_mean=p('rm'),
+                     running_var=p('unb'), num_batches_tracked=None, momentum=1.0, eps=table['eps'], mean=p('mean'), invstd=p('invstd'),
+                     scale=p('scale'), shift=p('shift'))
+
+    def dense_moments(self, x, table, c0):
+        """train: the statistics of the STORED channels ``x`` = [c0, c0 + x.C) of the block (stem output / pooled transition output)"""
+        S = fill(STRUCTS['salt_dense_moments_args'](), dtype=self.dt, x=shaped_view(1, x.B, x.H, x.W, x.C))
+        nparts = lib.salt_dense_moments_parts(ctypes.byref(S))
+        if nparts < 1:
+            raise SaltError('dense_moments: %s' % lib.salt_last_error().decode(errors='replace'))
+        stats = Scratch('stats' + self._scratch_sfx, 4 * lib.salt_bn_stats_floats(nparts, x.C))
+        cnt = Scratch('stats_cnt' + self._scratch_sfx, nparts * 4)
+        if x.on_side and self.fwd.default_stream == 0:
+            self.join()
+        self.fwd.add('dense_moments', dtype=self.dt, x=x.view(), stats=stats, stats_cnt=cnt)
+        self.dense_table_fill(table, c0, x.C, stats, cnt, nparts)
+
+    def dense_conv(self, x, bn_in, conv, bn_out=None, relu=None, out=None, table=None, name=''):
+        """conv(relu(bn_in(x))) with a bias-free 1x1 ``conv``, optionally followed by bn_out (+ReLU): conv1 of a DenseNet layer (bn_out =
+        norm2) or a transition (bn_out None).  ``x`` is a channel prefix of the block's concatenation buffer; relu(bn_in(x)) is never
+        stored (salt_dense_conv, csrc/dense.hip, reads the fp32 master weight: nothing to pack or refresh).
+        eval: ONE launch, bn_in folded into the loader transform, bn_out into the epilogue.
+        train: ``table`` (dense_table) holds the batch statistics of x's channels; salt_dense_bn_prep derives this layer's in_scale /
+        in_shift and updates ITS running statistics; the launch stores the raw output with per-tile statistics partials and the usual
+        bn_finalize + affine_act follow (_bn_behind).  Backward: bn_out's backward, the weight gradient on the weight-gradient
+        stream, and the data gradient with bn_in's backward inside (dgamma / dbeta of bn_in included) into x's gradient."""
+        eng = self.engine
+        Cout, Cin = conv.weight.shape[0], conv.weight.shape[1]
+        relu = (bn_out is not None) if relu is None else relu
+        if tuple(conv.weight.shape[2:]) != (1, 1) or conv.bias is not None or tuple(conv.stride) != (1, 1) or tuple(conv.padding) != (0, 0) \
+                or Cin != x.C or bn_in.num_features != Cin or (bn_out is not None and bn_out.num_features != Cout):
+            raise SaltError('dense_conv %s: weight %s on %d channels (a bias-free unit-step 1x1 behind a BatchNorm of its input is expected)'
+                            % (name, tuple(conv.weight.shape), x.C))
+        S = fill(STRUCTS['salt_dense_conv_args'](), dtype=self.dt, x=shaped_view(1, x.B, x.H, x.W, Cin), y=shaped_view(1, x.B, x.H, x.W, Cout))
+        nparts = lib.salt_dense_conv_stats_parts(ctypes.byref(S))
+        if nparts < 1:
+            raise SaltError('dense_conv %s: %s' % (name, lib.salt_last_error().decode(errors='replace')))
+        if out is None:
+            out = self.new_act(x.B, x.H, x.W, Cout, name)
+        if (out.B, out.H, out.W, out.C) != (x.B, x.H, x.W, Cout):
+            raise SaltError('dense_conv %s: output %s does not fit %s' % (name, (out.B, out.H, out.W, out.C), (x.B, x.H, x.W, Cout)))
+        w1 = eng.bn_work(bn_in)
+        tr = dict(in_scale=w1['scale'].data_ptr(), in_shift=w1['shift'].data_ptr())
+        # the kernels read these vectors 16 bytes at a time.  Engine._flatten starts every live parameter on a multiple of 4 floats of the
+        # flat buffer and the work vectors are allocations of their own, so this holds by construction; a parameter that is not in the
+        # flat buffer (a dead or frozen one) need not be - refuse it here, not at run time
+        for what, t in (('conv.weight', conv.weight), ('bn_in.weight', bn_in.weight), ('bn_in.bias', bn_in.bias)):
+            if t.data_ptr() % 16:
+                raise SaltError('dense_conv %s: %s is not 16-byte aligned' % (name, what))
+        common = dict(dtype=self.dt, w=conv.weight.data_ptr(), **tr)
+        if x.on_side and self.fwd.default_stream == 0:
+            self.join()
+        if not self.train:
+            ep = {}
+            if bn_out is not None:
+                w2 = eng.bn_work(bn_out)
+                ep = dict(scale=w2['scale'].data_ptr(), shift=w2['shift'].data_ptr())
+            self.fwd.add('dense_conv', x=x.view(), y=out.view(), relu=int(relu), **ep, **common)
+            out.on_side = self.fwd.default_stream == 1
+            return out
+        if table is None or x.buf is not table['block'].buf or x.c0 != table['block'].c0 or x.C > table['block'].C:
+            raise SaltError('dense_conv %s: train mode needs the statistics table of the block x is a prefix of' % name)
+        if bn_in.eps != table['eps']:
+            raise SaltError('dense_conv %s: BatchNorm eps %g, the block statistics table was built with %g' % (name, bn_in.eps, table['eps']))
+        if bn_in.momentum is None:
+            raise SaltError('dense_conv %s: momentum=None (cumulative averaging) is not built' % name)
+        if bn_out is None and relu:
+            raise SaltError('dense_conv %s: a ReLU without a BatchNorm behind the convolution is not on the reference path' % name)
+        nbt = bn_in.num_batches_tracked.data_ptr() if bn_in.num_batches_tracked is not None else None
+        self.fwd.add('dense_bn_prep', C=Cin, mean=table['mean'].data_ptr(), invstd=table['invstd'].data_ptr(), unbiased_var=table['unb'].data_ptr(),
+                     gamma=bn_in.weight.data_ptr(), beta=bn_in.bias.data_ptr(), running_mean=bn_in.running_mean.data_ptr(),
+                     running_var=bn_in.running_var.data_ptr(), num_batches_tracked=nbt, momentum=bn_in.momentum, **tr)
+        w2 = None
+        if bn_out is not None:
+            y = self.new_act(x.B, x.H, x.W, Cout, name + '.y')
+            # (the kernel knows the per-tile partials protocol only)
+            w2, _ = self._bn_behind(lambda **st: self.fwd.add('dense_conv', x=x.view(), y=y.view(), **st, **common), False, nparts, y, bn_out, relu,
+                                    None, out, self._scratch_sfx)
+        else:
+            y = out
+            self.fwd.add('dense_conv', x=x.view(), y=out.view(), relu=0, **common)
+        out.on_side = self.fwd.default_stream == 1
+
+        def backward():
+            if bn_out is not None:
+                self._bn_train_bwd(y, bn_out, relu, None, out, w2)
+            wg = dict(dtype=self.dt, x=x.view(), dy=y.gview(), **tr)
+            ns = lib.salt_dense_conv_wgrad_parts(ctypes.byref(fill(STRUCTS['salt_dense_conv_wgrad_args'](), **wg)))
+            if ns < 1:
+                raise SaltError('dense_conv %s: weight-gradient plan failed: %s' % (name, lib.salt_last_error().decode(errors='replace')))
+            self.bwd.add('dense_conv_wgrad', stream=1, partials=Scratch('dense_wgrad', ns * Cout * Cin * 4), nsplit=ns, grad=self._gp(conv.weight),
+                         accumulate=0, **wg)
+            acc = x.grad_state()
+            # g is recomputed by the apply pass, not stashed: the only workspaces are the per-tile sums, shared by every layer
+            self.bwd.add('dense_conv_dgrad', dy=y.gview(), x=x.view(), mean=table['mean'].data_ptr(), invstd=table['invstd'].data_ptr(),
+                         gamma=bn_in.weight.data_ptr(), partials=Scratch('dense_dgrad', nparts * 2 * Cin * 4), nparts=nparts,
+                         sums=Scratch('dense_sums', 2 * Cin * 4), dgamma=self._gp(bn_in.weight), dbeta=self._gp(bn_in.bias), accumulate_param_grads=0,
+                         dx=x.gview(), accumulate=acc, **common)
         self.tape.append(backward)
         return out
 

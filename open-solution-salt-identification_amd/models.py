@@ -38,6 +38,10 @@ ARCHITECTURES = {
     'UNetSeResNetXt': {'model': A.UNetSeResNetXt,
                        'model_config': {'encoder_depth': 50, 'use_hypercolumn': True, 'dropout_2d': 0.0, 'pretrained': False, 'pool0': False},
                        'init_weights': False},
+    # models.py:30-34 with `pretrained` off: DenseNet-121 encoders (csrc/dense.hip)
+    'UNetDenseNet': {'model': A.UNetDenseNet,
+                     'model_config': {'encoder_depth': 121, 'use_hypercolumn': True, 'dropout_2d': 0.0, 'pretrained': False, 'pool0': False},
+                     'init_weights': False},
     # unet_models.py zoo (named by BASELINE.json's north_star; not wired into the reference's registry)
     'TernausUNetResNet': {'model': A.TernausUNetResNet,
                           'model_config': {'encoder_depth': 34, 'num_filters': 32, 'dropout_2d': 0.0, 'pretrained': False, 'is_deconv': True},
