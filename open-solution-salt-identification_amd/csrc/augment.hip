@@ -400,7 +400,5 @@ extern "C" int salt_augment_preprocess(const salt_augment_preprocess_args* a, vo
     }
     p.cfg = c; p.seed = a->seed; p.counter = a->counter; p.params = a->params; p.params_given = a->params_given;
     p.geo_img = a->geo_img; p.geo_mask = a->geo_mask; p.gray = a->gray;
-    hipLaunchKernelGGL(augment_kernel, dim3(a->B), dim3(NT), 0, (hipStream_t)stream, p);
-    SALT_CHECK_LAUNCH();
-    return SALT_OK;
+    return salt_launch(augment_kernel, dim3(a->B), dim3(NT), 0, (hipStream_t)stream, p);
 }

@@ -16,19 +16,6 @@ constexpr int POOL = 8;                 // nn.AvgPool2d(8): window side, window 
 constexpr int NPIX = POOL * POOL;
 constexpr int KMAX = 8;
 
-// 16-byte pieces when the channel run allows it (VEC), single elements otherwise (odd C, unaligned slices)
-template <typename T, bool VEC> struct Piece;
-template <typename T> struct Piece<T, true> {
-    static constexpr int N = Elem<T>::VE;
-    static __device__ __forceinline__ void ld(const T* p, float* f) { unpack16<T>(*reinterpret_cast<const u32x4*>(p), f); }
-    static __device__ __forceinline__ void st(T* p, const float* f) { *reinterpret_cast<u32x4*>(p) = pack16<T>(f); }
-};
-template <typename T> struct Piece<T, false> {
-    static constexpr int N = 1;
-    static __device__ __forceinline__ void ld(const T* p, float* f) { f[0] = Elem<T>::ld(p); }
-    static __device__ __forceinline__ void st(T* p, const float* f) { Elem<T>::st(p, f[0]); }
-};
-
 // One workgroup per window (b, oh, ow).  `lanes` = min(C / N, 256) threads share a pixel (consecutive 16-byte pieces), 256 / lanes pixel
 // rows walk the 64 pixels; the rows' partial sums meet in LDS in ascending row order, then every thread owns channels c = tid, tid + 256,
 // ...: pooled value, K partial dot products, wave shuffles, one LDS step.
@@ -189,11 +176,6 @@ __global__ __launch_bounds__(256) void pool_head_bwd_kernel(salt_view dx, const 
     }
 }
 
-template <typename T> bool piece_vec(const salt_view& v) {
-    constexpr int VE = Elem<T>::VE;
-    return v.C % VE == 0 && v.cs % VE == 0 && ((uintptr_t)v.p & 15) == 0;
-}
-
 // LDS of the forward kernel: [R][C] doubles, R C <= 256 N when C / N < 256, one row otherwise
 size_t pool_lds(int C, int N) {
     const int cpv = C / N, lanes = cpv < 256 ? cpv : 256;
@@ -212,14 +194,12 @@ extern "C" int salt_pool_head(const salt_pool_head_args* a, void* stream) {
     const dim3 grid(a->x.B * OH * OW);
     hipStream_t st = (hipStream_t)stream;
     SALT_DISPATCH_DTYPE(a->dtype, T, {
-        const bool vec = piece_vec<T>(a->x);
+        const bool vec = view_vec(a->x, Elem<T>::VE);
         const size_t lds = pool_lds(a->x.C, vec ? Elem<T>::VE : 1);
         if (lds > 48 * 1024) SALT_FAIL(SALT_E_UNSUPPORTED, "pool_head: %d channels", a->x.C);
-        if (vec) hipLaunchKernelGGL((pool_head_kernel<T, true>), grid, dim3(256), lds, st, a->x, a->w, a->bias, a->K, OH, OW, a->logits_nchw, a->pooled);
-        else hipLaunchKernelGGL((pool_head_kernel<T, false>), grid, dim3(256), lds, st, a->x, a->w, a->bias, a->K, OH, OW, a->logits_nchw, a->pooled);
+        if (vec) return salt_launch(pool_head_kernel<T, true>, grid, dim3(256), lds, st, a->x, a->w, a->bias, a->K, OH, OW, a->logits_nchw, a->pooled);
+        return salt_launch(pool_head_kernel<T, false>, grid, dim3(256), lds, st, a->x, a->w, a->bias, a->K, OH, OW, a->logits_nchw, a->pooled);
     });
-    SALT_CHECK_LAUNCH();
-    return SALT_OK;
 }
 
 extern "C" int salt_pool_head_bwd(const salt_pool_head_bwd_args* a, void* stream) {
@@ -230,7 +210,7 @@ extern "C" int salt_pool_head_bwd(const salt_pool_head_bwd_args* a, void* stream
     if ((int64_t)v.B * OH * OW > 0x3fffffffLL) SALT_FAIL(SALT_E_BADARG, "pool_head_bwd: too many windows");
     hipStream_t st = (hipStream_t)stream;
     SALT_DISPATCH_DTYPE(a->dtype, T, {
-        const bool vec = v.p && piece_vec<T>(v);
+        const bool vec = v.p && view_vec(v, Elem<T>::VE);
         const int N = vec ? Elem<T>::VE : 1;
         const int nwin = v.p ? v.B * OH * OW : 0;
         const int64_t edge_units = (int64_t)(v.H * v.W - OH * OW * NPIX) * (v.C / N);
@@ -238,11 +218,9 @@ extern "C" int salt_pool_head_bwd(const salt_pool_head_bwd_args* a, void* stream
         if (v.p && !a->accumulate && edge_units > 0) per_image = (int)(edge_units < 64 * 256 ? (edge_units + 255) / 256 : 64);
         const int nedge = per_image * v.B, ngw = cdiv(v.C, 256);
         const dim3 grid(nwin + nedge + ngw + 1);
-        if (vec) hipLaunchKernelGGL((pool_head_bwd_kernel<T, true>), grid, dim3(256), 0, st, v, a->w, a->K, OH, OW, a->dlogits_nchw, a->pooled,
+        if (vec) return salt_launch(pool_head_bwd_kernel<T, true>, grid, dim3(256), 0, st, v, a->w, a->K, OH, OW, a->dlogits_nchw, a->pooled,
                                     a->accumulate, a->gw, a->gb, nwin, nedge, per_image, ngw);
-        else hipLaunchKernelGGL((pool_head_bwd_kernel<T, false>), grid, dim3(256), 0, st, v, a->w, a->K, OH, OW, a->dlogits_nchw, a->pooled,
-                                a->accumulate, a->gw, a->gb, nwin, nedge, per_image, ngw);
+        return salt_launch(pool_head_bwd_kernel<T, false>, grid, dim3(256), 0, st, v, a->w, a->K, OH, OW, a->dlogits_nchw, a->pooled,
+                           a->accumulate, a->gw, a->gb, nwin, nedge, per_image, ngw);
     });
-    SALT_CHECK_LAUNCH();
-    return SALT_OK;
 }

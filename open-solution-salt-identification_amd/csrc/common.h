@@ -1,6 +1,7 @@
 // common.h — shared device/host helpers for libsaltnet_hip (gfx950 only).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <hip/hip_ext.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -58,6 +59,55 @@ template <> __device__ __forceinline__ u32x4 pack16<bf16_t>(const float* f) {
     return v;
 }
 
+// One 16-byte piece (VEC) or one element (!VEC) of a pixel's channel run, as floats: the streaming kernels take 16-byte pieces when
+// the views allow it (view_vec below) and single elements otherwise (odd channel counts, unaligned slices)
+template <typename T, bool VEC> struct Piece;
+template <typename T> struct Piece<T, true> {
+    static constexpr int N = Elem<T>::VE;
+    static __device__ __forceinline__ void ld(const T* p, float* f) { unpack16<T>(*reinterpret_cast<const u32x4*>(p), f); }
+    static __device__ __forceinline__ void st(T* p, const float* f) { *reinterpret_cast<u32x4*>(p) = pack16<T>(f); }
+};
+template <typename T> struct Piece<T, false> {
+    static constexpr int N = 1;
+    static __device__ __forceinline__ void ld(const T* p, float* f) { f[0] = Elem<T>::ld(p); }
+    static __device__ __forceinline__ void st(T* p, const float* f) { Elem<T>::st(p, f[0]); }
+};
+
+// One 16-byte k-step of a 32x32 accumulator (conv_mfma.hip, dense.hip): bf16 one 32x32x16 MFMA, f32 four exact-f32 32x32x2 MFMAs
+template <typename T> struct Mma;
+template <> struct Mma<float> {
+    static __device__ __forceinline__ void step(const u32x4& a, const u32x4& b, f32x16& c) {
+        c = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(a.x), __uint_as_float(b.x), c, 0, 0, 0);
+        c = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(a.y), __uint_as_float(b.y), c, 0, 0, 0);
+        c = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(a.z), __uint_as_float(b.z), c, 0, 0, 0);
+        c = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(a.w), __uint_as_float(b.w), c, 0, 0, 0);
+    }
+};
+template <> struct Mma<bf16_t> {
+    static __device__ __forceinline__ void step(const u32x4& a, const u32x4& b, f32x16& c) {
+        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
+    }
+};
+
+// byte address of 16-byte slot `slot` of 64-byte LDS row `row`, XOR-swizzled (conflict-free ds_read_b128 fragment reads)
+__device__ __forceinline__ int swz64(int row, int slot) { return row * 64 + (((slot ^ (row >> 2)) & 3) << 4); }
+
+// 16 zero bytes in device memory: a masked-out piece of a branch-free loader reads them instead of zero-initialising its
+// destination registers under a branch (see conv_wgrad_fast_kernel in conv_wgrad.hip).  static: the library is built without
+// relocatable device code, every translation unit that reads it carries its own copy
+static __device__ __attribute__((aligned(16))) unsigned int g_zero_piece[4] = {0u, 0u, 0u, 0u};
+
+// split-K weight gradients (conv_group.hip, dense.hip): the nsplit fp32 slabs summed in ascending order.  A template, so that only the
+// translation units that launch it carry a copy
+template <int = 0>
+__global__ __launch_bounds__(256) void slab_sum_kernel(const float* partials, int nsplit, int total, float* grad, int accumulate) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    float s = partials[i];
+    for (int k = 1; k < nsplit; ++k) s += partials[(int64_t)k * total + i];
+    grad[i] = accumulate ? grad[i] + s : s;
+}
+
 // 16-byte piece load from global with channel-tail / alignment handling (conv_mfma.hip, conv_wgrad.hip).
 template <typename T>
 __device__ __forceinline__ u32x4 load_piece(const T* base, int64_t off, int ch0, int C, bool vec_ok) {
@@ -111,6 +161,7 @@ void salt_set_error(const char* fmt, ...);
 // kernel's own completion signal orders the side stream and no marker packet is queued behind the kernel.
 hipEvent_t salt_take_fork_event();
 #define SALT_FAIL(code, ...) do { salt_set_error(__VA_ARGS__); return (code); } while (0)
+#define SALT_TRY(call) do { const int rc_ = (call); if (rc_) return rc_; } while (0)      // a non-zero code of `call` leaves the entry point
 #define SALT_CHECK_LAUNCH() do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) { \
     salt_set_error("%s:%d launch failed: %s", __FILE__, __LINE__, hipGetErrorString(e_)); return (int)e_; } } while (0)
 
@@ -168,7 +219,12 @@ static inline int salt_raise_lds_limit(const void* kern) {
         if (k == kern) return 0;
         if (!k) { free_slot = &slot; break; }
     }
-    hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    // The CU's 160 KB hold the kernel's static LDS too: a request for 160 KB of dynamic LDS is rejected (invalid argument) for a kernel
+    // that also declares __shared__ arrays.  lovasz_pass_kernel (loss.hip) is the one such kernel above 64 KB; for every kernel
+    // without static LDS the request is the 160 KB it always was.
+    hipFuncAttributes fa;
+    hipError_t e = hipFuncGetAttributes(&fa, kern);
+    if (e == hipSuccess) e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - (int)fa.sharedSizeBytes);
     if (e != hipSuccess) SALT_FAIL((int)e, "hipFuncSetAttribute: %s", hipGetErrorString(e));
     const void* none = nullptr;
     if (free_slot) free_slot->compare_exchange_strong(none, kern, std::memory_order_release, std::memory_order_relaxed);
@@ -178,6 +234,16 @@ template <typename... Params, typename... Args>
 static inline int salt_launch(void (*kern)(Params...), dim3 grid, dim3 block, size_t lds, hipStream_t st, const Args&... args) {
     if (lds > 64 * 1024) { const int rc = salt_raise_lds_limit(reinterpret_cast<const void*>(kern)); if (rc) return rc; }
     hipLaunchKernelGGL(kern, grid, block, lds, st, args...);
+    SALT_CHECK_LAUNCH();
+    return 0;
+}
+// Fork hand-off sites (salt_take_fork_event): a non-null `ev` is bound to the launch's completion signal as its stop event; a null
+// `ev` is the plain launch.
+template <typename... Params, typename... Args>
+static inline int salt_launch_ev(void (*kern)(Params...), dim3 grid, dim3 block, size_t lds, hipStream_t st, hipEvent_t ev, const Args&... args) {
+    if (!ev) return salt_launch(kern, grid, block, lds, st, args...);
+    if (lds > 64 * 1024) { const int rc = salt_raise_lds_limit(reinterpret_cast<const void*>(kern)); if (rc) return rc; }
+    hipExtLaunchKernelGGL(kern, grid, block, lds, st, nullptr, ev, 0, args...);
     SALT_CHECK_LAUNCH();
     return 0;
 }
@@ -197,6 +263,17 @@ static inline int ilog2_ceil(int v) { int l = 0; while ((1 << l) < v) ++l; retur
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 static inline bool view_ok(const salt_view& v) { return v.p && v.B > 0 && v.H > 0 && v.W > 0 && v.C > 0 && v.cs >= v.C; }
 static inline int64_t view_pixels(const salt_view& v) { return (int64_t)v.B * v.H * v.W; }
+__host__ __device__ static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+template <typename... P> static inline bool aligned16(const void* p, const P*... more) { return aligned16(p) && aligned16(more...); }
+// can v be read / written 16 bytes (ve elements) at a time?
+static inline bool view_vec(const salt_view& v, int ve) { return v.C % ve == 0 && v.cs % ve == 0 && aligned16(v.p); }
+// v must be a 16-byte addressable [B,H,W,C] view of `dtype`
+static inline int view_check16(const char* op, const char* what, const salt_view& v, int dtype, int B, int H, int W, int C) {
+    const int ve = dtype == SALT_F32 ? 4 : 8;
+    if (!view_ok(v) || v.B != B || v.H != H || v.W != W || v.C != C || (v.cs % ve) || !aligned16(v.p))
+        SALT_FAIL(SALT_E_BADARG, "%s: %s must be a 16-byte aligned [%d,%d,%d,%d] view with cs a multiple of %d", op, what, B, H, W, C, ve);
+    return SALT_OK;
+}
 
 // generic dtype dispatch
 #define SALT_DISPATCH_DTYPE(dtype, T, ...) \

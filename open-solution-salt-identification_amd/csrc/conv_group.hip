@@ -12,7 +12,7 @@
 //                  about the tile mean, count: fixed order) or as fp64 shard adds without a ticket.  dgrad: dx (+)= v.
 //   gconv_wgrad    a workgroup owns (pixel split, 32-channel block); 256 threads = 8 Cg (channel, 4 inputs) quads x 32 / Cg pixel
 //                  sub-sets, 36 accumulators each; the sub-sets meet in LDS in ascending order, the split's slab goes out in the
-//                  reference layout, and gconv_wgrad_reduce adds the slabs in ascending split order.
+//                  reference layout, and slab_sum_kernel (common.h) adds the slabs in ascending split order.
 #include "common.h"
 
 namespace {
@@ -282,14 +282,6 @@ __global__ __launch_bounds__(256) void gconv_wgrad_kernel(GwKP p) {
     }
 }
 
-__global__ __launch_bounds__(256) void gconv_wgrad_reduce_kernel(const float* partials, int nsplit, int total, float* grad, int accumulate) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= total) return;
-    float s = partials[i];
-    for (int k = 1; k < nsplit; ++k) s += partials[(int64_t)k * total + i];
-    grad[i] = accumulate ? grad[i] + s : s;
-}
-
 // ---------------------------------------------------------------- host
 int gconv_shape_check(const char* op, const salt_view& x, int groups, int stride) {
     if (groups != 32) SALT_FAIL(SALT_E_UNSUPPORTED, "%s: %d groups (supported: 32)", op, groups);
@@ -300,13 +292,6 @@ int gconv_shape_check(const char* op, const salt_view& x, int groups, int stride
     return SALT_OK;
 }
 inline int out_size(int n, int stride) { return (n - 1) / stride + 1; }
-
-int gconv_view_check(const char* op, const char* what, const salt_view& v, int dtype, int B, int H, int W, int C) {
-    const int ve = dtype == SALT_F32 ? 4 : 8;
-    if (!view_ok(v) || v.B != B || v.H != H || v.W != W || v.C != C || (v.cs % ve) || (reinterpret_cast<uintptr_t>(v.p) & 15))
-        SALT_FAIL(SALT_E_BADARG, "%s: %s must be a 16-byte aligned [%d,%d,%d,%d] view with cs a multiple of %d", op, what, B, H, W, C, ve);
-    return SALT_OK;
-}
 
 template <typename T, int CG>
 int gconv_launch_cg(int mode, const GconvKP& p, hipStream_t st) {
@@ -381,8 +366,8 @@ extern "C" int salt_gconv(const salt_gconv_args* a, void* stream) {
     if (rc) return rc;
     if (a->dtype != SALT_F32 && a->dtype != SALT_BF16) SALT_FAIL(SALT_E_BADARG, "gconv: bad dtype %d", a->dtype);
     const int OH = out_size(a->x.H, a->stride), OW = out_size(a->x.W, a->stride);
-    if ((rc = gconv_view_check("gconv", "x", a->x, a->dtype, a->x.B, a->x.H, a->x.W, a->x.C))) return rc;
-    if ((rc = gconv_view_check("gconv", "y", a->y, a->dtype, a->x.B, OH, OW, a->x.C))) return rc;
+    if ((rc = view_check16("gconv", "x", a->x, a->dtype, a->x.B, a->x.H, a->x.W, a->x.C))) return rc;
+    if ((rc = view_check16("gconv", "y", a->y, a->dtype, a->x.B, OH, OW, a->x.C))) return rc;
     if (!a->w) SALT_FAIL(SALT_E_BADARG, "gconv: w");
     if ((a->scale == nullptr) != (a->shift == nullptr)) SALT_FAIL(SALT_E_BADARG, "gconv: scale/shift");
     if (a->stats && a->fin_acc) SALT_FAIL(SALT_E_BADARG, "gconv: statistics go to the partials or to the shards, not both");
@@ -402,8 +387,8 @@ extern "C" int salt_gconv_dgrad(const salt_gconv_dgrad_args* a, void* stream) {
     if (rc) return rc;
     if (a->dtype != SALT_F32 && a->dtype != SALT_BF16) SALT_FAIL(SALT_E_BADARG, "gconv_dgrad: bad dtype %d", a->dtype);
     const int OH = out_size(a->dx.H, a->stride), OW = out_size(a->dx.W, a->stride);
-    if ((rc = gconv_view_check("gconv_dgrad", "dx", a->dx, a->dtype, a->dx.B, a->dx.H, a->dx.W, a->dx.C))) return rc;
-    if ((rc = gconv_view_check("gconv_dgrad", "dy", a->dy, a->dtype, a->dx.B, OH, OW, a->dx.C))) return rc;
+    if ((rc = view_check16("gconv_dgrad", "dx", a->dx, a->dtype, a->dx.B, a->dx.H, a->dx.W, a->dx.C))) return rc;
+    if ((rc = view_check16("gconv_dgrad", "dy", a->dy, a->dtype, a->dx.B, OH, OW, a->dx.C))) return rc;
     if (!a->w) SALT_FAIL(SALT_E_BADARG, "gconv_dgrad: w");
     GconvKP p;
     p.in = a->dy.p; p.out = a->dx.p; p.w = a->w; p.scale = nullptr; p.shift = nullptr; p.stats = nullptr; p.stats_cnt = nullptr; p.fin_acc = nullptr;
@@ -430,8 +415,8 @@ extern "C" int salt_gconv_wgrad(const salt_gconv_wgrad_args* a, void* stream) {
     if (rc) return rc;
     if (a->dtype != SALT_F32 && a->dtype != SALT_BF16) SALT_FAIL(SALT_E_BADARG, "gconv_wgrad: bad dtype %d", a->dtype);
     const int OH = out_size(a->x.H, a->stride), OW = out_size(a->x.W, a->stride);
-    if ((rc = gconv_view_check("gconv_wgrad", "x", a->x, a->dtype, a->x.B, a->x.H, a->x.W, a->x.C))) return rc;
-    if ((rc = gconv_view_check("gconv_wgrad", "dy", a->dy, a->dtype, a->x.B, OH, OW, a->x.C))) return rc;
+    if ((rc = view_check16("gconv_wgrad", "x", a->x, a->dtype, a->x.B, a->x.H, a->x.W, a->x.C))) return rc;
+    if ((rc = view_check16("gconv_wgrad", "dy", a->dy, a->dtype, a->x.B, OH, OW, a->x.C))) return rc;
     if (!a->partials || !a->grad) SALT_FAIL(SALT_E_BADARG, "gconv_wgrad: partials / grad");
     GwKP p; int nsplit = 0;
     p.x = a->x.p; p.dy = a->dy.p; p.partials = a->partials;
@@ -442,5 +427,5 @@ extern "C" int salt_gconv_wgrad(const salt_gconv_wgrad_args* a, void* stream) {
     SALT_DISPATCH_DTYPE(a->dtype, T, rc = gwgrad_launch<T>(a->stride, p, nsplit, st))
     if (rc) return rc;
     const int total = a->x.C * (a->x.C / 32) * 9;
-    return salt_launch(gconv_wgrad_reduce_kernel, dim3(cdiv(total, 256)), dim3(256), 0, st, (const float*)a->partials, nsplit, total, a->grad, a->accumulate ? 1 : 0);
+    return salt_launch(slab_sum_kernel<>, dim3(cdiv(total, 256)), dim3(256), 0, st, (const float*)a->partials, nsplit, total, a->grad, a->accumulate ? 1 : 0);
 }

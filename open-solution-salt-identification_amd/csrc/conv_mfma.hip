@@ -56,25 +56,6 @@ struct ConvKP {
     const float* in_scale; const float* in_shift; int in_relu, in_tab_off; BnFin in_fin;
 };
 
-template <typename T> struct Mma;
-template <> struct Mma<float> {
-    static __device__ __forceinline__ void step(const u32x4& a, const u32x4& b, f32x16& c) {
-        c = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(a.x), __uint_as_float(b.x), c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(a.y), __uint_as_float(b.y), c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(a.z), __uint_as_float(b.z), c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(a.w), __uint_as_float(b.w), c, 0, 0, 0);
-    }
-};
-template <> struct Mma<bf16_t> {
-    static __device__ __forceinline__ void step(const u32x4& a, const u32x4& b, f32x16& c) {
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-    }
-};
-
-__device__ __forceinline__ int swz_addr(int row, int slot) {        // 64-byte rows, 4 x 16-byte slots
-    return row * 64 + (((slot ^ (row >> 2)) & 3) << 4);
-}
-
 // Row m of a pixel tile -> (column, row, image) inside the tile.  Power-of-two tiles: shifts.  General tiles (gen; the fused-fold data
 // gradients of the small decoder maps: full-width strips of the 10 / 18 / 34-wide extended grid instead of 16-wide tiles that are
 // 40 - 60 % empty): two multiply-high divisions; rows past nb * th * tw belong to no pixel (bl = 2^20: fails every b0 + bl < B test).
@@ -94,10 +75,6 @@ __device__ __forceinline__ TilePix tile_pix(const ConvKP& p, int m) {
     }
     return t;
 }
-
-// 16 zero bytes in device memory: a masked-out piece of a branch-free loader reads them instead of zero-initialising its
-// destination registers under a branch (see conv_wgrad_fast_kernel in conv_wgrad.hip)
-__device__ __attribute__((aligned(16))) unsigned int g_zero_piece[4] = {0u, 0u, 0u, 0u};
 
 constexpr int MAXA = 9;     // halo pieces per thread: P_halo*4 <= 9*256 (6*256 for the 256-pixel tile: keeps its prefetch registers in budget)
 constexpr int maxa_for(int bm) { return bm >= 256 ? 6 : MAXA; }
@@ -548,12 +525,12 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(ConvKP p) {
     // not depend on the tap: byte = t*BN*64 + const.
     int b_addr[NI];
 #pragma unroll
-    for (int j = 0; j < NI; ++j) b_addr[j] = swz_addr(nrow[j], khalf);
+    for (int j = 0; j < NI; ++j) b_addr[j] = swz64(nrow[j], khalf);
     auto tap_mma = [&](int t, int toff) {
         u32x4 a0[MI], a1[MI], b0[NI], b1[NI];
 #pragma unroll
         for (int i = 0; i < MI; ++i) {
-            const int ad = swz_addr(pbase[i] + toff, khalf);
+            const int ad = swz64(pbase[i] + toff, khalf);
             a0[i] = *reinterpret_cast<const u32x4*>(sA + ad);
             a1[i] = *reinterpret_cast<const u32x4*>(sA + (ad ^ 32));
         }
@@ -581,7 +558,7 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(ConvKP p) {
 #pragma unroll
         for (int t = 0; t < NT; ++t)
 #pragma unroll
-            for (int i = 0; i < MI; ++i) a_addr[t][i] = swz_addr(pbase[i] + p.tap_off[t], khalf);
+            for (int i = 0; i < MI; ++i) a_addr[t][i] = swz64(pbase[i] + p.tap_off[t], khalf);
     }
     auto load_frag = [&](int s, Frag& f) {
         const int t = s >> 1, hx = (s & 1) << 5;
@@ -633,7 +610,7 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(ConvKP p) {
         // Piece q = tid + 256 k sits in LDS row (tid >> 2) + 64 k, slot tid & 3.  64 % 4 == 0, so the swizzle term is the same for every
         // k: LDS store address = lane constant + 4096 k.  The weight row of piece k is t * BN + n with (64 k + (tid >> 2)) = t * BN + n:
         // its global offset splits into a lane constant and a part that only depends on k (uniform) - no per-piece index math per chunk.
-        const int lds_lane = swz_addr(tid >> 2, tid & 3);
+        const int lds_lane = swz64(tid >> 2, tid & 3);
         constexpr int RPP = 64;                                     // LDS rows per 256-thread pass
         const int lrow = tid >> 2;
         int b_lane_off, b_lane_n;                                   // element offset / output channel of the lane inside a pass
@@ -742,7 +719,7 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(ConvKP p) {
                     u32x4 v = {0u, 0u, 0u, 0u};
                     const int ch0 = ch_base + (q & 3) * VE;
                     if (a_goff[k] >= 0 && ch0 < p.Cin) v = load_piece<T>(xg0, a_goff[k] + ch_base, ch0, p.Cin, x_vec);
-                    *reinterpret_cast<u32x4*>(sA + swz_addr(q >> 2, q & 3)) = v;
+                    *reinterpret_cast<u32x4*>(sA + swz64(q >> 2, q & 3)) = v;
                 }
             }
             for (int q = tid; q < nbp; q += 256) {
@@ -751,7 +728,7 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(ConvKP p) {
                 u32x4 v = {0u, 0u, 0u, 0u};
                 if (n0 + n < p.Cout)
                     v = *reinterpret_cast<const u32x4*>(wg + (((int64_t)c * p.ntaps + t) * p.Cout + n0 + n) * KCE + (q & 3) * VE);
-                *reinterpret_cast<u32x4*>(sB + swz_addr(row, q & 3)) = v;
+                *reinterpret_cast<u32x4*>(sB + swz64(row, q & 3)) = v;
             }
             __syncthreads();
             compute_chunk(no_hook, no_vm);
@@ -943,7 +920,7 @@ __global__ __launch_bounds__(512, 2) void conv_glds_kernel(ConvKP p) {
     }
     int b_addr[NI];
 #pragma unroll
-    for (int j = 0; j < NI; ++j) b_addr[j] = p.a_bytes + swz_addr(j * 32 + l31, khalf);
+    for (int j = 0; j < NI; ++j) b_addr[j] = p.a_bytes + swz64(j * 32 + l31, khalf);
 
     f32x16 acc[MI][NI];
 #pragma unroll
@@ -970,7 +947,7 @@ __global__ __launch_bounds__(512, 2) void conv_glds_kernel(ConvKP p) {
 #pragma unroll
         for (int t = 0; t < NTL; ++t)
 #pragma unroll
-            for (int i = 0; i < MI; ++i) a_addr[t][i] = swz_addr(pbase[i] + p.tap_off[TA + t], khalf);
+            for (int i = 0; i < MI; ++i) a_addr[t][i] = swz64(pbase[i] + p.tap_off[TA + t], khalf);
         const int hx4 = (KS == 4) ? (hsel << 5) : 0;
         auto load_frag = [&](int s, const unsigned char* base, Frag& f) {  // s is a constant after unrolling
             const int tl = (KS == 2) ? (s >> 1) : s;
@@ -1366,7 +1343,7 @@ int make_plan(const salt_conv_args* a, Plan* pl) {
         if (a->fold_bottom || a->fold_left || a->fold_top < 0 || a->fold_right < 0 || a->out_step != 1 || a->out_oy || a->out_ox || a->stats || a->fin_acc ||
             a->OH != a->y.H + a->fold_top || a->OW != a->y.W + a->fold_right)
             SALT_FAIL(SALT_E_BADARG, "conv: fused fold needs OH/OW = y.H + top / y.W + right (top / right pads only), out_step 1, no stats");
-        if (a->y.C % ve || a->y.cs % ve || (reinterpret_cast<uintptr_t>(a->y.p) & 15))
+        if (!view_vec(a->y, ve))
             SALT_FAIL(SALT_E_BADARG, "conv: fused fold needs 16-byte aligned whole channel pieces");
     }
     if (!a->strip && !fold_fused && ((a->OH - 1) * a->out_step + a->out_oy >= a->y.H || (a->OW - 1) * a->out_step + a->out_ox >= a->y.W))
@@ -1385,7 +1362,7 @@ int make_plan(const salt_conv_args* a, Plan* pl) {
     static const int v2_env = getenv("SALT_CONV_V2") ? atoi(getenv("SALT_CONV_V2")) : 1;     // 0: off, N >= 6: force config N
     const bool in_tf = a->in_scale || a->in_fin_acc;            // the input transform lives in conv_mfma_kernel's register-staged loader
     const bool v2_ok = a->dtype == SALT_BF16 && a->in_step == 1 && (a->ntaps == 9 || a->ntaps == 4) && a->x.C % 32 == 0 &&
-                       a->x.cs % 8 == 0 && (reinterpret_cast<uintptr_t>(a->x.p) & 15) == 0 && !in_tf;
+                       a->x.cs % 8 == 0 && aligned16(a->x.p) && !in_tf;
     // ---- tile config heuristic (overridable for tests/tuning)
     int id = ((a->cfg & 0xff) >= 9 && (a->cfg & 0xff) <= 13) ? 0 : (a->cfg & 0xff);   // 9 = "conv_ws_kernel where it applies" (conv_ws.hip): the heuristic decides for the rest
     if (id >= 6 && !v2_ok) id = 0;            // a forced conv_glds config applies where the kernel does (tests force one config per graph)
@@ -1531,9 +1508,9 @@ int make_plan(const salt_conv_args* a, Plan* pl) {
             SALT_FAIL(SALT_E_BADARG, "conv: bnb_y shape");
         if (!a->bnb_mean || !a->bnb_invstd || !a->bnb_gamma || !a->bnb_beta) SALT_FAIL(SALT_E_BADARG, "conv: bnb parameters missing");
         if (a->bnb_a.p && (!view_ok(a->bnb_a) || a->bnb_a.B != a->y.B || a->bnb_a.H != a->y.H || a->bnb_a.W != a->y.W || a->bnb_a.C != a->y.C ||
-                           a->bnb_a.cs % ve || (reinterpret_cast<uintptr_t>(a->bnb_a.p) & 15)))
+                           a->bnb_a.cs % ve || !aligned16(a->bnb_a.p)))
             SALT_FAIL(SALT_E_BADARG, "conv: bnb_a shape / alignment");
-        if (Cout % ve || a->y.cs % ve || a->bnb_y.cs % ve || ((reinterpret_cast<uintptr_t>(a->y.p) | reinterpret_cast<uintptr_t>(a->bnb_y.p)) & 15))
+        if (Cout % ve || a->y.cs % ve || a->bnb_y.cs % ve || !aligned16(a->y.p, a->bnb_y.p))
             SALT_FAIL(SALT_E_BADARG, "conv: BatchNorm-backward sums need 16-byte aligned whole channel pieces");
         const size_t red_bytes = (size_t)((cfg->KS > 0 ? 512 : 256) / (BN / ve)) * BN * 2 * sizeof(float) + 16;
         if (red_bytes > pl->lds) pl->lds = red_bytes;
@@ -1546,7 +1523,7 @@ int make_plan(const salt_conv_args* a, Plan* pl) {
             SALT_FAIL(SALT_E_BADARG, "conv: the residual epilogue needs a plain full-grid launch");
         if (!view_ok(a->res) || a->res.B != a->y.B || a->res.H != a->y.H || a->res.W != a->y.W || a->res.C != a->y.C)
             SALT_FAIL(SALT_E_BADARG, "conv: res shape");
-        if (Cout % ve || a->y.cs % ve || a->res.cs % ve || ((reinterpret_cast<uintptr_t>(a->y.p) | reinterpret_cast<uintptr_t>(a->res.p)) & 15))
+        if (Cout % ve || a->y.cs % ve || a->res.cs % ve || !aligned16(a->y.p, a->res.p))
             SALT_FAIL(SALT_E_BADARG, "conv: the residual epilogue needs 16-byte aligned whole channel pieces");
     }
     k.fin.acc = nullptr; k.bnbf.acc = nullptr;
@@ -1605,7 +1582,7 @@ int launch_cfg(const Plan& pl, hipStream_t st) {
     if constexpr (sizeof(T) == 2 && MI * WM != 2) {                       // bf16, 128- and 256-pixel tiles: interleaved loader
         const ConvKP& k = pl.kp;
         const int npa = (k.nb * k.hh * k.hw * k.vt * 4 + 255) >> 8;
-        const bool ok = k.x_cs % 8 == 0 && k.Cin % 8 == 0 && (reinterpret_cast<uintptr_t>(k.x) & 15) == 0;
+        const bool ok = k.x_cs % 8 == 0 && k.Cin % 8 == 0 && aligned16(k.x);
         if (k.in_scale || k.in_fin.acc) {                                  // input transform: the interleaved 9-tap loader only
             if (!ok || k.ntaps != 9 || k.vt != 1) SALT_FAIL(SALT_E_UNSUPPORTED, "conv: the input transform needs a 9-tap bf16 launch over aligned 16-byte pieces");
             if constexpr (MI * WM == 8) { if (npa <= 6) return launch_cfg_nt<T, MI, NI, WM, WN, 9, 6, true>(pl, st); }
@@ -1695,7 +1672,7 @@ __host__ __device__ inline bool pack_vec_ok(const salt_pack_conv_weight_args& a,
     const int kk = a.KH * a.KW;
     if (a.d1_cnt || a.n_off || a.n_total || a.chunk_off) return false;          // sub-block jobs: scalar paths
     if (dtype != SALT_BF16 || (kk != 9 && kk != 1) || a.ntaps != kk || (a.transpose ? a.D0 : a.D1) % 32) return false;
-    if ((reinterpret_cast<uintptr_t>(a.wp) & 15) || (!a.transpose && (reinterpret_cast<uintptr_t>(a.w) & 15))) return false;
+    if (!aligned16(a.wp) || (!a.transpose && !aligned16(a.w))) return false;
     for (int t = 0; t < kk; ++t) if (a.tap_kh[t] * a.KW + a.tap_kw[t] != t) return false;
     return true;
 }
@@ -1878,7 +1855,7 @@ extern "C" int salt_conv(const salt_conv_args* a, void* stream) {
     if (a->strip) {
         if (a->stats || a->out_step != 1 || a->out_oy || a->out_ox || a->fold_top < 0 || a->fold_bottom < 0 || a->fold_left < 0 || a->fold_right < 0 ||
             a->OH != a->y.H + a->fold_top + a->fold_bottom || a->OW != a->y.W + a->fold_left + a->fold_right || a->strip_cs < a->y.C ||
-            (reinterpret_cast<uintptr_t>(a->strip) & 15))
+            !aligned16(a->strip))
             SALT_FAIL(SALT_E_BADARG, "conv: fold mode needs OH/OW = y.H/y.W + pads, out_step 1, no stats, 16-byte aligned strip");
     }
     const bool in_tf = a->in_scale || a->in_fin_acc;                              // input transform: conv_mfma_kernel only
@@ -1939,11 +1916,9 @@ extern "C" int salt_pack_conv_weight(const salt_pack_conv_weight_args* a, void* 
     }
     const int64_t total = (int64_t)p.nchunk * p.ntaps * p.N * KCE;
     const int blocks = (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
-    if (a->dtype == SALT_F32) hipLaunchKernelGGL(pack_weight_kernel<float>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, p);
-    else if (a->dtype == SALT_BF16) hipLaunchKernelGGL(pack_weight_kernel<bf16_t>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, p);
-    else SALT_FAIL(SALT_E_BADARG, "pack: dtype");
-    SALT_CHECK_LAUNCH();
-    return SALT_OK;
+    if (a->dtype == SALT_F32) return salt_launch(pack_weight_kernel<float>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, p);
+    if (a->dtype == SALT_BF16) return salt_launch(pack_weight_kernel<bf16_t>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, p);
+    SALT_FAIL(SALT_E_BADARG, "pack: dtype");
 }
 
 extern "C" int salt_pack_job_blocks(const salt_pack_conv_weight_args* a) {
@@ -1965,7 +1940,7 @@ extern "C" int salt_adam_pack(const salt_adam_pack_args* a, void* stream) {
     if (!a || !a->param || !a->grad || !a->exp_avg || !a->exp_avg_sq || !a->hyper || a->n < 0 || a->njobs < 0 || a->nrest < 0 || a->pack_blocks < 0 ||
         a->rest_blocks < 0 || (a->njobs && (!a->jobs || !a->job_block0)) || (a->nrest && (!a->rest || !a->rest_block0)))
         SALT_FAIL(SALT_E_BADARG, "adam_pack: bad args");
-    if ((reinterpret_cast<uintptr_t>(a->param) | reinterpret_cast<uintptr_t>(a->grad) | reinterpret_cast<uintptr_t>(a->exp_avg) | reinterpret_cast<uintptr_t>(a->exp_avg_sq)) & 15)
+    if (!aligned16(a->param, a->grad, a->exp_avg, a->exp_avg_sq))
         SALT_FAIL(SALT_E_BADARG, "adam_pack: buffers must be 16-byte aligned");
     const int64_t blocks = (int64_t)a->pack_blocks + a->rest_blocks;
     if (blocks == 0) return SALT_OK;
@@ -1980,9 +1955,7 @@ extern "C" int salt_adam_pack(const salt_adam_pack_args* a, void* stream) {
 extern "C" int salt_pack_batched(const salt_pack_batched_args* a, void* stream) {
     if (!a || !a->jobs || !a->job_block0 || a->njobs < 1 || a->total_blocks < 1) SALT_FAIL(SALT_E_BADARG, "pack_batched: bad args");
     const auto* jobs = reinterpret_cast<const salt_pack_conv_weight_args*>(a->jobs);
-    if (a->dtype == SALT_F32) hipLaunchKernelGGL(pack_batched_kernel<float>, dim3(a->total_blocks), dim3(256), 0, (hipStream_t)stream, jobs, a->job_block0, a->njobs);
-    else if (a->dtype == SALT_BF16) hipLaunchKernelGGL(pack_batched_kernel<bf16_t>, dim3(a->total_blocks), dim3(256), 0, (hipStream_t)stream, jobs, a->job_block0, a->njobs);
-    else SALT_FAIL(SALT_E_BADARG, "pack_batched: dtype");
-    SALT_CHECK_LAUNCH();
-    return SALT_OK;
+    if (a->dtype == SALT_F32) return salt_launch(pack_batched_kernel<float>, dim3(a->total_blocks), dim3(256), 0, (hipStream_t)stream, jobs, a->job_block0, a->njobs);
+    if (a->dtype == SALT_BF16) return salt_launch(pack_batched_kernel<bf16_t>, dim3(a->total_blocks), dim3(256), 0, (hipStream_t)stream, jobs, a->job_block0, a->njobs);
+    SALT_FAIL(SALT_E_BADARG, "pack_batched: dtype");
 }

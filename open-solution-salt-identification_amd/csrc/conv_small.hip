@@ -677,38 +677,30 @@ extern "C" int salt_conv_first_wgrad(const salt_conv_first_wgrad_args* a, void* 
     FirstWgPlan pl;
     if (const int rc = first_wgrad_plan(a, &pl)) return rc;
     if (const int rc = a->dtype == SALT_F32 ? first_wgrad_launch<float>(pl, (hipStream_t)stream) : first_wgrad_launch<bf16_t>(pl, (hipStream_t)stream)) return rc;
-    if (pl.wide) hipLaunchKernelGGL(partial_sum_wide_kernel, dim3((unsigned)pl.n), dim3(256), 0, (hipStream_t)stream, a->partials, pl.nparts, pl.n, a->grad, a->accumulate);
-    else hipLaunchKernelGGL(partial_sum_kernel, dim3((unsigned)((pl.n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a->partials, pl.nparts, pl.n, a->grad, a->accumulate);
-    SALT_CHECK_LAUNCH();
-    return SALT_OK;
+    if (pl.wide) return salt_launch(partial_sum_wide_kernel, dim3((unsigned)pl.n), dim3(256), 0, (hipStream_t)stream, a->partials, pl.nparts, pl.n, a->grad, a->accumulate);
+    return salt_launch(partial_sum_kernel, dim3((unsigned)((pl.n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a->partials, pl.nparts, pl.n, a->grad, a->accumulate);
 }
 
 extern "C" int salt_s2d(const salt_s2d_args* a, void* stream) {
     if (!a || !a->x || !view_ok(a->z) || a->Cin < 1 || a->Cin > 4 || (a->H & 1) || (a->W & 1) || a->z.H != a->H / 2 || a->z.W != a->W / 2 ||
-        a->z.C != 16 || a->z.B != a->B || (a->z.cs % 16) != 0 || (reinterpret_cast<uintptr_t>(a->z.p) & 15) || (reinterpret_cast<uintptr_t>(a->x) & 7))
+        a->z.C != 16 || a->z.B != a->B || (a->z.cs % 16) != 0 || !aligned16(a->z.p) || (reinterpret_cast<uintptr_t>(a->x) & 7))
         SALT_FAIL(SALT_E_BADARG, "s2d: bad args");
     const int64_t npix = view_pixels(a->z);
     const int blocks = (int)((npix + 255) / 256 < 4096 ? (npix + 255) / 256 : 4096);
-    SALT_DISPATCH_DTYPE(a->dtype, T, { hipLaunchKernelGGL(s2d_kernel<T>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, a->x, a->B, a->Cin, a->H, a->W, a->z); })
-    SALT_CHECK_LAUNCH();
-    return SALT_OK;
+    SALT_DISPATCH_DTYPE(a->dtype, T, return salt_launch(s2d_kernel<T>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, a->x, a->B, a->Cin, a->H, a->W, a->z))
 }
 
 extern "C" int salt_pack_stem_weight(const salt_pack_stem_weight_args* a, void* stream) {
     if (!a || !a->w || !a->wp || a->Cin < 1 || a->Cin > 4 || !(a->K & 1) || a->K < 3 || a->K > 7) SALT_FAIL(SALT_E_BADARG, "pack_stem_weight: bad args");
     const int TT = (a->K + 1) / 2;
     const int total = TT * TT * a->Cout * (a->dtype == SALT_F32 ? 16 : 32);
-    SALT_DISPATCH_DTYPE(a->dtype, T, { hipLaunchKernelGGL(pack_stem_weight_kernel<T>, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream, a->w, a->Cout, a->Cin, a->K, (T*)a->wp); })
-    SALT_CHECK_LAUNCH();
-    return SALT_OK;
+    SALT_DISPATCH_DTYPE(a->dtype, T, return salt_launch(pack_stem_weight_kernel<T>, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream, a->w, a->Cout, a->Cin, a->K, (T*)a->wp))
 }
 
 extern "C" int salt_stem_grad_unfold(const salt_stem_grad_unfold_args* a, void* stream) {
     if (!a || !a->g16 || !a->grad || a->Cin < 1 || a->Cin > 4 || !(a->K & 1) || a->K < 3 || a->K > 7) SALT_FAIL(SALT_E_BADARG, "stem_grad_unfold: bad args");
     const int total = a->Cout * a->Cin * a->K * a->K;
-    hipLaunchKernelGGL(stem_grad_unfold_kernel, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream, a->g16, a->Cout, a->Cin, a->K, a->grad, a->accumulate);
-    SALT_CHECK_LAUNCH();
-    return SALT_OK;
+    return salt_launch(stem_grad_unfold_kernel, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream, a->g16, a->Cout, a->Cin, a->K, a->grad, a->accumulate);
 }
 
 namespace {
@@ -723,7 +715,7 @@ int head_select(const salt_head1x1_args* a) {
     if (a->dtype != SALT_F32 && a->dtype != SALT_BF16) SALT_FAIL(SALT_E_BADARG, "bad dtype %d", (int)a->dtype);
     const int VE = a->dtype == SALT_F32 ? Elem<float>::VE : Elem<bf16_t>::VE;
     const int cpv = a->x.C / VE;
-    const bool vec = (a->x.C % VE) == 0 && (a->x.cs % VE) == 0 && ((reinterpret_cast<uintptr_t>(a->x.p) & 15) == 0) && cpv >= 1 && cpv <= 64 && (cpv & (cpv - 1)) == 0;
+    const bool vec = view_vec(a->x, VE) && cpv >= 1 && cpv <= 64 && (cpv & (cpv - 1)) == 0;
     if (!vec) return HEAD_SCALAR;
     const int64_t hw = (int64_t)a->x.H * a->x.W;
     return a->Cout == 2 && hw < (1ll << 30) ? HEAD_VEC_CO2 : HEAD_VEC;
@@ -738,7 +730,7 @@ int head_bwd_select(const salt_head1x1_bwd_args* a, int* nparts, int64_t* per) {
     if (a->nparts != *nparts) SALT_FAIL(SALT_E_BADARG, "head1x1_bwd: nparts %d, expected %d", a->nparts, *nparts);
     const int VE = a->dtype == SALT_F32 ? Elem<float>::VE : Elem<bf16_t>::VE;
     const bool v = a->x.C % VE == 0 && a->x.cs % VE == 0 && a->dx.cs % VE == 0 && a->x.C / VE <= 256 &&
-                   ((reinterpret_cast<uintptr_t>(a->x.p) | reinterpret_cast<uintptr_t>(a->dx.p)) & 15) == 0;
+                   aligned16(a->x.p, a->dx.p);
     return v ? HEAD_VEC : HEAD_SCALAR;
 }
 
@@ -762,16 +754,12 @@ extern "C" int salt_head1x1(const salt_head1x1_args* a, void* stream) {
             const int64_t hw = (int64_t)a->x.H * a->x.W;
             const int hw_shift = (hw & (hw - 1)) == 0 ? ilog2_ceil((int)hw) : -1;
             if (kern == HEAD_VEC_CO2)
-                hipLaunchKernelGGL((head1x1_vec_co_kernel<T, 2>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, a->x, a->w, a->bias, a->y_nchw, a->y, ilog2_ceil(cpv), hw_shift);
-            else
-                hipLaunchKernelGGL(head1x1_vec_kernel<T>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, a->x, a->w, a->bias, a->Cout, a->y_nchw, a->y, ilog2_ceil(cpv));
-        } else {
-            const int blocks = (int)((npix + 255) / 256 < 4096 ? (npix + 255) / 256 : 4096);
-            hipLaunchKernelGGL(head1x1_kernel<T>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, a->x, a->w, a->bias, a->Cout, a->y_nchw, a->y);
+                return salt_launch(head1x1_vec_co_kernel<T, 2>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, a->x, a->w, a->bias, a->y_nchw, a->y, ilog2_ceil(cpv), hw_shift);
+            return salt_launch(head1x1_vec_kernel<T>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, a->x, a->w, a->bias, a->Cout, a->y_nchw, a->y, ilog2_ceil(cpv));
         }
+        const int blocks = (int)((npix + 255) / 256 < 4096 ? (npix + 255) / 256 : 4096);
+        return salt_launch(head1x1_kernel<T>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, a->x, a->w, a->bias, a->Cout, a->y_nchw, a->y);
     })
-    SALT_CHECK_LAUNCH();
-    return SALT_OK;
 }
 
 extern "C" int salt_head1x1_bwd_parts(const salt_head1x1_bwd_args* a) {
@@ -792,13 +780,10 @@ extern "C" int salt_head1x1_bwd(const salt_head1x1_bwd_args* a, void* stream) {
     const int PW = a->Cout * (a->x.C + 1);
     SALT_DISPATCH_DTYPE(a->dtype, T, {
         constexpr int VE = Elem<T>::VE;
-        if (kern == HEAD_VEC) hipLaunchKernelGGL(head1x1_bwd_vec_kernel<T>, dim3(nparts), dim3(256), 256 * VE * 4 * sizeof(float), (hipStream_t)stream,
-                                                 a->x, a->w, a->Cout, a->dy_nchw, a->dx, a->accumulate, a->partials, per);
-        else hipLaunchKernelGGL(head1x1_bwd_kernel<T>, dim3(nparts), dim3(256), 256 * 5 * sizeof(float), (hipStream_t)stream,
-                                a->x, a->w, a->Cout, a->dy_nchw, a->dx, a->accumulate, a->partials, per);
+        if (kern == HEAD_VEC) SALT_TRY(salt_launch(head1x1_bwd_vec_kernel<T>, dim3(nparts), dim3(256), 256 * VE * 4 * sizeof(float), (hipStream_t)stream,
+                                                   a->x, a->w, a->Cout, a->dy_nchw, a->dx, a->accumulate, a->partials, per));
+        else SALT_TRY(salt_launch(head1x1_bwd_kernel<T>, dim3(nparts), dim3(256), 256 * 5 * sizeof(float), (hipStream_t)stream,
+                                  a->x, a->w, a->Cout, a->dy_nchw, a->dx, a->accumulate, a->partials, per));
     })
-    SALT_CHECK_LAUNCH();
-    hipLaunchKernelGGL(head1x1_bwd_finalize, dim3(cdiv(PW, 16)), dim3(256), 0, (hipStream_t)stream, a->partials, nparts, a->Cout, a->x.C, a->gw, a->gb);
-    SALT_CHECK_LAUNCH();
-    return SALT_OK;
+    return salt_launch(head1x1_bwd_finalize, dim3(cdiv(PW, 16)), dim3(256), 0, (hipStream_t)stream, a->partials, nparts, a->Cout, a->x.C, a->gw, a->gb);
 }

@@ -31,12 +31,8 @@ struct ThKP {
     double* fin_acc; double* bnb_acc;
 };
 
-__device__ __attribute__((aligned(16))) unsigned int g_thin_zero[4] = {0u, 0u, 0u, 0u};
-
 typedef __attribute__((address_space(3))) void* lds_ptr_t;
 typedef const __attribute__((address_space(1))) void* glb_ptr_t;
-
-__device__ __forceinline__ int th_swz(int row, int slot) { return row * 64 + (((slot ^ (row >> 2)) & 3) << 4); }
 
 // CI / CO: 16-channel chunks of the input / blocks of the output; NT taps; PH = 4: the phase-fused launch of a stride-2 transposed
 // convolution (salt_conv_args.nphase: four output-parity phases with a packed weight block each, out_step 2) - a tile's halo is staged
@@ -63,7 +59,7 @@ __global__ __launch_bounds__(256) void conv_thin_kernel(ThKP p) {
         TC c; const int tx = t % p.tiles_x; const int r = t / p.tiles_x;
         c.ox0 = tx << 4; c.oy0 = (r % p.tiles_y) << 4; c.b = r / p.tiles_y; return c;
     };
-    const unsigned char* zp = reinterpret_cast<const unsigned char*>(g_thin_zero);
+    const unsigned char* zp = reinterpret_cast<const unsigned char*>(g_zero_piece);
     auto dma = [&](const void* src, int dst) {
         __builtin_amdgcn_global_load_lds((glb_ptr_t)src, (lds_ptr_t)(smem + dst), 16, 0, 0);
     };
@@ -144,9 +140,9 @@ __global__ __launch_bounds__(256) void conv_thin_kernel(ThKP p) {
         auto load_frag = [&](int s, Frag& f) {                               // s = (chunk, tap), a constant after unrolling
             const int c = s / NT, t = s - c * NT;
 #pragma unroll
-            for (int cb = 0; cb < CO; ++cb) f.a[cb] = *reinterpret_cast<const f32x4*>(smem + th_swz(wrow0 + s * BN + cb * 16 + l15, kg));
+            for (int cb = 0; cb < CO; ++cb) f.a[cb] = *reinterpret_cast<const f32x4*>(smem + swz64(wrow0 + s * BN + cb * 16 + l15, kg));
 #pragma unroll
-            for (int pb = 0; pb < 4; ++pb) f.b[pb] = *reinterpret_cast<const f32x4*>(hb + c * HC_BYTES + th_swz(brow[pb] + p.tap_off[t], kg));
+            for (int pb = 0; pb < 4; ++pb) f.b[pb] = *reinterpret_cast<const f32x4*>(hb + c * HC_BYTES + swz64(brow[pb] + p.tap_off[t], kg));
         };
         auto mma_frag = [&](const Frag& f) {
 #pragma unroll
@@ -292,7 +288,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_thin_kernel(TwKP p) {
         TC c; const int tx = t % p.tiles_x; const int r = t / p.tiles_x;
         c.ox0 = tx << 4; c.oy0 = (r % p.tiles_y) * TR; c.b = r / p.tiles_y; return c;
     };
-    const unsigned char* zp = reinterpret_cast<const unsigned char*>(g_thin_zero);
+    const unsigned char* zp = reinterpret_cast<const unsigned char*>(g_zero_piece);
     auto dma = [&](const void* src, int dst) {
         __builtin_amdgcn_global_load_lds((glb_ptr_t)src, (lds_ptr_t)(smem + dst), 16, 0, 0);
     };
@@ -435,14 +431,14 @@ int conv_thin_variant(const salt_conv_args* a) {
     if (a->x.B != a->y.B || a->OH % 16 || a->OW % 16) return 0;
     const TapBox tb = tap_box(a->tap_dy, a->tap_dx, a->ntaps);
     if (tb.max_dy - tb.min_dy > 2 || tb.max_dx - tb.min_dx > 2) return 0;
-    if (a->x.cs % 4 || a->y.cs % 4 || ((reinterpret_cast<uintptr_t>(a->x.p) | reinterpret_cast<uintptr_t>(a->y.p) | reinterpret_cast<uintptr_t>(a->w)) & 15)) return 0;
+    if (a->x.cs % 4 || a->y.cs % 4 || !aligned16(a->x.p, a->y.p, a->w)) return 0;
     auto small = [&](const salt_view& v) { return !v.p || (int64_t)v.B * v.H * v.W * v.cs < (int64_t)1 << 31; };
     if (!small(a->x) || !small(a->y) || !small(a->bnb_y) || !small(a->bnb_a)) return 0;
     if (a->bnb_acc) {
         if (!view_ok(a->bnb_y) || a->bnb_y.B != a->y.B || a->bnb_y.H != a->y.H || a->bnb_y.W != a->y.W || a->bnb_y.C != Cout || a->bnb_y.cs % 4 ||
-            (reinterpret_cast<uintptr_t>(a->bnb_y.p) & 15) || !a->bnb_mean || !a->bnb_invstd || !a->bnb_gamma || !a->bnb_beta) return 0;
+            !aligned16(a->bnb_y.p) || !a->bnb_mean || !a->bnb_invstd || !a->bnb_gamma || !a->bnb_beta) return 0;
         if (a->bnb_a.p && (a->bnb_a.B != a->y.B || a->bnb_a.H != a->y.H || a->bnb_a.W != a->y.W || a->bnb_a.C != Cout || a->bnb_a.cs % 4 ||
-                           (reinterpret_cast<uintptr_t>(a->bnb_a.p) & 15))) return 0;
+                           !aligned16(a->bnb_a.p))) return 0;
     }
     const int64_t ntiles = (int64_t)a->y.B * (a->OH / 16) * (a->OW / 16);
     if (!asked && ntiles < thin_cus() / 2) return 0;                       // too few tiles to fill the chip
@@ -496,7 +492,7 @@ int conv_wgrad_thin(const salt_conv_wgrad_args* a, bool launch, hipStream_t st, 
     const TapBox tb = tap_box(a->tap_dy, a->tap_dx, 9);
     const int min_dy = tb.min_dy, min_dx = tb.min_dx;
     if (tb.max_dy - min_dy > 2 || tb.max_dx - min_dx > 2) return 0;
-    if (a->p.cs % 4 || a->q.cs % 4 || ((reinterpret_cast<uintptr_t>(a->p.p) | reinterpret_cast<uintptr_t>(a->q.p)) & 15)) return 0;
+    if (a->p.cs % 4 || a->q.cs % 4 || !aligned16(a->p.p, a->q.p)) return 0;
     if ((int64_t)a->p.B * a->p.H * a->p.W * a->p.cs >= (int64_t)1 << 31 || (int64_t)a->q.B * a->q.H * a->q.W * a->q.cs >= (int64_t)1 << 31) return 0;
     const int ntiles = a->p.B * (a->p.H / tr) * (a->p.W / 16);
     if (ntiles < thin_cus() / 2) return 0;

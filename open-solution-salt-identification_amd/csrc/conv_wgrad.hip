@@ -977,7 +977,7 @@ static thread_local int* g_wgrad_probe = nullptr;
 // at most maxq pieces for each of 256 threads
 static bool wgrad_whole_pieces(const WgradKP& k, int ve, int maxq) {
     return k.p_cs % ve == 0 && k.q_cs % ve == 0 && k.Ca % ve == 0 && k.Cb % ve == 0 &&
-           ((reinterpret_cast<uintptr_t>(k.P) | reinterpret_cast<uintptr_t>(k.Q) | reinterpret_cast<uintptr_t>(k.partials)) & 15) == 0 &&
+           aligned16(k.P, k.Q, k.partials) &&
            k.nb * k.hh * k.hw * (64 / ve) <= maxq * 256;
 }
 
@@ -1088,8 +1088,6 @@ extern "C" int salt_wgrad_reduce(const salt_wgrad_reduce_args* a, void* stream) 
         p.tap_kh[t] = a->tap_kh[t]; p.tap_kw[t] = a->tap_kw[t];
     }
     const int64_t slab = (int64_t)a->ntaps * a->Ca * a->Cb;
-    if (a->nsplit <= 8) hipLaunchKernelGGL(wgrad_reduce8_kernel, dim3((unsigned)((slab + 255) / 256)), dim3(256), 0, (hipStream_t)stream, p);
-    else hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)((slab + 63) / 64)), dim3(256), 0, (hipStream_t)stream, p);
-    SALT_CHECK_LAUNCH();
-    return SALT_OK;
+    if (a->nsplit <= 8) return salt_launch(wgrad_reduce8_kernel, dim3((unsigned)((slab + 255) / 256)), dim3(256), 0, (hipStream_t)stream, p);
+    return salt_launch(wgrad_reduce_kernel, dim3((unsigned)((slab + 63) / 64)), dim3(256), 0, (hipStream_t)stream, p);
 }

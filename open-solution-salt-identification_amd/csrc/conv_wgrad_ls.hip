@@ -541,11 +541,11 @@ int conv_wgrad_ls(const salt_conv_wgrad_args* a, bool launch, hipStream_t st, in
     for (int t = 0; t < 9; ++t)
         if (a->tap_dy[t] != a->tap_dy[0] + t / 3 || a->tap_dx[t] != a->tap_dx[0] + t % 3) return 0;     // raster 3 x 3 window
     if (a->p.cs % 8 || a->q.cs % 8 || a->p.C % 8 || a->q.C % 8 || a->p.B != a->q.B) return 0;
-    if ((reinterpret_cast<uintptr_t>(a->p.p) | reinterpret_cast<uintptr_t>(a->q.p)) & 15) return 0;
+    if (!aligned16(a->p.p, a->q.p)) return 0;
     if ((long long)a->q.B * a->q.H * a->q.W * (a->q_plane ? a->q.C : a->q.cs) * 2 >= (1ll << 31) || (long long)a->p.B * a->p.H * a->p.W * a->p.cs * 2 >= (1ll << 31)) return 0;
     // (salt_conv_wgrad_nsplit reported THIS kernel's split count for the shape: a misaligned slab pointer must not silently fall through
     //  to the generic kernel, whose split count differs - ADVICE r4)
-    if (launch && (reinterpret_cast<uintptr_t>(a->partials) & 15)) {
+    if (launch && !aligned16(a->partials)) {
         salt_set_error("conv_wgrad: the partials workspace must be 16-byte aligned for this shape (conv_wgrad_ls_kernel)");
         if (rc) *rc = SALT_E_BADARG;
         return 1;

@@ -78,7 +78,6 @@ __device__ unsigned long long g_ws_clk[256 * 48];
 typedef __attribute__((address_space(3))) void* lds_ptr_t;
 typedef const __attribute__((address_space(1))) void* glb_ptr_t;
 
-__device__ __forceinline__ int ws_swz(int row, int slot) { return row * 64 + (((slot ^ (row >> 2)) & 3) << 4); }
 // MFMA row -> pixel of a 32-pixel (2 image rows x 16) block such that every 16-lane group of a ds_read_b128 covers 16 CONSECUTIVE
 // pixels of one image row (conflict-free for the 18-pixel halo pitch; see conv_glds_kernel)
 __device__ __forceinline__ int ws_perm(int m) { return (int)((0x73261540u >> ((m >> 2) * 4)) & 0xfu) * 4 + (m & 3); }
@@ -474,13 +473,13 @@ __global__ __launch_bounds__(512) void conv_ws_kernel(WsKP p) {
             int pb = pbase[i];
             asm volatile("" : "+v"(pb));                                     // recomputed per tile: kept live across the epilogue these 36 addresses were spilled
 #pragma unroll
-            for (int t = 0; t < NT; ++t) a_addr[t][i] = ws_swz(pb + p.tap_off[t], khalf);
+            for (int t = 0; t < NT; ++t) a_addr[t][i] = swz64(pb + p.tap_off[t], khalf);
         }
         {
             int lb = l31;
             asm volatile("" : "+v"(lb));
 #pragma unroll
-            for (int j = 0; j < NI; ++j) b_addr[j] = ws_swz(j * 32 + lb, khalf);
+            for (int j = 0; j < NI; ++j) b_addr[j] = swz64(j * 32 + lb, khalf);
         }
 #pragma unroll
         for (int i = 0; i < MI; ++i)
@@ -824,14 +823,14 @@ __global__ __launch_bounds__(256 + 64 * NLW) void conv_ls_kernel(LsKP p) {
                     int pb = pbase[i];
                     asm volatile("" : "+v"(pb));                           // per item: not kept live across the epilogue
 #pragma unroll
-                    for (int t = 0; t < NT; ++t) a_addr[t][i] = ws_swz(pb + p.tap_off[t], khalf);
+                    for (int t = 0; t < NT; ++t) a_addr[t][i] = swz64(pb + p.tap_off[t], khalf);
                 }
             }
             {
                 int lb = l31;
                 asm volatile("" : "+v"(lb));
 #pragma unroll
-                for (int j = 0; j < NI; ++j) b_addr[j] = H_BYTES + ws_swz(j * 32 + lb, khalf);
+                for (int j = 0; j < NI; ++j) b_addr[j] = H_BYTES + swz64(j * 32 + lb, khalf);
             }
             unsigned pix[MT][MI];
             auto set_pix = [&](int lx) {
@@ -867,7 +866,7 @@ __global__ __launch_bounds__(256 + 64 * NLW) void conv_ls_kernel(LsKP p) {
                     for (int i = 0; i < MI; ++i) {
                         // (two-tile items: the 18 tap addresses do not fit beside 128 accumulator registers - kept, they were spilled and reloaded
                         //  from scratch INSIDE this loop, 58 dependent loads per chunk - so they are formed per stage: 7 VALU per 4 MFMAs)
-                        const int ad = (MT == 1 ? a_addr[t][i] : ws_swz(pbc[i] + p.tap_off[t], khalf)) ^ hx;
+                        const int ad = (MT == 1 ? a_addr[t][i] : swz64(pbc[i] + p.tap_off[t], khalf)) ^ hx;
 #pragma unroll
                         for (int m = 0; m < MT; ++m) f.a[m][i] = *reinterpret_cast<const u32x4*>(hb + m * HT_BYTES + ad);
                     }
@@ -1078,9 +1077,9 @@ __global__ __launch_bounds__(512) void conv1x1_ls_kernel(L1KP p) {
     const WsEpi ep = {p.y, nullptr, nullptr, p.y_cs, 0, 0, p.relu, p.accumulate, 0, p.bias || p.scale || p.shift || p.relu, MODE == 1, p.res, p.res_cs};
     int a_addr[MI], b_addr[NI];
 #pragma unroll
-    for (int i = 0; i < MI; ++i) a_addr[i] = ws_swz(wm * 64 + i * 32 + l31, khalf);
+    for (int i = 0; i < MI; ++i) a_addr[i] = swz64(wm * 64 + i * 32 + l31, khalf);
 #pragma unroll
-    for (int j = 0; j < NI; ++j) b_addr[j] = X_BYTES + ws_swz(j * 32 + l31, khalf);
+    for (int j = 0; j < NI; ++j) b_addr[j] = X_BYTES + swz64(j * 32 + l31, khalf);
     struct Frag { u32x4 a[MI], b[NI]; };
     int g = 0;
 #pragma unroll 1
@@ -1260,9 +1259,9 @@ __global__ __launch_bounds__(512) void conv1x1_xs_kernel(XsKP p) {
         const WsEpi ep = {p.y, nullptr, nullptr, p.y_cs, 0, 0, p.relu, p.accumulate, 0, affine, false, p.res, p.res_cs};
         int a_addr[MI], b_addr[NI];
 #pragma unroll
-        for (int i = 0; i < MI; ++i) a_addr[i] = ws_swz(wm * 64 + i * 32 + l31, khalf);
+        for (int i = 0; i < MI; ++i) a_addr[i] = swz64(wm * 64 + i * 32 + l31, khalf);
 #pragma unroll
-        for (int j = 0; j < NI; ++j) b_addr[j] = ws_swz(j * 32 + l31, khalf);
+        for (int j = 0; j < NI; ++j) b_addr[j] = swz64(j * 32 + l31, khalf);
         float rs0[NI][4], rs1[NI][4];
 #pragma unroll
         for (int j = 0; j < NI; ++j)
@@ -1488,9 +1487,7 @@ int stem16_launch_mode(const S16KP& k, hipStream_t st) {
     constexpr int LDS = 32 * 1024 + 2 * 12 * 1024 + 1024 + 4 * 64 * 4;
     int wgs = ws_cus() * 2;
     if (wgs > k.ntiles) wgs = k.ntiles;
-    hipLaunchKernelGGL(conv_stem16_kernel<MODE>, dim3((unsigned)wgs), dim3(256), LDS, st, k);
-    SALT_CHECK_LAUNCH();
-    return SALT_OK;
+    return salt_launch(conv_stem16_kernel<MODE>, dim3((unsigned)wgs), dim3(256), LDS, st, k);
 }
 
 }  // namespace
@@ -1525,19 +1522,19 @@ bool conv_ws_eligible(const salt_conv_args* a) {
     if (a->y_plane && (a->y.cs != 64 || Cout % 64 || a->y_plane < (int64_t)a->y.B * a->y.H * a->y.W * 64 || a->y_plane % 8 || a->bnb_acc || a->res.p)) return false;
     // all taps x all input channels of ONE block of 32 | 64 output channels stay in LDS: Cin <= 64
     if (!((Cin == 64 && (Cout % 64 == 0 || Cout == 32)) || (Cin == 32 && Cout % 64 == 0))) return false;
-    if (a->x.cs % 8 || a->y.cs % 8 || ((reinterpret_cast<uintptr_t>(a->x.p) | reinterpret_cast<uintptr_t>(a->y.p) | reinterpret_cast<uintptr_t>(a->w)) & 15)) return false;
+    if (a->x.cs % 8 || a->y.cs % 8 || !aligned16(a->x.p, a->y.p, a->w)) return false;
     if (a->x.B != a->y.B) return false;
     if (a->fin_acc && (a->OH % 16 || a->OW % 16)) return false;           // forward statistics: whole tiles only (no per-pixel mask there)
     const TapBox tb = tap_box(a->tap_dy, a->tap_dx, 9);
     if (tb.max_dy - tb.min_dy != 2 || tb.max_dx - tb.min_dx != 2) return false;
     auto small = [](const salt_view& v) { return !v.p || (int64_t)v.B * v.H * v.W * v.cs < (int64_t)1 << 31; };
     if (!small(a->x) || !small(a->y) || !small(a->bnb_y) || !small(a->bnb_a) || !small(a->res)) return false;
-    if (a->res.p && (a->res.cs % 8 || (reinterpret_cast<uintptr_t>(a->res.p) & 15) || a->accumulate || a->fin_acc || a->bnb_acc || fold)) return false;
+    if (a->res.p && (a->res.cs % 8 || !aligned16(a->res.p) || a->accumulate || a->fin_acc || a->bnb_acc || fold)) return false;
     if (a->bnb_acc) {
         if (!view_ok(a->bnb_y) || a->bnb_y.B != a->y.B || a->bnb_y.H != a->y.H || a->bnb_y.W != a->y.W || a->bnb_y.C != Cout || a->bnb_y.cs % 8 ||
-            (reinterpret_cast<uintptr_t>(a->bnb_y.p) & 15) || !a->bnb_mean || !a->bnb_invstd || !a->bnb_gamma || !a->bnb_beta) return false;
+            !aligned16(a->bnb_y.p) || !a->bnb_mean || !a->bnb_invstd || !a->bnb_gamma || !a->bnb_beta) return false;
         if (a->bnb_a.p && (a->bnb_a.B != a->y.B || a->bnb_a.H != a->y.H || a->bnb_a.W != a->y.W || a->bnb_a.C != Cout || a->bnb_a.cs % 8 ||
-                           (reinterpret_cast<uintptr_t>(a->bnb_a.p) & 15))) return false;
+                           !aligned16(a->bnb_a.p))) return false;
         if (a->fin_acc) return false;
     }
     const int bn = Cout % 64 == 0 ? 64 : 32;
@@ -1599,7 +1596,7 @@ static int ls_common_ok(const salt_conv_args* a) {
     if (Cin % 32 || Cin < 64 || Cout % 32) return 0;
     if (a->y_plane) return 0;
     if (a->x_plane && (a->x.cs != 64 || Cin % 64 || a->x_plane % 8 || a->x_plane < (int64_t)a->x.B * a->x.H * a->x.W * 64)) return 0;
-    if (a->x.cs % 8 || a->y.cs % 8 || ((reinterpret_cast<uintptr_t>(a->x.p) | reinterpret_cast<uintptr_t>(a->y.p) | reinterpret_cast<uintptr_t>(a->w)) & 15)) return 0;
+    if (a->x.cs % 8 || a->y.cs % 8 || !aligned16(a->x.p, a->y.p, a->w)) return 0;
     if (a->OH != a->y.H || a->OW != a->y.W || a->OH % 16 || a->OW % 16 || a->x.B != a->y.B) return 0;
     const TapBox tb = tap_box(a->tap_dy, a->tap_dx, 9);
     if (tb.max_dy - tb.min_dy != 2 || tb.max_dx - tb.min_dx != 2) return 0;
@@ -1608,12 +1605,12 @@ static int ls_common_ok(const salt_conv_args* a) {
     // 256 x 256 hypercolumn is 2^31 elements); everything the epilogue touches is addressed from the tensor's base with 32 bits
     if ((int64_t)a->x.H * a->x.W * a->x.cs >= (int64_t)1 << 31 || (int64_t)a->x.B * a->x.H * a->x.W * a->x.cs >= (int64_t)1 << 40) return 0;
     if (!small(a->y) || !small(a->bnb_y) || !small(a->bnb_a) || !small(a->res)) return 0;
-    if (a->res.p && (a->res.cs % 8 || (reinterpret_cast<uintptr_t>(a->res.p) & 15) || a->accumulate || a->fin_acc || a->bnb_acc)) return 0;
+    if (a->res.p && (a->res.cs % 8 || !aligned16(a->res.p) || a->accumulate || a->fin_acc || a->bnb_acc)) return 0;
     if (a->bnb_acc) {
         if (!view_ok(a->bnb_y) || a->bnb_y.B != a->y.B || a->bnb_y.H != a->y.H || a->bnb_y.W != a->y.W || a->bnb_y.C != Cout || a->bnb_y.cs % 8 ||
-            (reinterpret_cast<uintptr_t>(a->bnb_y.p) & 15) || !a->bnb_mean || !a->bnb_invstd || !a->bnb_gamma || !a->bnb_beta) return 0;
+            !aligned16(a->bnb_y.p) || !a->bnb_mean || !a->bnb_invstd || !a->bnb_gamma || !a->bnb_beta) return 0;
         if (a->bnb_a.p && (a->bnb_a.B != a->y.B || a->bnb_a.H != a->y.H || a->bnb_a.W != a->y.W || a->bnb_a.C != Cout || a->bnb_a.cs % 8 ||
-                           (reinterpret_cast<uintptr_t>(a->bnb_a.p) & 15))) return 0;
+                           !aligned16(a->bnb_a.p))) return 0;
         if (a->fin_acc) return 0;
     }
     return 1;
@@ -1703,8 +1700,8 @@ int conv1x1_ls_variant(const salt_conv_args* a) {
     if (a->in_step == 2 && (a->y.H % 16 || a->y.W % 16 || 2 * a->y.H > a->x.H + 1 || 2 * a->y.W > a->x.W + 1)) return 0;
     const int64_t npix = (int64_t)a->y.B * a->y.H * a->y.W;
     if (npix % 256) return 0;
-    if (a->x.cs % 8 || a->y.cs % 8 || ((reinterpret_cast<uintptr_t>(a->x.p) | reinterpret_cast<uintptr_t>(a->y.p) | reinterpret_cast<uintptr_t>(a->w)) & 15)) return 0;
-    if (a->res.p && (a->res.cs % 8 || (reinterpret_cast<uintptr_t>(a->res.p) & 15) || a->accumulate)) return 0;
+    if (a->x.cs % 8 || a->y.cs % 8 || !aligned16(a->x.p, a->y.p, a->w)) return 0;
+    if (a->res.p && (a->res.cs % 8 || !aligned16(a->res.p) || a->accumulate)) return 0;
     auto small = [&](const salt_view& v) { return !v.p || (int64_t)v.B * v.H * v.W * v.cs < (int64_t)1 << 31; };
     if (!small(a->x) || !small(a->y) || !small(a->res)) return 0;
     const int wpx = ws_cus() / 8;
@@ -1785,7 +1782,7 @@ int conv_stem16_variant(const salt_conv_args* a) {
     if (a->x.C != 16 || a->y.C != 64 || a->x.B != a->y.B || a->OH != a->y.H || a->OW != a->y.W || a->OH % 16 || a->OW % 16) return 0;
     const TapBox tb = tap_box(a->tap_dy, a->tap_dx, 16);
     if (tb.max_dy - tb.min_dy > 3 || tb.max_dx - tb.min_dx > 3) return 0;
-    if (a->x.cs % 8 || a->y.cs % 8 || ((reinterpret_cast<uintptr_t>(a->x.p) | reinterpret_cast<uintptr_t>(a->y.p) | reinterpret_cast<uintptr_t>(a->w)) & 15)) return 0;
+    if (a->x.cs % 8 || a->y.cs % 8 || !aligned16(a->x.p, a->y.p, a->w)) return 0;
     if ((int64_t)a->x.B * a->x.H * a->x.W * a->x.cs >= (int64_t)1 << 31 || (int64_t)a->y.B * a->y.H * a->y.W * a->y.cs >= (int64_t)1 << 31) return 0;
     if (!asked && (int64_t)a->y.B * (a->OH / 16) * (a->OW / 16) < ws_cus() / 2) return 0;
     return 1;

@@ -30,20 +30,6 @@ template <typename T> struct Lds {
     static constexpr int RS = sizeof(T) == 2 ? 40 : 36;           // row stride in elements: 80 / 144 bytes, 16-byte aligned
     static constexpr int NS = sizeof(T) == 2 ? 2 : 4;             // Mma steps per 32-wide chunk
 };
-template <typename T> struct Mma;
-template <> struct Mma<float> {
-    static __device__ __forceinline__ void step(const u32x4& a, const u32x4& b, f32x16& c) {
-        c = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(a.x), __uint_as_float(b.x), c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(a.y), __uint_as_float(b.y), c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(a.z), __uint_as_float(b.z), c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(a.w), __uint_as_float(b.w), c, 0, 0, 0);
-    }
-};
-template <> struct Mma<bf16_t> {
-    static __device__ __forceinline__ void step(const u32x4& a, const u32x4& b, f32x16& c) {
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-    }
-};
 // the 16-byte fragment of lane (r = row, h) for step s of a chunk
 template <typename T>
 __device__ __forceinline__ u32x4 frag(const T* tile, int row, int s, int h) {
@@ -370,15 +356,6 @@ __global__ __launch_bounds__(256) void dense_wgrad_kernel(DwKP p) {
         slab[(int64_t)(n0 + 32 * nb + (q & 3) + 8 * (q >> 2) + 4 * h) * p.Cin + c0 + 32 * cb + r] = acc[q];
 }
 
-__global__ __launch_bounds__(256) void dense_wgrad_reduce_kernel(const float* partials, int nsplit, int total, float* grad, int accumulate) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= total) return;
-    float s = partials[i];
-    for (int k = 1; k < nsplit; ++k) s += partials[(int64_t)k * total + i];
-    grad[i] = accumulate ? grad[i] + s : s;
-}
-
-
 // ---------------------------------------------------------------- moments of a stored view / per-layer BatchNorm coefficients
 // Per-tile (sum, M2 about the tile's own mean, count) of a [pixels][C] view, salt_bn_finalize's protocol: a workgroup owns 128 pixels x
 // 64 channels, thread (row, channel) walks pixels row, row + 4, ... in ascending order, the four rows meet in ascending order.
@@ -424,19 +401,11 @@ __global__ __launch_bounds__(256) void dense_bn_prep_kernel(salt_dense_bn_prep_a
 }
 
 // ---------------------------------------------------------------- host
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 int dense_shape_check(const char* op, const salt_view& x, int Cout) {
     if (x.C < 32 || x.C > 2048 || x.C % 32) SALT_FAIL(SALT_E_UNSUPPORTED, "%s: %d input channels (supported: multiples of 32 in [32, 2048])", op, x.C);
     if (Cout < 64 || Cout > 1024 || Cout % 64) SALT_FAIL(SALT_E_UNSUPPORTED, "%s: %d output channels (supported: multiples of 64 in [64, 1024])", op, Cout);
     if (x.B < 1 || x.H < 1 || x.W < 1) SALT_FAIL(SALT_E_BADARG, "%s: empty batch %d x %d x %d", op, x.B, x.H, x.W);
     if (view_pixels(x) >= (1ll << 31) / 64) SALT_FAIL(SALT_E_UNSUPPORTED, "%s: too many pixels", op);
-    return SALT_OK;
-}
-int dense_view_check(const char* op, const char* what, const salt_view& v, int dtype, const salt_view& like, int C) {
-    const int ve = dtype == SALT_F32 ? 4 : 8;
-    if (!view_ok(v) || v.B != like.B || v.H != like.H || v.W != like.W || v.C != C || (v.cs % ve) || !aligned16(v.p))
-        SALT_FAIL(SALT_E_BADARG, "%s: %s must be a 16-byte aligned [%d,%d,%d,%d] view with cs a multiple of %d", op, what, like.B, like.H, like.W, C, ve);
     return SALT_OK;
 }
 int dense_vec_check(const char* op, const char* what, const void* p) {
@@ -469,8 +438,8 @@ extern "C" int salt_dense_conv(const salt_dense_conv_args* a, void* stream) {
     int rc = dense_shape_check("dense_conv", a->x, a->y.C);
     if (rc) return rc;
     if (a->dtype != SALT_F32 && a->dtype != SALT_BF16) SALT_FAIL(SALT_E_BADARG, "dense_conv: bad dtype %d", a->dtype);
-    if ((rc = dense_view_check("dense_conv", "x", a->x, a->dtype, a->x, a->x.C))) return rc;
-    if ((rc = dense_view_check("dense_conv", "y", a->y, a->dtype, a->x, a->y.C))) return rc;
+    if ((rc = view_check16("dense_conv", "x", a->x, a->dtype, a->x.B, a->x.H, a->x.W, a->x.C))) return rc;
+    if ((rc = view_check16("dense_conv", "y", a->y, a->dtype, a->x.B, a->x.H, a->x.W, a->y.C))) return rc;
     if ((rc = dense_vec_check("dense_conv", "w", a->w))) return rc;
     if ((rc = dense_vec_check("dense_conv", "in_scale", a->in_scale))) return rc;
     if ((rc = dense_vec_check("dense_conv", "in_shift", a->in_shift))) return rc;
@@ -498,9 +467,9 @@ extern "C" int salt_dense_conv_dgrad(const salt_dense_conv_dgrad_args* a, void* 
     int rc = dense_shape_check("dense_conv_dgrad", a->x, a->dy.C);
     if (rc) return rc;
     if (a->dtype != SALT_F32 && a->dtype != SALT_BF16) SALT_FAIL(SALT_E_BADARG, "dense_conv_dgrad: bad dtype %d", a->dtype);
-    if ((rc = dense_view_check("dense_conv_dgrad", "x", a->x, a->dtype, a->x, a->x.C))) return rc;
-    if ((rc = dense_view_check("dense_conv_dgrad", "dy", a->dy, a->dtype, a->x, a->dy.C))) return rc;
-    if ((rc = dense_view_check("dense_conv_dgrad", "dx", a->dx, a->dtype, a->x, a->x.C))) return rc;
+    if ((rc = view_check16("dense_conv_dgrad", "x", a->x, a->dtype, a->x.B, a->x.H, a->x.W, a->x.C))) return rc;
+    if ((rc = view_check16("dense_conv_dgrad", "dy", a->dy, a->dtype, a->x.B, a->x.H, a->x.W, a->dy.C))) return rc;
+    if ((rc = view_check16("dense_conv_dgrad", "dx", a->dx, a->dtype, a->x.B, a->x.H, a->x.W, a->x.C))) return rc;
     if ((rc = dense_vec_check("dense_conv_dgrad", "w", a->w))) return rc;
     if ((rc = dense_vec_check("dense_conv_dgrad", "in_scale", a->in_scale))) return rc;
     if ((rc = dense_vec_check("dense_conv_dgrad", "in_shift", a->in_shift))) return rc;
@@ -541,8 +510,8 @@ extern "C" int salt_dense_conv_wgrad(const salt_dense_conv_wgrad_args* a, void* 
     int rc = dense_shape_check("dense_conv_wgrad", a->x, a->dy.C);
     if (rc) return rc;
     if (a->dtype != SALT_F32 && a->dtype != SALT_BF16) SALT_FAIL(SALT_E_BADARG, "dense_conv_wgrad: bad dtype %d", a->dtype);
-    if ((rc = dense_view_check("dense_conv_wgrad", "x", a->x, a->dtype, a->x, a->x.C))) return rc;
-    if ((rc = dense_view_check("dense_conv_wgrad", "dy", a->dy, a->dtype, a->x, a->dy.C))) return rc;
+    if ((rc = view_check16("dense_conv_wgrad", "x", a->x, a->dtype, a->x.B, a->x.H, a->x.W, a->x.C))) return rc;
+    if ((rc = view_check16("dense_conv_wgrad", "dy", a->dy, a->dtype, a->x.B, a->x.H, a->x.W, a->dy.C))) return rc;
     if ((rc = dense_vec_check("dense_conv_wgrad", "in_scale", a->in_scale))) return rc;
     if ((rc = dense_vec_check("dense_conv_wgrad", "in_shift", a->in_shift))) return rc;
     if (!a->partials || !a->grad) SALT_FAIL(SALT_E_BADARG, "dense_conv_wgrad: partials / grad");
@@ -556,7 +525,7 @@ extern "C" int salt_dense_conv_wgrad(const salt_dense_conv_wgrad_args* a, void* 
     SALT_DISPATCH_DTYPE(a->dtype, T, rc = salt_launch(dense_wgrad_kernel<T>, grid, dim3(256), 0, st, p))
     if (rc) return rc;
     const int total = p.Cout * p.Cin;
-    return salt_launch(dense_wgrad_reduce_kernel, dim3(cdiv(total, 256)), dim3(256), 0, st, (const float*)a->partials, nsplit, total, a->grad, a->accumulate ? 1 : 0);
+    return salt_launch(slab_sum_kernel<>, dim3(cdiv(total, 256)), dim3(256), 0, st, (const float*)a->partials, nsplit, total, a->grad, a->accumulate ? 1 : 0);
 }
 
 extern "C" int salt_dense_moments_parts(const salt_dense_moments_args* a) {

@@ -8,19 +8,6 @@
 
 namespace {
 
-// 16-byte pieces when the channel run allows it (VEC), single elements otherwise (any C <= 256, odd sizes)
-template <typename T, bool VEC> struct Piece;
-template <typename T> struct Piece<T, true> {
-    static constexpr int N = Elem<T>::VE;
-    static __device__ __forceinline__ void ld(const T* p, float* f) { unpack16<T>(*reinterpret_cast<const u32x4*>(p), f); }
-    static __device__ __forceinline__ void st(T* p, const float* f) { *reinterpret_cast<u32x4*>(p) = pack16<T>(f); }
-};
-template <typename T> struct Piece<T, false> {
-    static constexpr int N = 1;
-    static __device__ __forceinline__ void ld(const T* p, float* f) { f[0] = Elem<T>::ld(p); }
-    static __device__ __forceinline__ void st(T* p, const float* f) { Elem<T>::st(p, f[0]); }
-};
-
 constexpr int UNR = 4;          // pixels in flight per thread (one 16-byte load each)
 
 __global__ void depth_gate_fwd_kernel(const float* d, const float* w, const float* bias, int B, int C, float* s) {
@@ -150,11 +137,6 @@ __global__ void gate_parts_reduce_kernel(const float* partials, int nparts, int 
     }
 }
 
-template <typename T> bool gate_vec(const salt_view& v) {
-    constexpr int VE = Elem<T>::VE;
-    return v.C % VE == 0 && v.cs % VE == 0 && ((uintptr_t)v.p & 15) == 0;
-}
-
 void gate_plan(const salt_view& x, int N, int* nparts, int* per) {
     const int cpv = x.C / N, R = 256 / cpv, hw = x.H * x.W;
     int np = cdiv(1024, x.B);                          // ~4 workgroups per CU over the batch
@@ -173,14 +155,10 @@ extern "C" int salt_depth_gate(const salt_depth_gate_args* a, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     if (!a->backward) {
         if (!a->w || !a->bias) SALT_FAIL(SALT_E_BADARG, "depth_gate: no parameters");
-        hipLaunchKernelGGL(depth_gate_fwd_kernel, dim3(cdiv(a->B * a->C, 256)), dim3(256), 0, st, a->d, a->w, a->bias, a->B, a->C, a->s);
-    } else {
-        if ((!a->ds && !a->ds_acc) || !a->gw || !a->gb) SALT_FAIL(SALT_E_BADARG, "depth_gate: backward needs ds or ds_acc, gw and gb");
-        hipLaunchKernelGGL(depth_gate_bwd_kernel, dim3(cdiv(a->C, 64)), dim3(64), 0, st, a->d, a->s, a->ds, a->ds_acc, a->B, a->C, a->gw, a->gb,
-                           a->accumulate);
+        return salt_launch(depth_gate_fwd_kernel, dim3(cdiv(a->B * a->C, 256)), dim3(256), 0, st, a->d, a->w, a->bias, a->B, a->C, a->s);
     }
-    SALT_CHECK_LAUNCH();
-    return SALT_OK;
+    if ((!a->ds && !a->ds_acc) || !a->gw || !a->gb) SALT_FAIL(SALT_E_BADARG, "depth_gate: backward needs ds or ds_acc, gw and gb");
+    return salt_launch(depth_gate_bwd_kernel, dim3(cdiv(a->C, 64)), dim3(64), 0, st, a->d, a->s, a->ds, a->ds_acc, a->B, a->C, a->gw, a->gb, a->accumulate);
 }
 
 static int gate_check(const salt_channel_gate_args* a) {
@@ -191,9 +169,10 @@ static int gate_check(const salt_channel_gate_args* a) {
 }
 
 template <typename T> static int gate_n(const salt_channel_gate_args* a) {
-    const bool vec = gate_vec<T>(a->x) && gate_vec<T>(a->y) && (!a->backward || gate_vec<T>(a->dx)) && a->x.C / Elem<T>::VE <= 256;
+    constexpr int VE = Elem<T>::VE;
+    const bool vec = view_vec(a->x, VE) && view_vec(a->y, VE) && (!a->backward || view_vec(a->dx, VE)) && a->x.C / VE <= 256;
     if (!vec && a->x.C > 256) return 0;
-    return vec ? Elem<T>::VE : 1;
+    return vec ? VE : 1;
 }
 
 extern "C" int salt_channel_gate_parts(const salt_channel_gate_args* a) {
@@ -218,9 +197,8 @@ extern "C" int salt_channel_gate(const salt_channel_gate_args* a, void* stream) 
         gate_plan(a->x, N, &nparts, &per);
         const dim3 grid(a->x.B * nparts);
         if (!a->backward) {
-            if (N > 1) hipLaunchKernelGGL((gate_fwd_kernel<T, true>), grid, dim3(256), 0, st, a->x, a->y, a->s, a->sC, a->c0, nparts, per);
-            else hipLaunchKernelGGL((gate_fwd_kernel<T, false>), grid, dim3(256), 0, st, a->x, a->y, a->s, a->sC, a->c0, nparts, per);
-            SALT_CHECK_LAUNCH();
+            if (N > 1) return salt_launch(gate_fwd_kernel<T, true>, grid, dim3(256), 0, st, a->x, a->y, a->s, a->sC, a->c0, nparts, per);
+            return salt_launch(gate_fwd_kernel<T, false>, grid, dim3(256), 0, st, a->x, a->y, a->s, a->sC, a->c0, nparts, per);
         } else {
             if (!view_ok(a->dx) || a->dx.B != a->x.B || a->dx.H != a->x.H || a->dx.W != a->x.W || a->dx.C != a->x.C)
                 SALT_FAIL(SALT_E_BADARG, "channel_gate: dx shape");
@@ -231,15 +209,11 @@ extern "C" int salt_channel_gate(const salt_channel_gate_args* a, void* stream) 
             const size_t lds = (size_t)R * a->x.C * sizeof(float);
             float* parts = a->ds ? a->partials : nullptr;
             double* acc = a->ds ? nullptr : a->ds_acc;
-            if (N > 1) hipLaunchKernelGGL((gate_bwd_kernel<T, true>), grid, dim3(256), lds, st, a->x, a->y, a->dx, a->s, a->sC, a->c0, a->accumulate,
-                                          a->inplace, parts, acc, nparts, per);
-            else hipLaunchKernelGGL((gate_bwd_kernel<T, false>), grid, dim3(256), lds, st, a->x, a->y, a->dx, a->s, a->sC, a->c0, a->accumulate,
-                                    a->inplace, parts, acc, nparts, per);
-            SALT_CHECK_LAUNCH();
-            if (a->ds) {
-                hipLaunchKernelGGL(gate_parts_reduce_kernel, dim3(a->x.B), dim3(256), 0, st, a->partials, nparts, a->x.C, a->ds, a->sC, a->c0);
-                SALT_CHECK_LAUNCH();
-            }
+            if (N > 1) SALT_TRY(salt_launch(gate_bwd_kernel<T, true>, grid, dim3(256), lds, st, a->x, a->y, a->dx, a->s, a->sC, a->c0, a->accumulate,
+                                            a->inplace, parts, acc, nparts, per));
+            else SALT_TRY(salt_launch(gate_bwd_kernel<T, false>, grid, dim3(256), lds, st, a->x, a->y, a->dx, a->s, a->sC, a->c0, a->accumulate,
+                                      a->inplace, parts, acc, nparts, per));
+            if (a->ds) SALT_TRY(salt_launch(gate_parts_reduce_kernel, dim3(a->x.B), dim3(256), 0, st, a->partials, nparts, a->x.C, a->ds, a->sC, a->c0));
         }
     });
     return SALT_OK;

@@ -4,27 +4,11 @@
 // pixel, so a wave reads whole 128-B+ lines), fp32 math, deterministic two-level reductions (no atomics).
 // Reference anchors are listed per entry point in include/saltnet.h.
 #include "common.h"
-#include <hip/hip_ext.h>
 #include <stdlib.h>
 
 namespace {
 
-// A "unit" is one 16-byte piece (VEC) or one element (!VEC) of one pixel of a view.
-template <typename T, bool VEC> struct Unit {
-    static constexpr int N = VEC ? Elem<T>::VE : 1;
-    static __device__ __forceinline__ void ld(const T* p, float* f) {
-        if constexpr (VEC) { u32x4 v = *reinterpret_cast<const u32x4*>(p); unpack16<T>(v, f); }
-        else f[0] = Elem<T>::ld(p);
-    }
-    static __device__ __forceinline__ void st(T* p, const float* f) {
-        if constexpr (VEC) *reinterpret_cast<u32x4*>(p) = pack16<T>(f);
-        else Elem<T>::st(p, f[0]);
-    }
-};
-
-inline bool vec_ok(const salt_view& v, int ve) {
-    return v.p == nullptr || ((v.C % ve) == 0 && (v.cs % ve) == 0 && (reinterpret_cast<uintptr_t>(v.p) & 15) == 0);
-}
+// A "unit" is one Piece (common.h) of one pixel of a view: 16 bytes (VEC) or one element (!VEC).
 inline int ew_blocks(int64_t units) {
     static const int64_t cap = getenv("SALT_EW_BLOCKS") ? atoi(getenv("SALT_EW_BLOCKS")) : 512;      // round 6: 512 = two workgroups per CU (same box: 1024 5.27, 768 5.27, 512 5.20, 384 5.21, 256 5.23, 192 5.34 ms; round 3: 768 - since then every workgroup of the consumer-side finalize kernels pays the statistics prologue)
     int64_t b = (units + 255) / 256; return (int)(b < 1 ? 1 : (b > cap ? cap : b));
@@ -36,27 +20,26 @@ inline int ew_blocks(int64_t units) {
 #ifndef SALT_AFF_UNITS
 #define SALT_AFF_UNITS 2          // ... in affine_act_kernel
 #endif
+// VEC dispatchers: each is an expression with salt_launch's return code
 #define EW_LAUNCH(KERN, T, allvec, units, stream, ...) \
-    do { if (allvec) hipLaunchKernelGGL((KERN<T, true>), dim3(ew_blocks(units)), dim3(256), 0, stream, __VA_ARGS__); \
-         else hipLaunchKernelGGL((KERN<T, false>), dim3(ew_blocks(units)), dim3(256), 0, stream, __VA_ARGS__); } while (0)
+    ((allvec) ? salt_launch(KERN<T, true>, dim3(ew_blocks(units)), dim3(256), 0, stream, __VA_ARGS__) \
+              : salt_launch(KERN<T, false>, dim3(ew_blocks(units)), dim3(256), 0, stream, __VA_ARGS__))
 
 #define EW_LAUNCH_U(KERN, T, allvec, UU, units, stream, ...) \
-    do { if (allvec) hipLaunchKernelGGL((KERN<T, true, UU>), dim3(ew_blocks(units)), dim3(256), 0, stream, __VA_ARGS__); \
-         else hipLaunchKernelGGL((KERN<T, false, UU>), dim3(ew_blocks(units)), dim3(256), 0, stream, __VA_ARGS__); } while (0)
+    ((allvec) ? salt_launch(KERN<T, true, UU>, dim3(ew_blocks(units)), dim3(256), 0, stream, __VA_ARGS__) \
+              : salt_launch(KERN<T, false, UU>, dim3(ew_blocks(units)), dim3(256), 0, stream, __VA_ARGS__))
 
 // same, with the launch's completion signal bound to ``ev`` when it is non-null (fork hand-off, see common.h)
 #define EW_LAUNCH_EV(KERN, T, allvec, units, stream, ev, ...) \
-    do { hipEvent_t ev_ = (ev); \
-         if (!ev_) { EW_LAUNCH(KERN, T, allvec, units, stream, __VA_ARGS__); } \
-         else if (allvec) hipExtLaunchKernelGGL((KERN<T, true>), dim3(ew_blocks(units)), dim3(256), 0, stream, nullptr, ev_, 0, __VA_ARGS__); \
-         else hipExtLaunchKernelGGL((KERN<T, false>), dim3(ew_blocks(units)), dim3(256), 0, stream, nullptr, ev_, 0, __VA_ARGS__); } while (0)
+    ((allvec) ? salt_launch_ev(KERN<T, true>, dim3(ew_blocks(units)), dim3(256), 0, stream, ev, __VA_ARGS__) \
+              : salt_launch_ev(KERN<T, false>, dim3(ew_blocks(units)), dim3(256), 0, stream, ev, __VA_ARGS__))
 
 // ---------------------------------------------------------------- affine + act (+ residual)
 // FIN: scale / shift are not read from memory - every workgroup finalizes the producer's fp64 statistics shards itself
 // (fin_forward_consumer, common.h) into LDS; workgroup 0 stores mean / invstd / scale / shift / running statistics.
 template <typename T, bool VEC, int U = 2, bool FIN = false>
 __global__ __launch_bounds__(256) void affine_act_kernel(salt_view y, const float* scale, const float* shift, salt_view res, int relu, salt_view a, BnFin fin) {
-    constexpr int N = Unit<T, VEC>::N;
+    constexpr int N = Piece<T, VEC>::N;
     const int cpv = y.C / N;
     const int64_t units = (int64_t)y.B * y.H * y.W * cpv;
     const int64_t stride = gridDim.x * 256LL;
@@ -79,8 +62,8 @@ __global__ __launch_bounds__(256) void affine_act_kernel(salt_view y, const floa
             for (int i = 0; i < U; ++i) {
                 const int64_t ui = u + i * stride;
                 pix[i] = (ui < units ? ui : u) / cpv;                 // past the end: re-read the first unit, never stored
-                Unit<T, VEC>::ld((const T*)y.p + pix[i] * y.cs + c0, f[i]);
-                if (res.p) Unit<T, VEC>::ld((const T*)res.p + pix[i] * res.cs + c0, r[i]);
+                Piece<T, VEC>::ld((const T*)y.p + pix[i] * y.cs + c0, f[i]);
+                if (res.p) Piece<T, VEC>::ld((const T*)res.p + pix[i] * res.cs + c0, r[i]);
             }
         };
         // the first iteration's loads go out BEFORE the statistics prologue (a chain of dependent shard loads + fp64 math + a barrier
@@ -101,7 +84,7 @@ __global__ __launch_bounds__(256) void affine_act_kernel(salt_view y, const floa
                     if (relu) v = fmaxf(v, 0.f);
                     f[i][j] = v;
                 }
-                if (i == 0 || u + i * stride < units) Unit<T, VEC>::st((T*)a.p + pix[i] * a.cs + c0, f[i]);
+                if (i == 0 || u + i * stride < units) Piece<T, VEC>::st((T*)a.p + pix[i] * a.cs + c0, f[i]);
             }
         }
         return;
@@ -110,8 +93,8 @@ __global__ __launch_bounds__(256) void affine_act_kernel(salt_view y, const floa
     for (int64_t u = blockIdx.x * 256LL + threadIdx.x; u < units; u += stride) {
         const int64_t pix = u / cpv; const int c0 = (int)(u - pix * cpv) * N;
         float f[N], r[N];
-        Unit<T, VEC>::ld((const T*)y.p + pix * y.cs + c0, f);
-        if (res.p) Unit<T, VEC>::ld((const T*)res.p + pix * res.cs + c0, r);
+        Piece<T, VEC>::ld((const T*)y.p + pix * y.cs + c0, f);
+        if (res.p) Piece<T, VEC>::ld((const T*)res.p + pix * res.cs + c0, r);
 #pragma unroll
         for (int j = 0; j < N; ++j) {
             float v = f[j];
@@ -120,7 +103,7 @@ __global__ __launch_bounds__(256) void affine_act_kernel(salt_view y, const floa
             if (relu) v = fmaxf(v, 0.f);
             f[j] = v;
         }
-        Unit<T, VEC>::st((T*)a.p + pix * a.cs + c0, f);
+        Piece<T, VEC>::st((T*)a.p + pix * a.cs + c0, f);
     }
 }
 
@@ -230,7 +213,7 @@ template <typename T, bool VEC>
 __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(salt_view da, salt_view a, salt_view y, int relu,
                                                             const float* mean, const float* invstd, const float* gamma, const float* beta,
                                                             float* partials, int64_t pix_per_block, BnbFin fin) {
-    constexpr int N = Unit<T, VEC>::N;
+    constexpr int N = Piece<T, VEC>::N;
     extern __shared__ float sm[];
     const int C = y.C, cpv = C / N;
     const int64_t npix = (int64_t)y.B * y.H * y.W;
@@ -260,14 +243,14 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(salt_view da, salt_v
 #pragma unroll
                     for (int j = 0; j < N; ++j) aa[u][j] = 0.f;
                     if (pix < p1) {
-                        Unit<T, VEC>::ld((const T*)da.p + pix * da.cs + c0, g[u]);
+                        Piece<T, VEC>::ld((const T*)da.p + pix * da.cs + c0, g[u]);
                         if (fin.da_bias) {
                             const float* bb = fin.da_bias + (size_t)bnb_image_of(fin, pix) * C + c0;
 #pragma unroll
                             for (int j = 0; j < N; ++j) g[u][j] += bb[j];
                         }
-                        Unit<T, VEC>::ld((const T*)y.p + pix * y.cs + c0, yy[u]);
-                        if (relu && !mask_from_y) Unit<T, VEC>::ld((const T*)a.p + pix * a.cs + c0, aa[u]);
+                        Piece<T, VEC>::ld((const T*)y.p + pix * y.cs + c0, yy[u]);
+                        if (relu && !mask_from_y) Piece<T, VEC>::ld((const T*)a.p + pix * a.cs + c0, aa[u]);
                     } else {
 #pragma unroll
                         for (int j = 0; j < N; ++j) { g[u][j] = 0.f; yy[u][j] = mu[j]; }
@@ -355,7 +338,7 @@ template <typename T, bool VEC, bool FIN = false, bool SEC = false>
 __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(salt_view da, salt_view a, salt_view y, int relu, const float* mean, const float* invstd,
                                     const float* gamma, const float* beta, const float* coef, salt_view dy, salt_view dres, int acc_dres, BnbFin fin,
                                     BnbSec sec) {
-    constexpr int N = Unit<T, VEC>::N;
+    constexpr int N = Piece<T, VEC>::N;
     const int C = y.C, cpv = C / N;
     const int64_t units = (int64_t)y.B * y.H * y.W * cpv;
     extern __shared__ float fin_sm[];
@@ -381,10 +364,10 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(salt_view da, salt_vi
                 for (int i = 0; i < UB; ++i) {
                     const int64_t ui = u + i * stride_;
                     pix[i] = (ui < units ? ui : u) / cpv;                  // past the end: unit 0 again, never stored
-                    Unit<T, VEC>::ld((const T*)da.p + pix[i] * da.cs + c0, g[i]);
-                    Unit<T, VEC>::ld((const T*)y.p + pix[i] * y.cs + c0, yy[i]);
-                    if (relu && !from_y) Unit<T, VEC>::ld((const T*)a.p + pix[i] * a.cs + c0, aa[i]);
-                    if (dres.p && acc_dres) Unit<T, VEC>::ld((const T*)dres.p + pix[i] * dres.cs + c0, old[i]);
+                    Piece<T, VEC>::ld((const T*)da.p + pix[i] * da.cs + c0, g[i]);
+                    Piece<T, VEC>::ld((const T*)y.p + pix[i] * y.cs + c0, yy[i]);
+                    if (relu && !from_y) Piece<T, VEC>::ld((const T*)a.p + pix[i] * a.cs + c0, aa[i]);
+                    if (dres.p && acc_dres) Piece<T, VEC>::ld((const T*)dres.p + pix[i] * dres.cs + c0, old[i]);
                 }
             };
             // the first iteration's loads go out BEFORE the coefficient prologue (dependent shard loads + fp64 math + a barrier in
@@ -432,16 +415,16 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(salt_view da, salt_vi
                         o[j] = A[j] * gg + (D[j] * (yy[i][j] - mu[j]) + E[j]);
                     }
                     if (i == 0 || u + i * stride_ < units) {
-                        Unit<T, VEC>::st((T*)dy.p + pix[i] * dy.cs + c0, o);
+                        Piece<T, VEC>::st((T*)dy.p + pix[i] * dy.cs + c0, o);
                         if (dres.p) {
                             if (acc_dres) {
 #pragma unroll
                                 for (int j = 0; j < N; ++j) g[i][j] += old[i][j];
                             }
-                            Unit<T, VEC>::st((T*)dres.p + pix[i] * dres.cs + c0, g[i]);
+                            Piece<T, VEC>::st((T*)dres.p + pix[i] * dres.cs + c0, g[i]);
                             if constexpr (SEC) {
                                 float ys[N];
-                                Unit<T, VEC>::ld((const T*)sec.y + pix[i] * sec.cs + c0, ys);
+                                Piece<T, VEC>::ld((const T*)sec.y + pix[i] * sec.cs + c0, ys);
                                 if constexpr (sizeof(T) == 2 && VEC) { const u32x4 v = pack16<T>(g[i]); unpack16<T>(v, g[i]); }   // the stored value
 #pragma unroll
                                 for (int j = 0; j < N; ++j) { t1[j] += g[i][j]; t2[j] += g[i][j] * (ys[j] - smu[j]) * sis[j]; }
@@ -473,13 +456,13 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(salt_view da, salt_vi
     for (int64_t u = blockIdx.x * 256LL + threadIdx.x; u < units; u += gridDim.x * 256LL) {
         const int64_t pix = u / cpv; const int c0 = (int)(u - pix * cpv) * N;
         float g[N], yy[N], o[N], msk[N];
-        Unit<T, VEC>::ld((const T*)da.p + pix * da.cs + c0, g);
+        Piece<T, VEC>::ld((const T*)da.p + pix * da.cs + c0, g);
         if (fin.da_bias) {
             const float* bb = fin.da_bias + (size_t)bnb_image_of(fin, pix) * C + c0;
 #pragma unroll
             for (int j = 0; j < N; ++j) g[j] += bb[j];
         }
-        Unit<T, VEC>::ld((const T*)y.p + pix * y.cs + c0, yy);
+        Piece<T, VEC>::ld((const T*)y.p + pix * y.cs + c0, yy);
 #pragma unroll
         for (int j = 0; j < N; ++j) msk[j] = 1.f;
         if (relu) {
@@ -491,7 +474,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(salt_view da, salt_vi
                 }
             } else {
                 float aa[N];
-                Unit<T, VEC>::ld((const T*)a.p + pix * a.cs + c0, aa);
+                Piece<T, VEC>::ld((const T*)a.p + pix * a.cs + c0, aa);
 #pragma unroll
                 for (int j = 0; j < N; ++j) msk[j] = aa[j] > 0.f ? 1.f : 0.f;
             }
@@ -503,44 +486,44 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(salt_view da, salt_vi
             const float xh = (yy[j] - mean[c0 + j]) * invstd[c0 + j];
             o[j] = coef[c0 + j] * (gg - coef[C + c0 + j] - xh * coef[2 * C + c0 + j]);
         }
-        Unit<T, VEC>::st((T*)dy.p + pix * dy.cs + c0, o);
+        Piece<T, VEC>::st((T*)dy.p + pix * dy.cs + c0, o);
         if (dres.p) {
             if (acc_dres) {
                 float old[N];
-                Unit<T, VEC>::ld((const T*)dres.p + pix * dres.cs + c0, old);
+                Piece<T, VEC>::ld((const T*)dres.p + pix * dres.cs + c0, old);
 #pragma unroll
                 for (int j = 0; j < N; ++j) g[j] += old[j];
             }
-            Unit<T, VEC>::st((T*)dres.p + pix * dres.cs + c0, g);
+            Piece<T, VEC>::st((T*)dres.p + pix * dres.cs + c0, g);
         }
     }
 }
 
 template <typename T, bool VEC>
 __global__ void relu_bwd_kernel(salt_view da, salt_view a, salt_view dy, int accumulate) {
-    constexpr int N = Unit<T, VEC>::N;
+    constexpr int N = Piece<T, VEC>::N;
     const int cpv = da.C / N;
     const int64_t units = (int64_t)da.B * da.H * da.W * cpv;
     for (int64_t u = blockIdx.x * 256LL + threadIdx.x; u < units; u += gridDim.x * 256LL) {
         const int64_t pix = u / cpv; const int c0 = (int)(u - pix * cpv) * N;
         float g[N], aa[N], old[N];
-        Unit<T, VEC>::ld((const T*)da.p + pix * da.cs + c0, g);
-        if (a.p) Unit<T, VEC>::ld((const T*)a.p + pix * a.cs + c0, aa);
-        if (accumulate) Unit<T, VEC>::ld((const T*)dy.p + pix * dy.cs + c0, old);
+        Piece<T, VEC>::ld((const T*)da.p + pix * da.cs + c0, g);
+        if (a.p) Piece<T, VEC>::ld((const T*)a.p + pix * a.cs + c0, aa);
+        if (accumulate) Piece<T, VEC>::ld((const T*)dy.p + pix * dy.cs + c0, old);
 #pragma unroll
         for (int j = 0; j < N; ++j) {
             float v = (a.p && !(aa[j] > 0.f)) ? 0.f : g[j];
             if (accumulate) v += old[j];
             g[j] = v;
         }
-        Unit<T, VEC>::st((T*)dy.p + pix * dy.cs + c0, g);
+        Piece<T, VEC>::st((T*)dy.p + pix * dy.cs + c0, g);
     }
 }
 
 // ---------------------------------------------------------------- pooling
 template <typename T, bool VEC>
 __global__ void maxpool2_kernel(salt_view x, salt_view y) {
-    constexpr int N = Unit<T, VEC>::N;
+    constexpr int N = Piece<T, VEC>::N;
     const int cpv = x.C / N;
     const int64_t units = (int64_t)y.B * y.H * y.W * cpv;
     for (int64_t u = blockIdx.x * 256LL + threadIdx.x; u < units; u += gridDim.x * 256LL) {
@@ -548,23 +531,23 @@ __global__ void maxpool2_kernel(salt_view x, salt_view y) {
         const int ox = (int)(pix % y.W); int64_t r = pix / y.W; const int oy = (int)(r % y.H); const int b = (int)(r / y.H);
         const T* base = (const T*)x.p + (((int64_t)b * x.H + 2 * oy) * x.W + 2 * ox) * x.cs + c0;
         float m[N], f[N];
-        Unit<T, VEC>::ld(base, m);
-        Unit<T, VEC>::ld(base + x.cs, f);
+        Piece<T, VEC>::ld(base, m);
+        Piece<T, VEC>::ld(base + x.cs, f);
 #pragma unroll
         for (int j = 0; j < N; ++j) m[j] = fmaxf(m[j], f[j]);
-        Unit<T, VEC>::ld(base + (int64_t)x.W * x.cs, f);
+        Piece<T, VEC>::ld(base + (int64_t)x.W * x.cs, f);
 #pragma unroll
         for (int j = 0; j < N; ++j) m[j] = fmaxf(m[j], f[j]);
-        Unit<T, VEC>::ld(base + (int64_t)x.W * x.cs + x.cs, f);
+        Piece<T, VEC>::ld(base + (int64_t)x.W * x.cs + x.cs, f);
 #pragma unroll
         for (int j = 0; j < N; ++j) m[j] = fmaxf(m[j], f[j]);
-        Unit<T, VEC>::st((T*)y.p + pix * y.cs + c0, m);
+        Piece<T, VEC>::st((T*)y.p + pix * y.cs + c0, m);
     }
 }
 
 template <typename T, bool VEC>
 __global__ void maxpool2_bwd_kernel(salt_view x, salt_view dy, salt_view dx, int accumulate) {
-    constexpr int N = Unit<T, VEC>::N;
+    constexpr int N = Piece<T, VEC>::N;
     const int cpv = x.C / N;
     const int64_t units = (int64_t)x.B * x.H * x.W * cpv;
     for (int64_t u = blockIdx.x * 256LL + threadIdx.x; u < units; u += gridDim.x * 256LL) {
@@ -577,11 +560,11 @@ __global__ void maxpool2_bwd_kernel(salt_view x, salt_view dy, salt_view dx, int
         if (oy < dy.H && ox < dy.W) {
             const T* base = (const T*)x.p + (((int64_t)b * x.H + 2 * oy) * x.W + 2 * ox) * x.cs + c0;
             float w[4][N], g[N];
-            Unit<T, VEC>::ld(base, w[0]);
-            Unit<T, VEC>::ld(base + x.cs, w[1]);
-            Unit<T, VEC>::ld(base + (int64_t)x.W * x.cs, w[2]);
-            Unit<T, VEC>::ld(base + (int64_t)x.W * x.cs + x.cs, w[3]);
-            Unit<T, VEC>::ld((const T*)dy.p + (((int64_t)b * dy.H + oy) * dy.W + ox) * dy.cs + c0, g);
+            Piece<T, VEC>::ld(base, w[0]);
+            Piece<T, VEC>::ld(base + x.cs, w[1]);
+            Piece<T, VEC>::ld(base + (int64_t)x.W * x.cs, w[2]);
+            Piece<T, VEC>::ld(base + (int64_t)x.W * x.cs + x.cs, w[3]);
+            Piece<T, VEC>::ld((const T*)dy.p + (((int64_t)b * dy.H + oy) * dy.W + ox) * dy.cs + c0, g);
             const int me = ((iy & 1) << 1) | (ix & 1);
 #pragma unroll
             for (int j = 0; j < N; ++j) {
@@ -592,10 +575,10 @@ __global__ void maxpool2_bwd_kernel(salt_view x, salt_view dy, salt_view dx, int
             }
         }
         T* dst = (T*)dx.p + pix * dx.cs + c0;
-        if (accumulate) { float old[N]; Unit<T, VEC>::ld(dst, old);
+        if (accumulate) { float old[N]; Piece<T, VEC>::ld(dst, old);
 #pragma unroll
             for (int j = 0; j < N; ++j) o[j] += old[j]; }
-        Unit<T, VEC>::st(dst, o);
+        Piece<T, VEC>::st(dst, o);
     }
 }
 
@@ -604,7 +587,7 @@ __global__ void maxpool2_bwd_kernel(salt_view x, salt_view dy, salt_view dx, int
 // window order; windows overlap, so an input pixel gathers from up to 4 outputs (deterministic, no atomics).
 template <typename T, bool VEC>
 __global__ void maxpool3s2_kernel(salt_view x, salt_view y) {
-    constexpr int N = Unit<T, VEC>::N;
+    constexpr int N = Piece<T, VEC>::N;
     const int cpv = x.C / N;
     const int64_t units = (int64_t)y.B * y.H * y.W * cpv;
     for (int64_t u = blockIdx.x * 256LL + threadIdx.x; u < units; u += gridDim.x * 256LL) {
@@ -619,18 +602,18 @@ __global__ void maxpool3s2_kernel(salt_view x, salt_view y) {
             for (int kx = 0; kx < 3; ++kx) {
                 const int ix = 2 * ox - 1 + kx;
                 if (ix < 0 || ix >= x.W) continue;
-                Unit<T, VEC>::ld((const T*)x.p + (((int64_t)b * x.H + iy) * x.W + ix) * x.cs + c0, f);
+                Piece<T, VEC>::ld((const T*)x.p + (((int64_t)b * x.H + iy) * x.W + ix) * x.cs + c0, f);
 #pragma unroll
                 for (int j = 0; j < N; ++j) m[j] = fmaxf(m[j], f[j]);
             }
         }
-        Unit<T, VEC>::st((T*)y.p + pix * y.cs + c0, m);
+        Piece<T, VEC>::st((T*)y.p + pix * y.cs + c0, m);
     }
 }
 
 template <typename T, bool VEC>
 __global__ void maxpool3s2_bwd_kernel(salt_view x, salt_view dy, salt_view dx, int accumulate) {
-    constexpr int N = Unit<T, VEC>::N;
+    constexpr int N = Piece<T, VEC>::N;
     const int cpv = x.C / N;
     const int64_t units = (int64_t)x.B * x.H * x.W * cpv;
     for (int64_t u = blockIdx.x * 256LL + threadIdx.x; u < units; u += gridDim.x * 256LL) {
@@ -639,7 +622,7 @@ __global__ void maxpool3s2_bwd_kernel(salt_view x, salt_view dy, salt_view dx, i
         float o[N], me[N];
 #pragma unroll
         for (int j = 0; j < N; ++j) o[j] = 0.f;
-        Unit<T, VEC>::ld((const T*)x.p + pix * x.cs + c0, me);
+        Piece<T, VEC>::ld((const T*)x.p + pix * x.cs + c0, me);
         // outputs whose window [2o-1, 2o+1] contains this pixel: o in {floor(i/2), floor((i+1)/2)}
         for (int oy = iy >> 1; oy <= (iy + 1) >> 1; ++oy) {
             if (oy >= dy.H) continue;
@@ -655,28 +638,28 @@ __global__ void maxpool3s2_bwd_kernel(salt_view x, salt_view dy, salt_view dx, i
                     for (int kx = 0; kx < 3; ++kx) {
                         const int wx = 2 * ox - 1 + kx;
                         if (wx < 0 || wx >= x.W || (wy == iy && wx == ix)) continue;
-                        Unit<T, VEC>::ld((const T*)x.p + (((int64_t)b * x.H + wy) * x.W + wx) * x.cs + c0, f);
+                        Piece<T, VEC>::ld((const T*)x.p + (((int64_t)b * x.H + wy) * x.W + wx) * x.cs + c0, f);
                         const bool before = wy < iy || (wy == iy && wx < ix);         // earlier in row-major window order
 #pragma unroll
                         for (int j = 0; j < N; ++j) if (before ? f[j] >= me[j] : f[j] > me[j]) first[j] = false;
                     }
                 }
-                Unit<T, VEC>::ld((const T*)dy.p + (((int64_t)b * dy.H + oy) * dy.W + ox) * dy.cs + c0, g);
+                Piece<T, VEC>::ld((const T*)dy.p + (((int64_t)b * dy.H + oy) * dy.W + ox) * dy.cs + c0, g);
 #pragma unroll
                 for (int j = 0; j < N; ++j) if (first[j]) o[j] += g[j];
             }
         }
         T* dst = (T*)dx.p + pix * dx.cs + c0;
-        if (accumulate) { float old[N]; Unit<T, VEC>::ld(dst, old);
+        if (accumulate) { float old[N]; Piece<T, VEC>::ld(dst, old);
 #pragma unroll
             for (int j = 0; j < N; ++j) o[j] += old[j]; }
-        Unit<T, VEC>::st(dst, o);
+        Piece<T, VEC>::st(dst, o);
     }
 }
 
 template <typename T, bool VEC>
 __global__ void avgpool2_kernel(salt_view x, salt_view y, int backward, int accumulate) {
-    constexpr int N = Unit<T, VEC>::N;
+    constexpr int N = Piece<T, VEC>::N;
     const int cpv = x.C / N;
     if (!backward) {
         const int64_t units = (int64_t)y.B * y.H * y.W * cpv;
@@ -685,17 +668,17 @@ __global__ void avgpool2_kernel(salt_view x, salt_view y, int backward, int accu
             const int ox = (int)(pix % y.W); int64_t r = pix / y.W; const int oy = (int)(r % y.H); const int b = (int)(r / y.H);
             const T* base = (const T*)x.p + (((int64_t)b * x.H + 2 * oy) * x.W + 2 * ox) * x.cs + c0;
             float s[N], f[N];
-            Unit<T, VEC>::ld(base, s);
-            Unit<T, VEC>::ld(base + x.cs, f);
+            Piece<T, VEC>::ld(base, s);
+            Piece<T, VEC>::ld(base + x.cs, f);
 #pragma unroll
             for (int j = 0; j < N; ++j) s[j] += f[j];
-            Unit<T, VEC>::ld(base + (int64_t)x.W * x.cs, f);
+            Piece<T, VEC>::ld(base + (int64_t)x.W * x.cs, f);
 #pragma unroll
             for (int j = 0; j < N; ++j) s[j] += f[j];
-            Unit<T, VEC>::ld(base + (int64_t)x.W * x.cs + x.cs, f);
+            Piece<T, VEC>::ld(base + (int64_t)x.W * x.cs + x.cs, f);
 #pragma unroll
             for (int j = 0; j < N; ++j) s[j] = (s[j] + f[j]) * 0.25f;
-            Unit<T, VEC>::st((T*)y.p + pix * y.cs + c0, s);
+            Piece<T, VEC>::st((T*)y.p + pix * y.cs + c0, s);
         }
     } else {
         const int64_t units = (int64_t)x.B * x.H * x.W * cpv;
@@ -706,15 +689,15 @@ __global__ void avgpool2_kernel(salt_view x, salt_view y, int backward, int accu
 #pragma unroll
             for (int j = 0; j < N; ++j) o[j] = 0.f;
             if ((iy >> 1) < y.H && (ix >> 1) < y.W) {
-                Unit<T, VEC>::ld((const T*)y.p + (((int64_t)b * y.H + (iy >> 1)) * y.W + (ix >> 1)) * y.cs + c0, o);
+                Piece<T, VEC>::ld((const T*)y.p + (((int64_t)b * y.H + (iy >> 1)) * y.W + (ix >> 1)) * y.cs + c0, o);
 #pragma unroll
                 for (int j = 0; j < N; ++j) o[j] *= 0.25f;
             }
             T* dst = (T*)x.p + pix * x.cs + c0;
-            if (accumulate) { float old[N]; Unit<T, VEC>::ld(dst, old);
+            if (accumulate) { float old[N]; Piece<T, VEC>::ld(dst, old);
 #pragma unroll
                 for (int j = 0; j < N; ++j) o[j] += old[j]; }
-            Unit<T, VEC>::st(dst, o);
+            Piece<T, VEC>::st(dst, o);
         }
     }
 }
@@ -733,7 +716,7 @@ __device__ __forceinline__ float bil_mix(float ly, float lx, float a, float b, f
 
 template <typename T, bool VEC, int U = 4>
 __global__ __launch_bounds__(256) void bilinear_fwd_kernel(salt_view x, salt_view y, int R, int ac) {
-    constexpr int N = Unit<T, VEC>::N;
+    constexpr int N = Piece<T, VEC>::N;
     const unsigned cpv = x.C / N;
     const int64_t units = (int64_t)y.B * y.H * y.W * cpv;
     const int64_t stride = gridDim.x * 256LL;
@@ -759,10 +742,10 @@ __global__ __launch_bounds__(256) void bilinear_fwd_kernel(salt_view x, salt_vie
             bil_src(oy, R, x.H, ac, y0, y1, ly[i]);
             bil_src(ox, R, x.W, ac, x0, x1, lx[i]);
             const T* base = (const T*)x.p + (int64_t)b * x.H * x.W * x.cs + c0;
-            Unit<T, VEC>::ld(base + ((int64_t)y0 * x.W + x0) * x.cs, a[i]);
-            Unit<T, VEC>::ld(base + ((int64_t)y0 * x.W + x1) * x.cs, bq[i]);
-            Unit<T, VEC>::ld(base + ((int64_t)y1 * x.W + x0) * x.cs, c[i]);
-            Unit<T, VEC>::ld(base + ((int64_t)y1 * x.W + x1) * x.cs, d[i]);
+            Piece<T, VEC>::ld(base + ((int64_t)y0 * x.W + x0) * x.cs, a[i]);
+            Piece<T, VEC>::ld(base + ((int64_t)y0 * x.W + x1) * x.cs, bq[i]);
+            Piece<T, VEC>::ld(base + ((int64_t)y1 * x.W + x0) * x.cs, c[i]);
+            Piece<T, VEC>::ld(base + ((int64_t)y1 * x.W + x1) * x.cs, d[i]);
             dsto[i] = pix * y.cs + c0;
         }
 #pragma unroll
@@ -771,7 +754,7 @@ __global__ __launch_bounds__(256) void bilinear_fwd_kernel(salt_view x, salt_vie
 #pragma unroll
             for (int j = 0; j < N; ++j)
                 o[j] = bil_mix(ly[i], lx[i], a[i][j], bq[i][j], c[i][j], d[i][j]);
-            if (i == 0 || u0 + i * stride < units) Unit<T, VEC>::st((T*)y.p + dsto[i], o);
+            if (i == 0 || u0 + i * stride < units) Piece<T, VEC>::st((T*)y.p + dsto[i], o);
         }
     }
 }
@@ -780,7 +763,7 @@ __global__ __launch_bounds__(256) void bilinear_fwd_kernel(salt_view x, salt_vie
 // X_ONLY / Y_ONLY variants make it separable (two passes through a [B,OH,W,C] fp32-free temp of dtype T) for large R.
 template <typename T, bool VEC, int MODE>      // MODE 0: full 2-D, 1: x only (y.H == x.H), 2: y only (y.W == x.W)
 __global__ void bilinear_bwd_kernel(salt_view x, salt_view y, int R, int accumulate, int ac) {
-    constexpr int N = Unit<T, VEC>::N;
+    constexpr int N = Piece<T, VEC>::N;
     const int cpv = x.C / N;
     const int64_t units = (int64_t)x.B * x.H * x.W * cpv;
     for (int64_t u = blockIdx.x * 256LL + threadIdx.x; u < units; u += gridDim.x * 256LL) {
@@ -820,7 +803,7 @@ __global__ void bilinear_bwd_kernel(salt_view x, salt_view y, int R, int accumul
                     for (int k = 0; k < G; ++k) {
                         const int oxk = min(ox + k, ox_hi);
                         w[k] = ox + k <= ox_hi ? wy * wgt(oxk, x.W, ix) : 0.f;
-                        Unit<T, VEC>::ld(base + ((int64_t)oy * y.W + oxk) * y.cs, g[k]);
+                        Piece<T, VEC>::ld(base + ((int64_t)oy * y.W + oxk) * y.cs, g[k]);
                     }
 #pragma unroll
                     for (int k = 0; k < G; ++k)
@@ -842,7 +825,7 @@ __global__ void bilinear_bwd_kernel(salt_view x, salt_view y, int R, int accumul
                 for (int k = 0; k < G; ++k) {
                     const int qk = min(q + k, hi);
                     w[k] = q + k <= hi ? wgt(qk, n, ii) : 0.f;
-                    Unit<T, VEC>::ld(base + line + qk * step, g[k]);
+                    Piece<T, VEC>::ld(base + line + qk * step, g[k]);
                 }
 #pragma unroll
                 for (int k = 0; k < G; ++k)
@@ -853,10 +836,10 @@ __global__ void bilinear_bwd_kernel(salt_view x, salt_view y, int R, int accumul
             }
         }
         T* dst = (T*)x.p + pix * x.cs + c0;
-        if (accumulate) { float old[N]; Unit<T, VEC>::ld(dst, old);
+        if (accumulate) { float old[N]; Piece<T, VEC>::ld(dst, old);
 #pragma unroll
             for (int j = 0; j < N; ++j) o[j] += old[j]; }
-        Unit<T, VEC>::st(dst, o);
+        Piece<T, VEC>::st(dst, o);
     }
 }
 
@@ -1093,7 +1076,7 @@ __global__ __launch_bounds__(256) void bilinear_bwd_rows_kernel(salt_view x, sal
 // ---------------------------------------------------------------- replicate-pad adjoint
 template <typename T, bool VEC>
 __global__ void pad_fold_kernel(salt_view xp, int top, int bottom, int left, int right, salt_view x, int accumulate) {
-    constexpr int N = Unit<T, VEC>::N;
+    constexpr int N = Piece<T, VEC>::N;
     const int cpv = x.C / N;
     const int64_t units = (int64_t)x.B * x.H * x.W * cpv;
     for (int64_t u = blockIdx.x * 256LL + threadIdx.x; u < units; u += gridDim.x * 256LL) {
@@ -1107,22 +1090,22 @@ __global__ void pad_fold_kernel(salt_view xp, int top, int bottom, int left, int
         for (int py = py0; py <= py1; ++py)
             for (int px = px0; px <= px1; ++px) {
                 float g[N];
-                Unit<T, VEC>::ld((const T*)xp.p + (((int64_t)b * xp.H + py) * xp.W + px) * xp.cs + c0, g);
+                Piece<T, VEC>::ld((const T*)xp.p + (((int64_t)b * xp.H + py) * xp.W + px) * xp.cs + c0, g);
 #pragma unroll
                 for (int j = 0; j < N; ++j) o[j] += g[j];
             }
         T* dst = (T*)x.p + pix * x.cs + c0;
-        if (accumulate) { float old[N]; Unit<T, VEC>::ld(dst, old);
+        if (accumulate) { float old[N]; Piece<T, VEC>::ld(dst, old);
 #pragma unroll
             for (int j = 0; j < N; ++j) o[j] += old[j]; }
-        Unit<T, VEC>::st(dst, o);
+        Piece<T, VEC>::st(dst, o);
     }
 }
 
 // second half of the fused fold: one unit per (image, perimeter pixel, channel piece); sums the pad-ring pixels that clamp onto it
 template <typename T, bool VEC>
 __global__ void pad_fold_strip_kernel(const T* strip, int strip_cs, int top, int bottom, int left, int right, salt_view x, int nperim) {
-    constexpr int N = Unit<T, VEC>::N;
+    constexpr int N = Piece<T, VEC>::N;
     const int cpv = x.C / N, H = x.H, W = x.W;
     const int64_t ring = (int64_t)(top + bottom) * (W + left + right) + (int64_t)H * (left + right);
     const int64_t units = (int64_t)x.B * nperim * cpv;
@@ -1144,35 +1127,35 @@ __global__ void pad_fold_strip_kernel(const T* strip, int strip_cs, int top, int
             for (int px = px0; px <= px1; ++px) {
                 if (py == iy + top && px == ix + left) continue;              // the interior value is already in x
                 float g[N];
-                Unit<T, VEC>::ld(strip + ((int64_t)b * ring + fold_ring_index(py, px, H, W, top, bottom, left, right)) * strip_cs + c0, g);
+                Piece<T, VEC>::ld(strip + ((int64_t)b * ring + fold_ring_index(py, px, H, W, top, bottom, left, right)) * strip_cs + c0, g);
 #pragma unroll
                 for (int j = 0; j < N; ++j) o[j] += g[j];
             }
         T* dst = (T*)x.p + (((int64_t)b * H + iy) * W + ix) * x.cs + c0;
         float old[N];
-        Unit<T, VEC>::ld(dst, old);
+        Piece<T, VEC>::ld(dst, old);
 #pragma unroll
         for (int j = 0; j < N; ++j) o[j] += old[j];
-        Unit<T, VEC>::st(dst, o);
+        Piece<T, VEC>::st(dst, o);
     }
 }
 
 template <typename T, bool VEC>
 __global__ void add_kernel(salt_view a, salt_view b, salt_view y, int accumulate) {
-    constexpr int N = Unit<T, VEC>::N;
+    constexpr int N = Piece<T, VEC>::N;
     const int cpv = a.C / N;
     const int64_t units = (int64_t)a.B * a.H * a.W * cpv;
     for (int64_t u = blockIdx.x * 256LL + threadIdx.x; u < units; u += gridDim.x * 256LL) {
         const int64_t pix = u / cpv; const int c0 = (int)(u - pix * cpv) * N;
         float f[N], g[N];
-        Unit<T, VEC>::ld((const T*)a.p + pix * a.cs + c0, f);
-        if (b.p) { Unit<T, VEC>::ld((const T*)b.p + pix * b.cs + c0, g);
+        Piece<T, VEC>::ld((const T*)a.p + pix * a.cs + c0, f);
+        if (b.p) { Piece<T, VEC>::ld((const T*)b.p + pix * b.cs + c0, g);
 #pragma unroll
             for (int j = 0; j < N; ++j) f[j] += g[j]; }
-        if (accumulate) { Unit<T, VEC>::ld((const T*)y.p + pix * y.cs + c0, g);
+        if (accumulate) { Piece<T, VEC>::ld((const T*)y.p + pix * y.cs + c0, g);
 #pragma unroll
             for (int j = 0; j < N; ++j) f[j] += g[j]; }
-        Unit<T, VEC>::st((T*)y.p + pix * y.cs + c0, f);
+        Piece<T, VEC>::st((T*)y.p + pix * y.cs + c0, f);
     }
 }
 
@@ -1201,7 +1184,7 @@ extern "C" int salt_affine_act(const salt_affine_act_args* a, void* stream) {
     if (a->fin_acc && a->y.C > 4096) SALT_FAIL(SALT_E_BADARG, "affine_act: fin_acc supports <= 4096 channels");
     SALT_DISPATCH_DTYPE(a->dtype, T, {
         const int ve = Elem<T>::VE;
-        const bool v = vec_ok(a->y, ve) && vec_ok(a->a, ve) && vec_ok(a->res, ve);
+        const bool v = view_vec(a->y, ve) && view_vec(a->a, ve) && (!a->res.p || view_vec(a->res, ve));
         const int64_t units = view_pixels(a->y) * (a->y.C / (v ? ve : 1));
         if (a->fin_acc) {
             const salt_bn_finalize_args* f = static_cast<const salt_bn_finalize_args*>(a->fin);
@@ -1210,14 +1193,11 @@ extern "C" int salt_affine_act(const salt_affine_act_args* a, void* stream) {
             const BnFin fin{const_cast<double*>(a->fin_acc), nullptr, f->gamma, f->beta, f->running_mean, f->running_var, f->num_batches_tracked,
                             f->momentum, f->eps, f->mean, f->invstd, f->scale, f->shift};
             const size_t lds = (size_t)a->y.C * 2 * sizeof(float);
-            if (v) hipLaunchKernelGGL((affine_act_kernel<T, true, SALT_AFF_UNITS, true>), dim3(ew_blocks(units)), dim3(256), lds, (hipStream_t)stream, a->y, nullptr, nullptr, a->res, a->relu, a->a, fin);
-            else hipLaunchKernelGGL((affine_act_kernel<T, false, SALT_AFF_UNITS, true>), dim3(ew_blocks(units)), dim3(256), lds, (hipStream_t)stream, a->y, nullptr, nullptr, a->res, a->relu, a->a, fin);
-        } else {
-            EW_LAUNCH_U(affine_act_kernel, T, v, SALT_AFF_UNITS, units, (hipStream_t)stream, a->y, a->scale, a->shift, a->res, a->relu, a->a, BnFin{});
+            if (v) return salt_launch(affine_act_kernel<T, true, SALT_AFF_UNITS, true>, dim3(ew_blocks(units)), dim3(256), lds, (hipStream_t)stream, a->y, nullptr, nullptr, a->res, a->relu, a->a, fin);
+            return salt_launch(affine_act_kernel<T, false, SALT_AFF_UNITS, true>, dim3(ew_blocks(units)), dim3(256), lds, (hipStream_t)stream, a->y, nullptr, nullptr, a->res, a->relu, a->a, fin);
         }
+        return EW_LAUNCH_U(affine_act_kernel, T, v, SALT_AFF_UNITS, units, (hipStream_t)stream, a->y, a->scale, a->shift, a->res, a->relu, a->a, BnFin{});
     })
-    SALT_CHECK_LAUNCH();
-    return SALT_OK;
 }
 
 extern "C" int64_t salt_bn_stats_floats(int nparts, int C) {
@@ -1229,18 +1209,14 @@ extern "C" int salt_bn_finalize(const salt_bn_finalize_args* a, void* stream) {
         SALT_FAIL(SALT_E_BADARG, "bn_finalize: bad args");
     const int rows = bn_rows_for(a->nparts);
     hipStream_t st = (hipStream_t)stream;
-    if (rows == 4) hipLaunchKernelGGL(bn_finalize_kernel<4>, dim3(cdiv(a->C, 64)), dim3(256), 0, st, *a);
-    else if (rows == 16) hipLaunchKernelGGL(bn_finalize_kernel<16>, dim3(cdiv(a->C, 16)), dim3(256), 0, st, *a);
-    else hipLaunchKernelGGL(bn_finalize_kernel<64>, dim3(cdiv(a->C, 4)), dim3(256), 0, st, *a);
-    SALT_CHECK_LAUNCH();
-    return SALT_OK;
+    if (rows == 4) return salt_launch(bn_finalize_kernel<4>, dim3(cdiv(a->C, 64)), dim3(256), 0, st, *a);
+    if (rows == 16) return salt_launch(bn_finalize_kernel<16>, dim3(cdiv(a->C, 16)), dim3(256), 0, st, *a);
+    return salt_launch(bn_finalize_kernel<64>, dim3(cdiv(a->C, 4)), dim3(256), 0, st, *a);
 }
 
 extern "C" int salt_bn_fold(const salt_bn_fold_args* a, void* stream) {
     if (!a || a->C < 1 || !a->gamma || !a->beta || !a->running_mean || !a->running_var || !a->scale || !a->shift) SALT_FAIL(SALT_E_BADARG, "bn_fold: bad args");
-    hipLaunchKernelGGL(bn_fold_kernel, dim3(cdiv(a->C, 64)), dim3(64), 0, (hipStream_t)stream, *a);
-    SALT_CHECK_LAUNCH();
-    return SALT_OK;
+    return salt_launch(bn_fold_kernel, dim3(cdiv(a->C, 64)), dim3(64), 0, (hipStream_t)stream, *a);
 }
 
 static int bn_bwd_nparts(const salt_bn_bwd_args* a, int64_t* ppb) {
@@ -1277,7 +1253,7 @@ extern "C" int salt_bn_bwd(const salt_bn_bwd_args* a, void* stream) {
     const int C = a->y.C;
     SALT_DISPATCH_DTYPE(a->dtype, T, {
         const int ve = Elem<T>::VE;
-        const bool v = vec_ok(a->da, ve) && vec_ok(a->y, ve) && vec_ok(a->dy, ve) && vec_ok(a->dres, ve) && vec_ok(a->a, ve);
+        const bool v = view_vec(a->da, ve) && view_vec(a->y, ve) && view_vec(a->dy, ve) && (!a->dres.p || view_vec(a->dres, ve)) && (!a->a.p || view_vec(a->a, ve));
         const int N = v ? ve : 1;
         const int cpv = C / N;
         const int cvn = cpv < 256 ? cpv : 256;
@@ -1296,43 +1272,39 @@ extern "C" int salt_bn_bwd(const salt_bn_bwd_args* a, void* stream) {
         const int hw_shift = (hw & (hw - 1)) == 0 ? ilog2_ceil((int)hw) : -1;
         const BnbFin fin{fin_here ? a->fin_acc : nullptr, a->fin_ticket, a->dgamma, a->dbeta, a->coef, a->accumulate_param_grads, (double)view_pixels(a->y), a->da_bias, hw, hw_shift};
         if (!a->partials_ready) {
-            if (v) hipLaunchKernelGGL((bn_bwd_reduce_kernel<T, true>), dim3(nparts), dim3(256), lds, st, a->da, a->a, a->y, a->relu, a->mean, a->invstd, a->gamma, a->beta, a->partials, per, fin);
-            else hipLaunchKernelGGL((bn_bwd_reduce_kernel<T, false>), dim3(nparts), dim3(256), lds, st, a->da, a->a, a->y, a->relu, a->mean, a->invstd, a->gamma, a->beta, a->partials, per, fin);
-            SALT_CHECK_LAUNCH();
+            if (v) SALT_TRY(salt_launch(bn_bwd_reduce_kernel<T, true>, dim3(nparts), dim3(256), lds, st, a->da, a->a, a->y, a->relu, a->mean, a->invstd, a->gamma, a->beta, a->partials, per, fin));
+            else SALT_TRY(salt_launch(bn_bwd_reduce_kernel<T, false>, dim3(nparts), dim3(256), lds, st, a->da, a->a, a->y, a->relu, a->mean, a->invstd, a->gamma, a->beta, a->partials, per, fin));
         }
         if (a->partials_ready != 2 && a->partials_ready != 3 && !fin_here) {
             const int rows = bn_rows_for(nparts);
             const double M = (double)view_pixels(a->y);
-            if (rows == 4) hipLaunchKernelGGL(bn_bwd_finalize_kernel<4>, dim3(cdiv(C, 64)), dim3(256), 0, st, a->partials, nparts, C, M, a->gamma, a->invstd, a->dgamma, a->dbeta, a->accumulate_param_grads, a->coef);
-            else if (rows == 16) hipLaunchKernelGGL(bn_bwd_finalize_kernel<16>, dim3(cdiv(C, 16)), dim3(256), 0, st, a->partials, nparts, C, M, a->gamma, a->invstd, a->dgamma, a->dbeta, a->accumulate_param_grads, a->coef);
-            else hipLaunchKernelGGL(bn_bwd_finalize_kernel<64>, dim3(cdiv(C, 4)), dim3(256), 0, st, a->partials, nparts, C, M, a->gamma, a->invstd, a->dgamma, a->dbeta, a->accumulate_param_grads, a->coef);
-            SALT_CHECK_LAUNCH();
+            if (rows == 4) SALT_TRY(salt_launch(bn_bwd_finalize_kernel<4>, dim3(cdiv(C, 64)), dim3(256), 0, st, a->partials, nparts, C, M, a->gamma, a->invstd, a->dgamma, a->dbeta, a->accumulate_param_grads, a->coef));
+            else if (rows == 16) SALT_TRY(salt_launch(bn_bwd_finalize_kernel<16>, dim3(cdiv(C, 16)), dim3(256), 0, st, a->partials, nparts, C, M, a->gamma, a->invstd, a->dgamma, a->dbeta, a->accumulate_param_grads, a->coef));
+            else SALT_TRY(salt_launch(bn_bwd_finalize_kernel<64>, dim3(cdiv(C, 4)), dim3(256), 0, st, a->partials, nparts, C, M, a->gamma, a->invstd, a->dgamma, a->dbeta, a->accumulate_param_grads, a->coef));
         }
         const int64_t units = view_pixels(a->y) * cpv;
         if (a->sec_acc) {
             // secondary sums: the vectorised fixed-piece path of the consumer-finalize apply pass only
             const int64_t grid_stride = (int64_t)ew_blocks(view_pixels(a->y) * cpv) * 256;
             if (!fin_apply || !v || !a->dres.p || a->accumulate_dres || !a->sec_mean || !a->sec_invstd || !view_ok(a->sec_y) || !same_shape(a->sec_y, a->y) ||
-                !vec_ok(a->sec_y, ve) || 256 % cpv || grid_stride % cpv || a->da_bias)
+                !view_vec(a->sec_y, ve) || 256 % cpv || grid_stride % cpv || a->da_bias)
                 SALT_FAIL(SALT_E_BADARG, "bn_bwd: secondary sums need the consumer-finalize apply pass (fin_acc, no ticket), a freshly written dres, aligned views and a channel-piece count that divides 256");
             const BnbFin fa{a->fin_acc, nullptr, a->dgamma, a->dbeta, a->coef, a->accumulate_param_grads, (double)view_pixels(a->y), nullptr, hw, hw_shift};
             const BnbSec sc{a->sec_y.p, a->sec_y.cs, a->sec_mean, a->sec_invstd, a->sec_acc};
             const size_t ldss = (size_t)C * 3 * sizeof(float) + (size_t)256 * ve * 2 * sizeof(float);
-            hipEvent_t ev_ = salt_take_fork_event();
-            hipExtLaunchKernelGGL((bn_bwd_apply_kernel<T, true, true, true>), dim3(ew_blocks(view_pixels(a->y) * cpv)), dim3(256), ldss, st, nullptr, ev_, 0, a->da, a->a, a->y, a->relu,
-                                  a->mean, a->invstd, a->gamma, a->beta, nullptr, a->dy, a->dres, a->accumulate_dres, fa, sc);
+            return salt_launch_ev(bn_bwd_apply_kernel<T, true, true, true>, dim3(ew_blocks(view_pixels(a->y) * cpv)), dim3(256), ldss, st, salt_take_fork_event(), a->da, a->a, a->y,
+                                  a->relu, a->mean, a->invstd, a->gamma, a->beta, nullptr, a->dy, a->dres, a->accumulate_dres, fa, sc);
         } else if (fin_apply) {
             const BnbFin fa{a->fin_acc, nullptr, a->dgamma, a->dbeta, a->coef, a->accumulate_param_grads, (double)view_pixels(a->y), a->da_bias, hw, hw_shift};
             const size_t lds3 = (size_t)C * 3 * sizeof(float);
-            hipEvent_t ev_ = salt_take_fork_event();
-            if (v) hipExtLaunchKernelGGL((bn_bwd_apply_kernel<T, true, true>), dim3(ew_blocks(units)), dim3(256), lds3, st, nullptr, ev_, 0, a->da, a->a, a->y, a->relu, a->mean, a->invstd, a->gamma, a->beta, nullptr, a->dy, a->dres, a->accumulate_dres, fa, BnbSec{});
-            else hipExtLaunchKernelGGL((bn_bwd_apply_kernel<T, false, true>), dim3(ew_blocks(units)), dim3(256), lds3, st, nullptr, ev_, 0, a->da, a->a, a->y, a->relu, a->mean, a->invstd, a->gamma, a->beta, nullptr, a->dy, a->dres, a->accumulate_dres, fa, BnbSec{});
+            hipEvent_t ev = salt_take_fork_event();
+            if (v) return salt_launch_ev(bn_bwd_apply_kernel<T, true, true>, dim3(ew_blocks(units)), dim3(256), lds3, st, ev, a->da, a->a, a->y, a->relu, a->mean, a->invstd, a->gamma, a->beta, nullptr, a->dy, a->dres, a->accumulate_dres, fa, BnbSec{});
+            return salt_launch_ev(bn_bwd_apply_kernel<T, false, true>, dim3(ew_blocks(units)), dim3(256), lds3, st, ev, a->da, a->a, a->y, a->relu, a->mean, a->invstd, a->gamma, a->beta, nullptr, a->dy, a->dres, a->accumulate_dres, fa, BnbSec{});
         } else {
-            EW_LAUNCH_EV(bn_bwd_apply_kernel, T, v, units, st, salt_take_fork_event(), a->da, a->a, a->y, a->relu, a->mean, a->invstd, a->gamma, a->beta, a->coef, a->dy, a->dres, a->accumulate_dres, BnbFin{nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0.0, a->da_bias, hw, hw_shift}, BnbSec{});
+            hipEvent_t ev = salt_take_fork_event();
+            return EW_LAUNCH_EV(bn_bwd_apply_kernel, T, v, units, st, ev, a->da, a->a, a->y, a->relu, a->mean, a->invstd, a->gamma, a->beta, a->coef, a->dy, a->dres, a->accumulate_dres, BnbFin{nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0.0, a->da_bias, hw, hw_shift}, BnbSec{});
         }
     })
-    SALT_CHECK_LAUNCH();
-    return SALT_OK;
 }
 
 extern "C" int salt_relu_bwd(const salt_relu_bwd_args* a, void* stream) {
@@ -1340,12 +1312,10 @@ extern "C" int salt_relu_bwd(const salt_relu_bwd_args* a, void* stream) {
     if (a->a.p && !same_shape(a->a, a->da)) SALT_FAIL(SALT_E_BADARG, "relu_bwd: mask shape");
     SALT_DISPATCH_DTYPE(a->dtype, T, {
         const int ve = Elem<T>::VE;
-        const bool v = vec_ok(a->da, ve) && vec_ok(a->dy, ve) && vec_ok(a->a, ve);
+        const bool v = view_vec(a->da, ve) && view_vec(a->dy, ve) && (!a->a.p || view_vec(a->a, ve));
         const int64_t units = view_pixels(a->da) * (a->da.C / (v ? ve : 1));
-        EW_LAUNCH(relu_bwd_kernel, T, v, units, (hipStream_t)stream, a->da, a->a, a->dy, a->accumulate);
+        return EW_LAUNCH(relu_bwd_kernel, T, v, units, (hipStream_t)stream, a->da, a->a, a->dy, a->accumulate);
     })
-    SALT_CHECK_LAUNCH();
-    return SALT_OK;
 }
 
 extern "C" int salt_maxpool2(const salt_maxpool2_args* a, void* stream) {
@@ -1353,12 +1323,10 @@ extern "C" int salt_maxpool2(const salt_maxpool2_args* a, void* stream) {
         SALT_FAIL(SALT_E_BADARG, "maxpool2: bad views");
     SALT_DISPATCH_DTYPE(a->dtype, T, {
         const int ve = Elem<T>::VE;
-        const bool v = vec_ok(a->x, ve) && vec_ok(a->y, ve);
+        const bool v = view_vec(a->x, ve) && view_vec(a->y, ve);
         const int64_t units = view_pixels(a->y) * (a->y.C / (v ? ve : 1));
-        EW_LAUNCH(maxpool2_kernel, T, v, units, (hipStream_t)stream, a->x, a->y);
+        return EW_LAUNCH(maxpool2_kernel, T, v, units, (hipStream_t)stream, a->x, a->y);
     })
-    SALT_CHECK_LAUNCH();
-    return SALT_OK;
 }
 
 extern "C" int salt_maxpool2_bwd(const salt_maxpool2_bwd_args* a, void* stream) {
@@ -1366,12 +1334,10 @@ extern "C" int salt_maxpool2_bwd(const salt_maxpool2_bwd_args* a, void* stream) 
         SALT_FAIL(SALT_E_BADARG, "maxpool2_bwd: bad views");
     SALT_DISPATCH_DTYPE(a->dtype, T, {
         const int ve = Elem<T>::VE;
-        const bool v = vec_ok(a->x, ve) && vec_ok(a->dy, ve) && vec_ok(a->dx, ve);
+        const bool v = view_vec(a->x, ve) && view_vec(a->dy, ve) && view_vec(a->dx, ve);
         const int64_t units = view_pixels(a->x) * (a->x.C / (v ? ve : 1));
-        EW_LAUNCH(maxpool2_bwd_kernel, T, v, units, (hipStream_t)stream, a->x, a->dy, a->dx, a->accumulate);
+        return EW_LAUNCH(maxpool2_bwd_kernel, T, v, units, (hipStream_t)stream, a->x, a->dy, a->dx, a->accumulate);
     })
-    SALT_CHECK_LAUNCH();
-    return SALT_OK;
 }
 
 extern "C" int salt_maxpool3s2(const salt_maxpool2_args* a, void* stream) {
@@ -1379,12 +1345,10 @@ extern "C" int salt_maxpool3s2(const salt_maxpool2_args* a, void* stream) {
         SALT_FAIL(SALT_E_BADARG, "maxpool3s2: bad views (output is ceil(H / 2) x ceil(W / 2))");
     SALT_DISPATCH_DTYPE(a->dtype, T, {
         const int ve = Elem<T>::VE;
-        const bool v = vec_ok(a->x, ve) && vec_ok(a->y, ve);
+        const bool v = view_vec(a->x, ve) && view_vec(a->y, ve);
         const int64_t units = view_pixels(a->y) * (a->y.C / (v ? ve : 1));
-        EW_LAUNCH(maxpool3s2_kernel, T, v, units, (hipStream_t)stream, a->x, a->y);
+        return EW_LAUNCH(maxpool3s2_kernel, T, v, units, (hipStream_t)stream, a->x, a->y);
     })
-    SALT_CHECK_LAUNCH();
-    return SALT_OK;
 }
 
 extern "C" int salt_maxpool3s2_bwd(const salt_maxpool2_bwd_args* a, void* stream) {
@@ -1393,12 +1357,10 @@ extern "C" int salt_maxpool3s2_bwd(const salt_maxpool2_bwd_args* a, void* stream
         SALT_FAIL(SALT_E_BADARG, "maxpool3s2_bwd: bad views");
     SALT_DISPATCH_DTYPE(a->dtype, T, {
         const int ve = Elem<T>::VE;
-        const bool v = vec_ok(a->x, ve) && vec_ok(a->dy, ve) && vec_ok(a->dx, ve);
+        const bool v = view_vec(a->x, ve) && view_vec(a->dy, ve) && view_vec(a->dx, ve);
         const int64_t units = view_pixels(a->x) * (a->x.C / (v ? ve : 1));
-        EW_LAUNCH(maxpool3s2_bwd_kernel, T, v, units, (hipStream_t)stream, a->x, a->dy, a->dx, a->accumulate);
+        return EW_LAUNCH(maxpool3s2_bwd_kernel, T, v, units, (hipStream_t)stream, a->x, a->dy, a->dx, a->accumulate);
     })
-    SALT_CHECK_LAUNCH();
-    return SALT_OK;
 }
 
 extern "C" int salt_avgpool2(const salt_avgpool2_args* a, void* stream) {
@@ -1406,12 +1368,10 @@ extern "C" int salt_avgpool2(const salt_avgpool2_args* a, void* stream) {
         SALT_FAIL(SALT_E_BADARG, "avgpool2: bad views");
     SALT_DISPATCH_DTYPE(a->dtype, T, {
         const int ve = Elem<T>::VE;
-        const bool v = vec_ok(a->x, ve) && vec_ok(a->y, ve);
+        const bool v = view_vec(a->x, ve) && view_vec(a->y, ve);
         const int64_t units = (a->backward ? view_pixels(a->x) : view_pixels(a->y)) * (a->y.C / (v ? ve : 1));
-        EW_LAUNCH(avgpool2_kernel, T, v, units, (hipStream_t)stream, a->x, a->y, a->backward, a->accumulate);
+        return EW_LAUNCH(avgpool2_kernel, T, v, units, (hipStream_t)stream, a->x, a->y, a->backward, a->accumulate);
     })
-    SALT_CHECK_LAUNCH();
-    return SALT_OK;
 }
 
 extern "C" int salt_bilinear(const salt_bilinear_args* a, void* stream) {
@@ -1420,7 +1380,7 @@ extern "C" int salt_bilinear(const salt_bilinear_args* a, void* stream) {
     static const bool rows_off = getenv("SALT_BILINEAR_ROWS") && atoi(getenv("SALT_BILINEAR_ROWS")) == 0;      // A/B: the unit-per-thread kernels
     SALT_DISPATCH_DTYPE(a->dtype, T, {
         const int ve = Elem<T>::VE;
-        const bool v = vec_ok(a->x, ve) && vec_ok(a->y, ve);
+        const bool v = view_vec(a->x, ve) && view_vec(a->y, ve);
         // row-structured kernels: vectorised views, align_corners = False, a whole number of pixels per 256-thread sweep, 32-bit row offsets
         const int cpv = a->x.C / ve;
         const bool rows_ok = !rows_off && v && !a->align_corners && cpv >= 1 && cpv <= 256 && 256 % cpv == 0 &&
@@ -1430,45 +1390,35 @@ extern "C" int salt_bilinear(const salt_bilinear_args* a, void* stream) {
         if (cells_ok) {
             const int64_t units = view_pixels(a->x) * cpv;
             const dim3 grid((unsigned)((units + 255) / 256 < 65536 ? (units + 255) / 256 : 65536));
-            if (a->R == 2) hipLaunchKernelGGL((bilinear_fwd_cells_kernel<T, 2>), grid, dim3(256), 0, (hipStream_t)stream, a->x, a->y);
-            else if (a->R == 4) hipLaunchKernelGGL((bilinear_fwd_cells_kernel<T, 4>), grid, dim3(256), 0, (hipStream_t)stream, a->x, a->y);
-            else if (a->R == 8) hipLaunchKernelGGL((bilinear_fwd_cells_kernel<T, 8>), grid, dim3(256), 0, (hipStream_t)stream, a->x, a->y);
-            else hipLaunchKernelGGL((bilinear_fwd_cells_kernel<T, 16>), grid, dim3(256), 0, (hipStream_t)stream, a->x, a->y);
+            if (a->R == 2) return salt_launch(bilinear_fwd_cells_kernel<T, 2>, grid, dim3(256), 0, (hipStream_t)stream, a->x, a->y);
+            if (a->R == 4) return salt_launch(bilinear_fwd_cells_kernel<T, 4>, grid, dim3(256), 0, (hipStream_t)stream, a->x, a->y);
+            if (a->R == 8) return salt_launch(bilinear_fwd_cells_kernel<T, 8>, grid, dim3(256), 0, (hipStream_t)stream, a->x, a->y);
+            return salt_launch(bilinear_fwd_cells_kernel<T, 16>, grid, dim3(256), 0, (hipStream_t)stream, a->x, a->y);
         } else if (!a->backward && rows_ok) {
-            hipLaunchKernelGGL((bilinear_fwd_rows_kernel<T, 4>), row_grid((int64_t)a->y.B * a->y.H), dim3(256), 0, (hipStream_t)stream, a->x, a->y, a->R);
+            return salt_launch(bilinear_fwd_rows_kernel<T, 4>, row_grid((int64_t)a->y.B * a->y.H), dim3(256), 0, (hipStream_t)stream, a->x, a->y, a->R);
         } else if (a->backward && rows_ok) {
             if (a->R >= 4 && a->tmp) {
                 salt_view t = a->x; t.p = a->tmp; t.H = a->y.H; t.cs = ((a->x.C + ve - 1) / ve) * ve;
-                hipLaunchKernelGGL((bilinear_bwd_rows_kernel<T, 1, false>), row_grid((int64_t)t.B * t.H), dim3(256), 0, (hipStream_t)stream, t, a->y, a->R, 0);
-                SALT_CHECK_LAUNCH();
-                hipLaunchKernelGGL((bilinear_bwd_rows_kernel<T, 2, false>), row_grid((int64_t)a->x.B * a->x.H), dim3(256), 0, (hipStream_t)stream, a->x, t, a->R, a->accumulate);
-            } else if (a->R == 2) {
-                hipLaunchKernelGGL((bilinear_bwd_rows_kernel<T, 0, true>), row_grid((int64_t)a->x.B * a->x.H), dim3(256), 0, (hipStream_t)stream, a->x, a->y, a->R, a->accumulate);
-            } else {
-                hipLaunchKernelGGL((bilinear_bwd_rows_kernel<T, 0, false>), row_grid((int64_t)a->x.B * a->x.H), dim3(256), 0, (hipStream_t)stream, a->x, a->y, a->R, a->accumulate);
+                SALT_TRY(salt_launch(bilinear_bwd_rows_kernel<T, 1, false>, row_grid((int64_t)t.B * t.H), dim3(256), 0, (hipStream_t)stream, t, a->y, a->R, 0));
+                return salt_launch(bilinear_bwd_rows_kernel<T, 2, false>, row_grid((int64_t)a->x.B * a->x.H), dim3(256), 0, (hipStream_t)stream, a->x, t, a->R, a->accumulate);
             }
+            if (a->R == 2) return salt_launch(bilinear_bwd_rows_kernel<T, 0, true>, row_grid((int64_t)a->x.B * a->x.H), dim3(256), 0, (hipStream_t)stream, a->x, a->y, a->R, a->accumulate);
+            return salt_launch(bilinear_bwd_rows_kernel<T, 0, false>, row_grid((int64_t)a->x.B * a->x.H), dim3(256), 0, (hipStream_t)stream, a->x, a->y, a->R, a->accumulate);
         } else if (!a->backward) {
             const int64_t units = view_pixels(a->y) * (a->y.C / (v ? ve : 1));
-            EW_LAUNCH(bilinear_fwd_kernel, T, v, units, (hipStream_t)stream, a->x, a->y, a->R, a->align_corners);
+            return EW_LAUNCH(bilinear_fwd_kernel, T, v, units, (hipStream_t)stream, a->x, a->y, a->R, a->align_corners);
         } else {
             const int64_t units = view_pixels(a->x) * (a->x.C / (v ? ve : 1));
             if (a->R >= 4 && a->tmp) {
                 // separable: x-pass into tmp [B, OH, W, C] (same dtype, contiguous), then y-pass into x
                 salt_view t = a->x; t.p = a->tmp; t.H = a->y.H; t.cs = ((a->x.C + ve - 1) / ve) * ve;
                 const int64_t tunits = view_pixels(t) * (a->x.C / (v ? ve : 1));
-                if (v) hipLaunchKernelGGL((bilinear_bwd_kernel<T, true, 1>), dim3(ew_blocks(tunits)), dim3(256), 0, (hipStream_t)stream, t, a->y, a->R, 0, a->align_corners);
-                else hipLaunchKernelGGL((bilinear_bwd_kernel<T, false, 1>), dim3(ew_blocks(tunits)), dim3(256), 0, (hipStream_t)stream, t, a->y, a->R, 0, a->align_corners);
-                SALT_CHECK_LAUNCH();
-                if (v) hipLaunchKernelGGL((bilinear_bwd_kernel<T, true, 2>), dim3(ew_blocks(units)), dim3(256), 0, (hipStream_t)stream, a->x, t, a->R, a->accumulate, a->align_corners);
-                else hipLaunchKernelGGL((bilinear_bwd_kernel<T, false, 2>), dim3(ew_blocks(units)), dim3(256), 0, (hipStream_t)stream, a->x, t, a->R, a->accumulate, a->align_corners);
-            } else {
-                if (v) hipLaunchKernelGGL((bilinear_bwd_kernel<T, true, 0>), dim3(ew_blocks(units)), dim3(256), 0, (hipStream_t)stream, a->x, a->y, a->R, a->accumulate, a->align_corners);
-                else hipLaunchKernelGGL((bilinear_bwd_kernel<T, false, 0>), dim3(ew_blocks(units)), dim3(256), 0, (hipStream_t)stream, a->x, a->y, a->R, a->accumulate, a->align_corners);
+                SALT_TRY(EW_LAUNCH_U(bilinear_bwd_kernel, T, v, 1, tunits, (hipStream_t)stream, t, a->y, a->R, 0, a->align_corners));
+                return EW_LAUNCH_U(bilinear_bwd_kernel, T, v, 2, units, (hipStream_t)stream, a->x, t, a->R, a->accumulate, a->align_corners);
             }
+            return EW_LAUNCH_U(bilinear_bwd_kernel, T, v, 0, units, (hipStream_t)stream, a->x, a->y, a->R, a->accumulate, a->align_corners);
         }
     })
-    SALT_CHECK_LAUNCH();
-    return SALT_OK;
 }
 
 extern "C" int salt_pad_fold(const salt_pad_fold_args* a, void* stream) {
@@ -1476,12 +1426,10 @@ extern "C" int salt_pad_fold(const salt_pad_fold_args* a, void* stream) {
         SALT_FAIL(SALT_E_BADARG, "pad_fold: bad views");
     SALT_DISPATCH_DTYPE(a->dtype, T, {
         const int ve = Elem<T>::VE;
-        const bool v = vec_ok(a->x, ve) && vec_ok(a->xp, ve);
+        const bool v = view_vec(a->x, ve) && view_vec(a->xp, ve);
         const int64_t units = view_pixels(a->x) * (a->x.C / (v ? ve : 1));
-        EW_LAUNCH(pad_fold_kernel, T, v, units, (hipStream_t)stream, a->xp, a->top, a->bottom, a->left, a->right, a->x, a->accumulate);
+        return EW_LAUNCH(pad_fold_kernel, T, v, units, (hipStream_t)stream, a->xp, a->top, a->bottom, a->left, a->right, a->x, a->accumulate);
     })
-    SALT_CHECK_LAUNCH();
-    return SALT_OK;
 }
 
 extern "C" int64_t salt_fold_strip_pixels(int H, int W, int top, int bottom, int left, int right) {
@@ -1495,12 +1443,10 @@ extern "C" int salt_pad_fold_strip(const salt_pad_fold_strip_args* a, void* stre
     const int nperim = (H < 3 || W < 3) ? H * W : 2 * W + 2 * (H - 2);
     SALT_DISPATCH_DTYPE(a->dtype, T, {
         const int ve = Elem<T>::VE;
-        const bool v = vec_ok(a->x, ve) && (a->strip_cs % ve) == 0 && (reinterpret_cast<uintptr_t>(a->strip) & 15) == 0;
+        const bool v = view_vec(a->x, ve) && (a->strip_cs % ve) == 0 && aligned16(a->strip);
         const int64_t units = (int64_t)a->x.B * nperim * (a->x.C / (v ? ve : 1));
-        EW_LAUNCH(pad_fold_strip_kernel, T, v, units, (hipStream_t)stream, (const T*)a->strip, a->strip_cs, a->top, a->bottom, a->left, a->right, a->x, nperim);
+        return EW_LAUNCH(pad_fold_strip_kernel, T, v, units, (hipStream_t)stream, (const T*)a->strip, a->strip_cs, a->top, a->bottom, a->left, a->right, a->x, nperim);
     })
-    SALT_CHECK_LAUNCH();
-    return SALT_OK;
 }
 
 extern "C" int salt_add(const salt_add_args* a, void* stream) {
@@ -1508,20 +1454,16 @@ extern "C" int salt_add(const salt_add_args* a, void* stream) {
     if (a->b.p && !same_shape(a->a, a->b)) SALT_FAIL(SALT_E_BADARG, "add: b shape");
     SALT_DISPATCH_DTYPE(a->dtype, T, {
         const int ve = Elem<T>::VE;
-        const bool v = vec_ok(a->a, ve) && vec_ok(a->b, ve) && vec_ok(a->y, ve);
+        const bool v = view_vec(a->a, ve) && (!a->b.p || view_vec(a->b, ve)) && view_vec(a->y, ve);
         const int64_t units = view_pixels(a->a) * (a->a.C / (v ? ve : 1));
-        EW_LAUNCH(add_kernel, T, v, units, (hipStream_t)stream, a->a, a->b, a->y, a->accumulate);
+        return EW_LAUNCH(add_kernel, T, v, units, (hipStream_t)stream, a->a, a->b, a->y, a->accumulate);
     })
-    SALT_CHECK_LAUNCH();
-    return SALT_OK;
 }
 
 extern "C" int salt_layout(const salt_layout_args* a, void* stream) {
     if (!a || !a->nchw || !view_ok(a->nhwc)) SALT_FAIL(SALT_E_BADARG, "layout: bad args");
     const int64_t npix = view_pixels(a->nhwc);
     SALT_DISPATCH_DTYPE(a->dtype, T, {
-        hipLaunchKernelGGL(layout_kernel<T>, dim3(ew_blocks(npix)), dim3(256), 0, (hipStream_t)stream, a->nchw, a->nhwc, a->to_nhwc);
+        return salt_launch(layout_kernel<T>, dim3(ew_blocks(npix)), dim3(256), 0, (hipStream_t)stream, a->nchw, a->nhwc, a->to_nhwc);
     })
-    SALT_CHECK_LAUNCH();
-    return SALT_OK;
 }

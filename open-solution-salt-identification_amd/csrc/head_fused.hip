@@ -14,7 +14,6 @@
 // Rounding points are the unfused path's: `a` and `da` are rounded to the storage dtype where salt_affine_act / salt_head1x1_bwd would
 // have stored them, so the two paths differ only in summation order (tests/test_gpu_head_fused.py bounds it).
 #include "common.h"
-#include <hip/hip_ext.h>
 #include <stdlib.h>
 
 namespace {
@@ -300,7 +299,7 @@ __global__ __launch_bounds__(256) void head_bn_bwd_apply_kernel(salt_view y, int
 template <typename T> bool head_bn_ok(const salt_view& v) {
     constexpr int VE = Elem<T>::VE;
     const int cpv = v.C / VE;
-    return (v.C % VE) == 0 && (v.cs % VE) == 0 && ((reinterpret_cast<uintptr_t>(v.p) & 15) == 0) && cpv >= 1 && cpv <= 64 && (cpv & (cpv - 1)) == 0;
+    return view_vec(v, VE) && cpv >= 1 && cpv <= 64 && (cpv & (cpv - 1)) == 0;
 }
 
 int head_bn_parts(const salt_view& x, int64_t* per) {
@@ -321,11 +320,12 @@ inline int head_bn_blocks(int64_t units) {
 
 }  // namespace
 
-#define SALT_HB(CO) hipLaunchKernelGGL((head_bn_fwd_kernel<T, CO>), dim3(blocks), dim3(256), lds, st, a->y, fin, a->relu, a->w, a->bias, a->y_nchw, ilog2_ceil(cpv), hw_shift)
-#define SALT_HBR(CO) hipLaunchKernelGGL((head_bn_bwd_reduce_kernel<T, CO>), dim3(nparts), dim3(256), lds1, st, a->y, a->relu, a->mean, a->invstd, a->gamma, a->beta, \
-                                        a->w, a->dy_nchw, a->partials, per, a->fin_acc, hw_shift)
-#define SALT_HBA(CO) hipExtLaunchKernelGGL((head_bn_bwd_apply_kernel<T, CO>), dim3(blocks), dim3(256), lds2, st, nullptr, ev_, 0, a->y, a->relu, a->mean, a->invstd, \
-                                           a->gamma, a->beta, a->w, a->dy_nchw, a->dy, fa, ilog2_ceil(cpv), hw_shift)
+// width dispatchers: each is an expression with salt_launch's return code
+#define SALT_HB(CO) salt_launch(head_bn_fwd_kernel<T, CO>, dim3(blocks), dim3(256), lds, st, a->y, fin, a->relu, a->w, a->bias, a->y_nchw, ilog2_ceil(cpv), hw_shift)
+#define SALT_HBR(CO) salt_launch(head_bn_bwd_reduce_kernel<T, CO>, dim3(nparts), dim3(256), lds1, st, a->y, a->relu, a->mean, a->invstd, a->gamma, a->beta, \
+                                 a->w, a->dy_nchw, a->partials, per, a->fin_acc, hw_shift)
+#define SALT_HBA(CO) salt_launch_ev(head_bn_bwd_apply_kernel<T, CO>, dim3(blocks), dim3(256), lds2, st, ev, a->y, a->relu, a->mean, a->invstd, \
+                                    a->gamma, a->beta, a->w, a->dy_nchw, a->dy, fa, ilog2_ceil(cpv), hw_shift)
 
 extern "C" int salt_head_bn(const salt_head_bn_args* a, void* stream) {
     if (!a || !view_ok(a->y) || !a->w || !a->y_nchw || !a->fin || !a->fin_acc || a->Cout < 1 || a->Cout > 4) SALT_FAIL(SALT_E_BADARG, "head_bn: bad args");
@@ -344,10 +344,8 @@ extern "C" int salt_head_bn(const salt_head_bn_args* a, void* stream) {
         const int blocks = head_bn_blocks(view_pixels(a->y) * cpv);
         const size_t lds = (size_t)a->y.C * 2 * sizeof(float);
         hipStream_t st = (hipStream_t)stream;
-        if (a->Cout == 1) SALT_HB(1); else if (a->Cout == 2) SALT_HB(2); else if (a->Cout == 3) SALT_HB(3); else SALT_HB(4);
+        return a->Cout == 1 ? SALT_HB(1) : a->Cout == 2 ? SALT_HB(2) : a->Cout == 3 ? SALT_HB(3) : SALT_HB(4);
     })
-    SALT_CHECK_LAUNCH();
-    return SALT_OK;
 }
 
 extern "C" int salt_head_bn_bwd_parts(const salt_head_bn_bwd_args* a) {
@@ -372,16 +370,12 @@ extern "C" int salt_head_bn_bwd(const salt_head_bn_bwd_args* a, void* stream) {
         if (!head_bn_ok<T>(a->y) || !head_bn_ok<T>(a->dy)) SALT_FAIL(SALT_E_UNSUPPORTED, "head_bn_bwd: C=%d must be a power-of-two number of aligned 16-byte pieces (<= 64)", C);
         const int cpv = C / VE;
         const size_t lds1 = (size_t)256 * VE * (a->Cout > 2 ? a->Cout : 2) * sizeof(float);
-        if (a->Cout == 1) SALT_HBR(1); else if (a->Cout == 2) SALT_HBR(2); else if (a->Cout == 3) SALT_HBR(3); else SALT_HBR(4);
-        SALT_CHECK_LAUNCH();
-        hipLaunchKernelGGL(head_bn_gw_finalize, dim3(cdiv(PW, 16)), dim3(256), 0, st, a->partials, nparts, a->Cout, C, a->gw, a->gb);
-        SALT_CHECK_LAUNCH();
+        SALT_TRY(a->Cout == 1 ? SALT_HBR(1) : a->Cout == 2 ? SALT_HBR(2) : a->Cout == 3 ? SALT_HBR(3) : SALT_HBR(4));
+        SALT_TRY(salt_launch(head_bn_gw_finalize, dim3(cdiv(PW, 16)), dim3(256), 0, st, a->partials, nparts, a->Cout, C, a->gw, a->gb));
         const BnbFin fa{a->fin_acc, nullptr, a->dgamma, a->dbeta, a->coef, 0, (double)view_pixels(a->y), nullptr, (unsigned)hw, hw_shift};
         const int blocks = head_bn_blocks(view_pixels(a->y) * cpv);
         const size_t lds2 = (size_t)C * 3 * sizeof(float);
-        hipEvent_t ev_ = salt_take_fork_event();       // the launch that completes dL/dy carries the weight-gradient queue's fork (common.h)
-        if (a->Cout == 1) SALT_HBA(1); else if (a->Cout == 2) SALT_HBA(2); else if (a->Cout == 3) SALT_HBA(3); else SALT_HBA(4);
+        hipEvent_t ev = salt_take_fork_event();        // the launch that completes dL/dy carries the weight-gradient queue's fork (common.h)
+        return a->Cout == 1 ? SALT_HBA(1) : a->Cout == 2 ? SALT_HBA(2) : a->Cout == 3 ? SALT_HBA(3) : SALT_HBA(4);
     })
-    SALT_CHECK_LAUNCH();
-    return SALT_OK;
 }

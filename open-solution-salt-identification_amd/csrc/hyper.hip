@@ -601,16 +601,16 @@ static int hs_check(const salt_hyper_stencil_args* a) {
     const int es = a->dtype == SALT_F32 ? 4 : 2;
     if (a->dtype != SALT_F32 && a->dtype != SALT_BF16) SALT_FAIL(SALT_E_BADARG, "hyper_stencil: dtype %d", a->dtype);
     const salt_view& y = a->y;
-    if (y.C % 8 || y.cs % 8 || (reinterpret_cast<uintptr_t>(y.p) & 15)) SALT_FAIL(SALT_E_UNSUPPORTED, "hyper_stencil: y needs C and cs multiples of 8 and a 16-byte aligned pointer");
+    if (!view_vec(y, 8)) SALT_FAIL(SALT_E_UNSUPPORTED, "hyper_stencil: y needs C and cs multiples of 8 and a 16-byte aligned pointer");
     if (a->y_in.p) {
         const salt_view& v = a->y_in;
-        if (v.B != y.B || v.H != y.H || v.W != y.W || v.C != y.C || v.cs % 8 || (reinterpret_cast<uintptr_t>(v.p) & 15)) SALT_FAIL(SALT_E_BADARG, "hyper_stencil: y_in does not match y");
+        if (v.B != y.B || v.H != y.H || v.W != y.W || v.C != y.C || v.cs % 8 || !aligned16(v.p)) SALT_FAIL(SALT_E_BADARG, "hyper_stencil: y_in does not match y");
     }
     for (int k = 0; k < a->nlev; ++k) {
         const salt_view& z = a->z[k];
         const int R = a->R[k];
         if (!view_ok(z) || R < 4 || R > 32 || (R & (R - 1)) || z.B != y.B || z.H * R != y.H || z.W * R != y.W || z.C != 9 * y.C || z.cs % 8 ||
-            (reinterpret_cast<uintptr_t>(z.p) & 15))
+            !aligned16(z.p))
             SALT_FAIL(SALT_E_BADARG, "hyper_stencil: level %d: z must be [B, H / R, W / R, 9 C] with R a power of two in 4..32, cs %% 8 == 0, 16-byte aligned", k);
         if ((int64_t)z.B * z.H * z.W * z.cs * es >= (1LL << 40)) SALT_FAIL(SALT_E_UNSUPPORTED, "hyper_stencil: level too large");
     }
@@ -656,8 +656,7 @@ extern "C" int salt_hyper_stencil(const salt_hyper_stencil_args* a, void* stream
         if (rc) return rc;
         if (p.head_y && p.cblocks > 1) {
             const int64_t hw = (int64_t)y.H * y.W, total = (int64_t)y.B * p.head_co * hw;
-            hipLaunchKernelGGL(head_sum_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, p.head_ws, p.head_b, p.head_y, p.cblocks, p.head_co, hw, total);
-            SALT_CHECK_LAUNCH();
+            return salt_launch(head_sum_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, p.head_ws, p.head_b, p.head_y, p.cblocks, p.head_co, hw, total);
         }
         return SALT_OK;
     }

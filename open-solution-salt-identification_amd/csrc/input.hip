@@ -114,7 +114,5 @@ extern "C" int salt_preprocess(const salt_preprocess_args* a, void* stream) {
     }
     const int64_t n = (int64_t)a->B * a->H * a->W;
     const int blocks = (int)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
-    hipLaunchKernelGGL(preprocess_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, p);
-    SALT_CHECK_LAUNCH();
-    return SALT_OK;
+    return salt_launch(preprocess_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, p);
 }

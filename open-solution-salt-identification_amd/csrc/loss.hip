@@ -598,20 +598,14 @@ extern "C" int salt_lovasz_hinge(const salt_lovasz_args* a, void* stream) {
         hipStream_t st = (hipStream_t)stream;
         LovaszSplit sp{S, a->ws_split, a->ws_split + (int64_t)3 * a->B * S * 256, reinterpret_cast<float*>(a->ws_split + (int64_t)3 * a->B * S * 256 + (int64_t)a->B * S)};
         const dim3 grid(a->B * S);
-        hipLaunchKernelGGL(lovasz_keys_kernel, grid, dim3(ST), 0, st, *a, sp);
+        SALT_TRY(salt_launch(lovasz_keys_kernel, grid, dim3(ST), 0, st, *a, sp));
         const size_t lds = (size_t)(S * 256 + S) * sizeof(unsigned);
-        for (int pass = 0; pass < 4; ++pass) hipLaunchKernelGGL(lovasz_pass_kernel, grid, dim3(ST), lds, st, *a, sp, pass);
-        hipLaunchKernelGGL(lovasz_scan_kernel, grid, dim3(ST), 0, st, *a, sp);
-        SALT_CHECK_LAUNCH();
-        hipLaunchKernelGGL(lovasz_mean_split_kernel, dim3(1), dim3(256), 0, st, sp.part, a->B, S, a->loss_scale, a->loss_per_image, a->loss);
-        SALT_CHECK_LAUNCH();
-        return SALT_OK;
+        for (int pass = 0; pass < 4; ++pass) SALT_TRY(salt_launch(lovasz_pass_kernel, grid, dim3(ST), lds, st, *a, sp, pass));
+        SALT_TRY(salt_launch(lovasz_scan_kernel, grid, dim3(ST), 0, st, *a, sp));
+        return salt_launch(lovasz_mean_split_kernel, dim3(1), dim3(256), 0, st, sp.part, a->B, S, a->loss_scale, a->loss_per_image, a->loss);
     }
-    hipLaunchKernelGGL(lovasz_pf_kernel, dim3(a->B), dim3(LT), 0, (hipStream_t)stream, *a);
-    SALT_CHECK_LAUNCH();
-    hipLaunchKernelGGL(mean_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, a->loss_per_image, a->B, a->loss_scale, a->loss);
-    SALT_CHECK_LAUNCH();
-    return SALT_OK;
+    SALT_TRY(salt_launch(lovasz_pf_kernel, dim3(a->B), dim3(LT), 0, (hipStream_t)stream, *a));
+    return salt_launch(mean_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, a->loss_per_image, a->B, a->loss_scale, a->loss);
 }
 
 extern "C" int salt_bce_dice_parts(const salt_bce_dice_args* a) {
@@ -625,15 +619,12 @@ extern "C" int salt_bce_dice(const salt_bce_dice_args* a, void* stream) {
     const int ppp = bce_ppp(a->HW, &per);
     if (a->nparts != a->B * a->C * ppp) SALT_FAIL(SALT_E_BADARG, "bce_dice: nparts %d, expected %d", a->nparts, a->B * a->C * ppp);
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(bce_dice_partial_kernel, dim3(a->nparts), dim3(256), 0, st, a->logits, a->target, a->HW, ppp, per, a->partials);
-    SALT_CHECK_LAUNCH();
-    hipLaunchKernelGGL(bce_dice_finalize_kernel, dim3(1), dim3(64), 0, st, a->partials, a->B, a->C, ppp, a->HW, a->dice_weight, a->bce_weight, a->loss_scale, a->sums, a->loss);
-    SALT_CHECK_LAUNCH();
+    SALT_TRY(salt_launch(bce_dice_partial_kernel, dim3(a->nparts), dim3(256), 0, st, a->logits, a->target, a->HW, ppp, per, a->partials));
+    SALT_TRY(salt_launch(bce_dice_finalize_kernel, dim3(1), dim3(64), 0, st, a->partials, a->B, a->C, ppp, a->HW, a->dice_weight, a->bce_weight, a->loss_scale, a->sums, a->loss));
     if (a->dlogits) {
         const int64_t n = (int64_t)a->B * a->C * a->HW;
         const int blocks = (int)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
-        hipLaunchKernelGGL(bce_dice_grad_kernel, dim3(blocks), dim3(256), 0, st, a->logits, a->target, a->B, a->C, a->HW, a->sums, a->dice_weight, a->bce_weight, a->loss_scale, a->dlogits);
-        SALT_CHECK_LAUNCH();
+        SALT_TRY(salt_launch(bce_dice_grad_kernel, dim3(blocks), dim3(256), 0, st, a->logits, a->target, a->B, a->C, a->HW, a->sums, a->dice_weight, a->bce_weight, a->loss_scale, a->dlogits));
     }
     return SALT_OK;
 }
@@ -641,20 +632,16 @@ extern "C" int salt_bce_dice(const salt_bce_dice_args* a, void* stream) {
 extern "C" int salt_adam(const salt_adam_args* a, void* stream) {
     if (!a || !a->param || !a->grad || !a->exp_avg || !a->exp_avg_sq || !a->hyper || a->n < 0) SALT_FAIL(SALT_E_BADARG, "adam: bad args");
     if (a->n == 0) return SALT_OK;
-    if ((reinterpret_cast<uintptr_t>(a->param) | reinterpret_cast<uintptr_t>(a->grad) | reinterpret_cast<uintptr_t>(a->exp_avg) | reinterpret_cast<uintptr_t>(a->exp_avg_sq)) & 15)
+    if (!aligned16(a->param, a->grad, a->exp_avg, a->exp_avg_sq))
         SALT_FAIL(SALT_E_BADARG, "adam: buffers must be 16-byte aligned");
     const int64_t n4 = (a->n + 3) / 4;
     const int blocks = (int)((n4 + 255) / 256 < 4096 ? (n4 + 255) / 256 : 4096);
-    hipLaunchKernelGGL(adam_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, a->param, a->grad, a->exp_avg, a->exp_avg_sq, a->n, a->hyper);
-    SALT_CHECK_LAUNCH();
-    return SALT_OK;
+    return salt_launch(adam_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, a->param, a->grad, a->exp_avg, a->exp_avg_sq, a->n, a->hyper);
 }
 
 extern "C" int salt_adam_tick(const salt_adam_tick_args* a, void* stream) {
     if (!a || !a->hyper || !a->step) SALT_FAIL(SALT_E_BADARG, "adam_tick: bad args");
-    hipLaunchKernelGGL(adam_tick_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, a->hyper, a->step);
-    SALT_CHECK_LAUNCH();
-    return SALT_OK;
+    return salt_launch(adam_tick_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, a->hyper, a->step);
 }
 
 extern "C" int salt_tta_mean(const salt_tta_mean_args* a, void* stream) {
@@ -671,18 +658,14 @@ extern "C" int salt_tta_mean(const salt_tta_mean_args* a, void* stream) {
     }
     const int64_t n = (int64_t)a->B * a->C * a->H * a->W;
     const int blocks = (int)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
-    hipLaunchKernelGGL(tta_mean_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, p);
-    SALT_CHECK_LAUNCH();
-    return SALT_OK;
+    return salt_launch(tta_mean_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, p);
 }
 
 extern "C" int salt_flip(const salt_flip_args* a, void* stream) {
     if (!a || !a->x || !a->y) SALT_FAIL(SALT_E_BADARG, "flip: bad args");
     const int64_t n = (int64_t)a->B * a->C * a->H * a->W;
     const int blocks = (int)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
-    hipLaunchKernelGGL(flip_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, *a);
-    SALT_CHECK_LAUNCH();
-    return SALT_OK;
+    return salt_launch(flip_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, *a);
 }
 
 static bool crop_ok(int B, int C, int H, int W, int cls, int top, int left, int h, int w) {
@@ -693,9 +676,7 @@ extern "C" int salt_crop_threshold(const salt_crop_threshold_args* a, void* stre
     if (!a || !a->prob || !a->mask || !crop_ok(a->B, a->C, a->H, a->W, a->cls, a->top, a->left, a->h, a->w)) SALT_FAIL(SALT_E_BADARG, "crop_threshold: bad args");
     const int64_t n = (int64_t)a->B * a->h * a->w;
     const int blocks = (int)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
-    hipLaunchKernelGGL(crop_threshold_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, *a);
-    SALT_CHECK_LAUNCH();
-    return SALT_OK;
+    return salt_launch(crop_threshold_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, *a);
 }
 
 extern "C" int salt_iou_sweep(const salt_iou_sweep_args* a, void* stream) {
@@ -704,7 +685,5 @@ extern "C" int salt_iou_sweep(const salt_iou_sweep_args* a, void* stream) {
     IouKP k;
     k.a = *a;
     for (int t = 0; t < SALT_MAX_THRESHOLDS; ++t) k.th[t] = t < a->T ? a->thresholds[t] : 2.0;
-    hipLaunchKernelGGL(iou_sweep_kernel, dim3(a->B), dim3(256), 0, (hipStream_t)stream, k);
-    SALT_CHECK_LAUNCH();
-    return SALT_OK;
+    return salt_launch(iou_sweep_kernel, dim3(a->B), dim3(256), 0, (hipStream_t)stream, k);
 }

@@ -84,7 +84,7 @@ struct EventPool {
 };
 thread_local EventPool g_events;
 thread_local hipEvent_t g_fork_event = nullptr;
-thread_local bool g_capturing = false;         // hipExtLaunchKernelGGL stop events are not capturable: plain event forks while a graph records
+thread_local bool g_capturing = false;         // the stop event of a salt_launch_ev launch is not capturable: plain event forks while a graph records
 // Side-stream entries are issued behind one fork per this many groups.  Eager run: 1, a fork per layer that rides on the producing
 // kernel's completion signal (6.18 ms per step; explicit event record 6.25, one fork per two layers 6.30).  While a hipGraph is captured: 8 (a
 // cross-stream edge of a replayed graph stalls the main branch ~10 us, a live event does not).
@@ -271,9 +271,7 @@ extern "C" int salt_zero(const salt_zero_args* a, void* stream) {
     if (a->bytes == 0) return SALT_OK;
     const int64_t n4 = a->bytes / 4;
     const int blocks = (int)((n4 + 255) / 256 < 2048 ? (n4 + 255) / 256 : 2048);
-    hipLaunchKernelGGL(zero_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (uint32_t*)a->p, n4);
-    SALT_CHECK_LAUNCH();
-    return SALT_OK;
+    return salt_launch(zero_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (uint32_t*)a->p, n4);
 }
 
 // sizeof() of every struct of saltnet.h in declaration order: the Python host compares them with its

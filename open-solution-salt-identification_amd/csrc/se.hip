@@ -9,12 +9,6 @@
 
 namespace {
 
-template <typename T> struct P16 {
-    static constexpr int N = Elem<T>::VE;
-    static __device__ __forceinline__ void ld(const T* p, float* f) { unpack16<T>(*reinterpret_cast<const u32x4*>(p), f); }
-    static __device__ __forceinline__ void st(T* p, const float* f) { *reinterpret_cast<u32x4*>(p) = pack16<T>(f); }
-};
-
 // Input transform of the scSE kernels (salt_scse_args.in_fin): x is a raw convolution output and the element the operator sees is
 // a = round_to_storage(relu?(y scale + shift)) - ONE pinned expression in the three kernels that read x, so they agree bit for bit
 // with each other (and with what salt_affine_act would have stored, up to the contraction of its own multiply-add).
@@ -29,7 +23,7 @@ __device__ __forceinline__ void in_transform(float* f, const float* sc, const fl
 // FIN: x is raw - every workgroup finalizes the producer's statistics shards into LDS (fin_forward_consumer), workgroup 0 stores them
 template <typename T, bool FIN = false>
 __global__ __launch_bounds__(256) void gap_partial_kernel(salt_view x, float* partials, int nparts, int pix_per_part, double* acc, BnFin fin, int in_relu) {
-    constexpr int N = P16<T>::N;
+    constexpr int N = Piece<T, true>::N;
     extern __shared__ float sm[];
     const int C = x.C, cpv = C / N, R = 256 / cpv;
     const int b = blockIdx.x / nparts, part = blockIdx.x % nparts;
@@ -48,7 +42,7 @@ __global__ __launch_bounds__(256) void gap_partial_kernel(salt_view x, float* pa
     }
     for (int pix = p0 + row; pix < p1; pix += R) {
         float f[N];
-        P16<T>::ld((const T*)x.p + ((int64_t)b * hw + pix) * x.cs + cv * N, f);
+        Piece<T, true>::ld((const T*)x.p + ((int64_t)b * hw + pix) * x.cs + cv * N, f);
         if constexpr (FIN) in_transform<T, N>(f, sc, sh, in_relu);
 #pragma unroll
         for (int j = 0; j < N; ++j) s[j] += f[j];
@@ -73,7 +67,7 @@ __global__ __launch_bounds__(256) void scse_apply_fc_kernel(salt_view x, const d
                                                             const float* w2, const float* b2, float* gap, float* hidden, float* gate_c,
                                                             const float* ws, const float* bs, float* gate_s, salt_view y, int cpv_log2,
                                                             int nparts, int pix_per_part, const float* in_scale, const float* in_shift, int in_relu) {
-    constexpr int N = P16<T>::N;
+    constexpr int N = Piece<T, true>::N;
     extern __shared__ float sm[];       // [C] gap, [R] hidden, [C] gate
     const int C = x.C, cpv = 1 << cpv_log2, RW = 256 >> cpv_log2;
     const int b = blockIdx.x / nparts, part = blockIdx.x % nparts;
@@ -115,7 +109,7 @@ __global__ __launch_bounds__(256) void scse_apply_fc_kernel(salt_view x, const d
         float f[N];
         float dot = 0.f;
         if (ok) {
-            P16<T>::ld((const T*)x.p + gp * x.cs + cv * N, f);
+            Piece<T, true>::ld((const T*)x.p + gp * x.cs + cv * N, f);
             if (in_scale) in_transform<T, N>(f, isc, ish, in_relu);
 #pragma unroll
             for (int j = 0; j < N; ++j) dot += f[j] * wsv[j];
@@ -125,7 +119,7 @@ __global__ __launch_bounds__(256) void scse_apply_fc_kernel(salt_view x, const d
             const float gs = 1.f / (1.f + __expf(-(dot + bsv)));
 #pragma unroll
             for (int j = 0; j < N; ++j) f[j] = fmaxf(f[j] * (gc[j] + gs), 0.f);
-            P16<T>::st((T*)y.p + gp * y.cs + cv * N, f);
+            Piece<T, true>::st((T*)y.p + gp * y.cs + cv * N, f);
             if (cv == 0) gate_s[gp] = gs;
         }
     }
@@ -159,7 +153,7 @@ __global__ void se_fc_kernel(const float* partials, int nparts, int C, int R, fl
 
 template <typename T>
 __global__ void scse_apply_kernel(salt_view x, const float* gate_c, const float* ws, const float* bs, float* gate_s, salt_view y, int cpv_log2) {
-    constexpr int N = P16<T>::N;
+    constexpr int N = Piece<T, true>::N;
     const int cpv = 1 << cpv_log2;
     const int hw = x.H * x.W;
     const int64_t npix = (int64_t)x.B * hw;
@@ -171,7 +165,7 @@ __global__ void scse_apply_kernel(salt_view x, const float* gate_c, const float*
         float dot = 0.f;
         const bool ok = pix < npix;
         if (ok) {
-            P16<T>::ld((const T*)x.p + pix * x.cs + cv * N, f);
+            Piece<T, true>::ld((const T*)x.p + pix * x.cs + cv * N, f);
 #pragma unroll
             for (int j = 0; j < N; ++j) dot += f[j] * ws[cv * N + j];
         }
@@ -181,7 +175,7 @@ __global__ void scse_apply_kernel(salt_view x, const float* gate_c, const float*
             const int b = (int)(pix / hw);
 #pragma unroll
             for (int j = 0; j < N; ++j) f[j] = fmaxf(f[j] * (gate_c[b * x.C + cv * N + j] + gs), 0.f);
-            P16<T>::st((T*)y.p + pix * y.cs + cv * N, f);
+            Piece<T, true>::st((T*)y.p + pix * y.cs + cv * N, f);
             if (cv == 0) gate_s[pix] = gs;
         }
     }
@@ -198,7 +192,7 @@ __global__ __launch_bounds__(256) void scse_bwd1_kernel(salt_view x, salt_view y
                                                         const float* ws, salt_view dx, int accumulate, float* partials, int nparts,
                                                         int pix_per_part, int cpv_log2, double* acc, const float* in_scale, const float* in_shift, int in_relu,
                                                         const float* bn_mean, const float* bn_invstd) {
-    constexpr int N = P16<T>::N;
+    constexpr int N = Piece<T, true>::N;
     extern __shared__ float sm[];
     const int C = x.C, cpv = 1 << cpv_log2, R = 256 >> cpv_log2;
     const int b = blockIdx.x / nparts, part = blockIdx.x % nparts;
@@ -263,7 +257,7 @@ __global__ __launch_bounds__(256) void scse_bwd1_kernel(salt_view x, salt_view y
             if (accumulate) { float old[N]; unpack16<T>(cur.old, old);
 #pragma unroll
                 for (int j = 0; j < N; ++j) o[j] += old[j]; }
-            P16<T>::st(dst, o);
+            Piece<T, true>::st(dst, o);
             if constexpr (BNB) {
                 if constexpr (sizeof(T) == 2) { const u32x4 v = pack16<T>(o); unpack16<T>(v, o); }     // the value salt_bn_bwd will read
 #pragma unroll
@@ -458,7 +452,7 @@ __global__ __launch_bounds__(256) void se_dgap_kernel(int C, int R, const float*
 
 template <typename T>
 __global__ void bcast_add_kernel(salt_view dx, const float* dgap) {
-    constexpr int N = P16<T>::N;
+    constexpr int N = Piece<T, true>::N;
     const int cpv = dx.C / N;
     const int hw = dx.H * dx.W;
     const int64_t units = (int64_t)dx.B * hw * cpv;
@@ -467,10 +461,10 @@ __global__ void bcast_add_kernel(salt_view dx, const float* dgap) {
         const int b = (int)(pix / hw);
         float f[N];
         T* p = (T*)dx.p + pix * dx.cs + cv * N;
-        P16<T>::ld(p, f);
+        Piece<T, true>::ld(p, f);
 #pragma unroll
         for (int j = 0; j < N; ++j) f[j] += dgap[b * dx.C + cv * N + j];
-        P16<T>::st(p, f);
+        Piece<T, true>::st(p, f);
     }
 }
 
@@ -488,7 +482,7 @@ int scse_nparts(const salt_view& x, int* per) {
 template <typename T> bool se_ok(const salt_view& v) {
     constexpr int VE = Elem<T>::VE;
     const int cpv = v.C / VE;
-    return (v.C % VE) == 0 && (v.cs % VE) == 0 && ((reinterpret_cast<uintptr_t>(v.p) & 15) == 0) && cpv >= 1 && cpv <= 64 && (cpv & (cpv - 1)) == 0;
+    return view_vec(v, VE) && cpv >= 1 && cpv <= 64 && (cpv & (cpv - 1)) == 0;
 }
 
 }  // namespace
@@ -515,30 +509,23 @@ extern "C" int salt_scse(const salt_scse_args* a, void* stream) {
                 SALT_FAIL(SALT_E_BADARG, "scse: in_fin needs gap_acc, in_fin_acc and the complete salt_bn_finalize arguments of a %d-channel layer", C);
             const BnFin fin{const_cast<double*>(a->in_fin_acc), nullptr, f->gamma, f->beta, f->running_mean, f->running_var, f->num_batches_tracked,
                             f->momentum, f->eps, f->mean, f->invstd, f->scale, f->shift};
-            hipLaunchKernelGGL((gap_partial_kernel<T, true>), dim3(a->x.B * nparts), dim3(256), (256 * VE + 2 * C) * sizeof(float), st, a->x, a->gap_partials, nparts, per,
-                               a->gap_acc, fin, a->in_relu);
+            SALT_TRY(salt_launch(gap_partial_kernel<T, true>, dim3(a->x.B * nparts), dim3(256), (256 * VE + 2 * C) * sizeof(float), st, a->x, a->gap_partials, nparts, per,
+                                 a->gap_acc, fin, a->in_relu));
         } else {
-            hipLaunchKernelGGL((gap_partial_kernel<T, false>), dim3(a->x.B * nparts), dim3(256), 256 * VE * sizeof(float), st, a->x, a->gap_partials, nparts, per, a->gap_acc,
-                               BnFin{}, 0);
+            SALT_TRY(salt_launch(gap_partial_kernel<T, false>, dim3(a->x.B * nparts), dim3(256), 256 * VE * sizeof(float), st, a->x, a->gap_partials, nparts, per, a->gap_acc,
+                                 BnFin{}, 0));
         }
-        SALT_CHECK_LAUNCH();
-        if (a->gap_acc) {
-            hipLaunchKernelGGL(scse_apply_fc_kernel<T>, dim3(a->x.B * nparts), dim3(256), (2 * C + a->R) * sizeof(float), st, a->x, a->gap_acc, a->R,
+        if (a->gap_acc)
+            return salt_launch(scse_apply_fc_kernel<T>, dim3(a->x.B * nparts), dim3(256), (2 * C + a->R) * sizeof(float), st, a->x, a->gap_acc, a->R,
                                1.0f / (float)(a->x.H * a->x.W), a->w1, a->b1, a->w2, a->b2, a->gap, a->hidden, a->gate_c, a->ws, a->bs, a->gate_s, a->y,
                                ilog2_ceil(C / VE), nparts, per, f ? f->scale : nullptr, f ? f->shift : nullptr, a->in_relu);
-            SALT_CHECK_LAUNCH();
-            return SALT_OK;
-        }
-        hipLaunchKernelGGL(se_fc_kernel, dim3(a->x.B), dim3(256), (C + a->R) * sizeof(float), st, a->gap_partials, nparts, C, a->R,
-                           1.0f / (float)(a->x.H * a->x.W), a->w1, a->b1, a->w2, a->b2, a->gap, a->hidden, a->gate_c);
-        SALT_CHECK_LAUNCH();
+        SALT_TRY(salt_launch(se_fc_kernel, dim3(a->x.B), dim3(256), (C + a->R) * sizeof(float), st, a->gap_partials, nparts, C, a->R,
+                             1.0f / (float)(a->x.H * a->x.W), a->w1, a->b1, a->w2, a->b2, a->gap, a->hidden, a->gate_c));
         const int cpv_log2 = ilog2_ceil(C / VE);
         const int64_t units = view_pixels(a->x) << cpv_log2;
         const int blocks = (int)((units + 255) / 256 < 4096 ? (units + 255) / 256 : 4096);
-        hipLaunchKernelGGL(scse_apply_kernel<T>, dim3(blocks), dim3(256), 0, st, a->x, a->gate_c, a->ws, a->bs, a->gate_s, a->y, cpv_log2);
+        return salt_launch(scse_apply_kernel<T>, dim3(blocks), dim3(256), 0, st, a->x, a->gate_c, a->ws, a->bs, a->gate_s, a->y, cpv_log2);
     })
-    SALT_CHECK_LAUNCH();
-    return SALT_OK;
 }
 
 // the single-workgroup FC backward over the whole batch (parameter gradients; with write_dgap also dgap and, with bnb_out, the sums)
@@ -583,32 +570,25 @@ extern "C" int salt_scse_bwd(const salt_scse_bwd_args* a, void* stream) {
         if (!se_ok<T>(a->x) || !se_ok<T>(a->y) || !se_ok<T>(a->dy) || !se_ok<T>(a->dx)) SALT_FAIL(SALT_E_UNSUPPORTED, "scse_bwd: layout");
         constexpr int VE = Elem<T>::VE;
         const int cpv_log2 = ilog2_ceil(C / VE);
-        if (bnb) hipLaunchKernelGGL((scse_bwd1_kernel<T, true>), dim3(B * nparts), dim3(256), 1024 * VE * sizeof(float), st, a->x, a->y, a->dy, a->gate_c,
-                                    a->gate_s, a->ws, a->dx, a->accumulate, a->partials, nparts, per, cpv_log2, a->acc, a->in_scale, a->in_shift, a->in_relu,
-                                    a->bn_mean, a->bn_invstd);
-        else hipLaunchKernelGGL((scse_bwd1_kernel<T, false>), dim3(B * nparts), dim3(256), (512 * VE + 256) * sizeof(float), st, a->x, a->y, a->dy, a->gate_c,
-                                a->gate_s, a->ws, a->dx, a->accumulate, a->partials, nparts, per, cpv_log2, a->acc, a->in_scale, a->in_shift, a->in_relu,
-                                nullptr, nullptr);
-        SALT_CHECK_LAUNCH();
-        if (!a->acc) {
-            hipLaunchKernelGGL(se_parts_reduce_kernel, dim3(B), dim3(256), 0, st, a->partials, nparts, 2 * C + 1);
-            SALT_CHECK_LAUNCH();
-        }
+        if (bnb) SALT_TRY(salt_launch(scse_bwd1_kernel<T, true>, dim3(B * nparts), dim3(256), 1024 * VE * sizeof(float), st, a->x, a->y, a->dy, a->gate_c,
+                                      a->gate_s, a->ws, a->dx, a->accumulate, a->partials, nparts, per, cpv_log2, a->acc, a->in_scale, a->in_shift, a->in_relu,
+                                      a->bn_mean, a->bn_invstd));
+        else SALT_TRY(salt_launch(scse_bwd1_kernel<T, false>, dim3(B * nparts), dim3(256), (512 * VE + 256) * sizeof(float), st, a->x, a->y, a->dy, a->gate_c,
+                                  a->gate_s, a->ws, a->dx, a->accumulate, a->partials, nparts, per, cpv_log2, a->acc, a->in_scale, a->in_shift, a->in_relu,
+                                  nullptr, nullptr));
+        if (!a->acc) SALT_TRY(salt_launch(se_parts_reduce_kernel, dim3(B), dim3(256), 0, st, a->partials, nparts, 2 * C + 1));
         if (a->defer_param_grads) {
             // only what the critical queue needs: dgap (+ the producer layer's BatchNorm-backward sums), one workgroup per image
-            hipLaunchKernelGGL(se_dgap_kernel, dim3(B), dim3(256), (size_t)(C + a->R) * sizeof(float), st, C, a->R, a->w1, a->w2, a->hidden, a->gate_c, a->dgap,
-                               1.0f / (float)(a->x.H * a->x.W), a->acc, bnb ? 6 * C + 1 : 2 * C + 1, bnb ? a->bnb_acc : nullptr);
+            SALT_TRY(salt_launch(se_dgap_kernel, dim3(B), dim3(256), (size_t)(C + a->R) * sizeof(float), st, C, a->R, a->w1, a->w2, a->hidden, a->gate_c, a->dgap,
+                                 1.0f / (float)(a->x.H * a->x.W), a->acc, bnb ? 6 * C + 1 : 2 * C + 1, bnb ? a->bnb_acc : nullptr));
         } else {
-            const int rc = launch_se_fc(a, nparts, st, 1, bnb ? a->bnb_acc : nullptr);
-            if (rc) return rc;
+            SALT_TRY(launch_se_fc(a, nparts, st, 1, bnb ? a->bnb_acc : nullptr));
         }
-        SALT_CHECK_LAUNCH();
         if (!a->skip_bcast) {                      // else: the consumer adds dgap[b][c] on the fly (salt_bn_bwd_args.da_bias)
             const int64_t units = view_pixels(a->dx) * (C / VE);
             const int blocks = (int)((units + 255) / 256 < 4096 ? (units + 255) / 256 : 4096);
-            hipLaunchKernelGGL(bcast_add_kernel<T>, dim3(blocks), dim3(256), 0, st, a->dx, a->dgap);
+            SALT_TRY(salt_launch(bcast_add_kernel<T>, dim3(blocks), dim3(256), 0, st, a->dx, a->dgap));
         }
     })
-    SALT_CHECK_LAUNCH();
     return SALT_OK;
 }

@@ -9,12 +9,6 @@
 
 namespace {
 
-template <typename T> struct P16 {
-    static constexpr int N = Elem<T>::VE;
-    static __device__ __forceinline__ void ld(const T* p, float* f) { unpack16<T>(*reinterpret_cast<const u32x4*>(p), f); }
-    static __device__ __forceinline__ void st(T* p, const float* f) { *reinterpret_cast<u32x4*>(p) = pack16<T>(f); }
-};
-
 // the one expression for z in the three kernels that need it (the FC on the pooled mean, the forward apply, the backward reduction): they
 // must agree on the value
 __device__ __forceinline__ float z_of(float x, float sc, float sh) { return __fmaf_rn(x, sc, sh); }
@@ -57,7 +51,7 @@ __device__ __forceinline__ void block_channel_sums(const float* s, float* sm, co
 // forward pass 1: per-image channel sums of the raw x
 template <typename T>
 __global__ __launch_bounds__(256) void se_res_pool_kernel(salt_view x, int nparts, int nchunks, int pix_per_part, int pc_log2, double* acc, float* partials) {
-    constexpr int N = P16<T>::N;
+    constexpr int N = Piece<T, true>::N;
     __shared__ float sm[256 * N];
     const int hw = x.H * x.W;
     const Tile t = tile_of(nparts, nchunks, pix_per_part, hw, pc_log2, N);
@@ -66,7 +60,7 @@ __global__ __launch_bounds__(256) void se_res_pool_kernel(salt_view x, int npart
     for (int j = 0; j < N; ++j) s[j] = 0.f;
     for (int pix = t.p0 + t.row; pix < t.p1; pix += t.rows) {
         float f[N];
-        P16<T>::ld((const T*)x.p + ((int64_t)t.b * hw + pix) * x.cs + t.c, f);
+        Piece<T, true>::ld((const T*)x.p + ((int64_t)t.b * hw + pix) * x.cs + t.c, f);
 #pragma unroll
         for (int j = 0; j < N; ++j) s[j] += f[j];
     }
@@ -127,7 +121,7 @@ __global__ __launch_bounds__(256) void se_res_fc_kernel(const double* acc, const
 template <typename T>
 __global__ __launch_bounds__(256) void se_res_apply_kernel(salt_view x, salt_view res, salt_view y, const float* in_scale, const float* in_shift, const float* gate,
                                                            int nparts, int nchunks, int pix_per_part, int pc_log2) {
-    constexpr int N = P16<T>::N;
+    constexpr int N = Piece<T, true>::N;
     const int hw = x.H * x.W;
     const Tile t = tile_of(nparts, nchunks, pix_per_part, hw, pc_log2, N);
     float g[N], sc[N], sh[N];
@@ -139,11 +133,11 @@ __global__ __launch_bounds__(256) void se_res_apply_kernel(salt_view x, salt_vie
     for (int pix = t.p0 + t.row; pix < t.p1; pix += t.rows) {
         const int64_t gp = (int64_t)t.b * hw + pix;
         float f[N], r[N];
-        P16<T>::ld((const T*)x.p + gp * x.cs + t.c, f);
-        P16<T>::ld((const T*)res.p + gp * res.cs + t.c, r);
+        Piece<T, true>::ld((const T*)x.p + gp * x.cs + t.c, f);
+        Piece<T, true>::ld((const T*)res.p + gp * res.cs + t.c, r);
 #pragma unroll
         for (int j = 0; j < N; ++j) f[j] = fmaxf(__fmaf_rn(g[j], in_scale ? z_of(f[j], sc[j], sh[j]) : f[j], r[j]), 0.f);
-        P16<T>::st((T*)y.p + gp * y.cs + t.c, f);
+        Piece<T, true>::st((T*)y.p + gp * y.cs + t.c, f);
     }
 }
 
@@ -151,7 +145,7 @@ __global__ __launch_bounds__(256) void se_res_apply_kernel(salt_view x, salt_vie
 template <typename T>
 __global__ __launch_bounds__(256) void se_res_bwd_reduce_kernel(salt_view x, salt_view y, salt_view dy, const float* in_scale, const float* in_shift, int nparts,
                                                                 int nchunks, int pix_per_part, int pc_log2, double* acc, float* partials) {
-    constexpr int N = P16<T>::N;
+    constexpr int N = Piece<T, true>::N;
     __shared__ float sm[256 * N];
     const int hw = x.H * x.W;
     const Tile t = tile_of(nparts, nchunks, pix_per_part, hw, pc_log2, N);
@@ -161,9 +155,9 @@ __global__ __launch_bounds__(256) void se_res_bwd_reduce_kernel(salt_view x, sal
     for (int pix = t.p0 + t.row; pix < t.p1; pix += t.rows) {
         const int64_t gp = (int64_t)t.b * hw + pix;
         float f[N], o[N], d[N];
-        P16<T>::ld((const T*)x.p + gp * x.cs + t.c, f);
-        P16<T>::ld((const T*)y.p + gp * y.cs + t.c, o);
-        P16<T>::ld((const T*)dy.p + gp * dy.cs + t.c, d);
+        Piece<T, true>::ld((const T*)x.p + gp * x.cs + t.c, f);
+        Piece<T, true>::ld((const T*)y.p + gp * y.cs + t.c, o);
+        Piece<T, true>::ld((const T*)dy.p + gp * dy.cs + t.c, d);
 #pragma unroll
         for (int j = 0; j < N; ++j) {
             const float z = in_scale ? z_of(f[j], sc[j], sh[j]) : f[j];
@@ -217,7 +211,7 @@ __global__ __launch_bounds__(256) void se_res_fc_bwd_kernel(const double* acc, c
 template <typename T>
 __global__ __launch_bounds__(256) void se_res_bwd_apply_kernel(salt_view y, salt_view dy, const float* gate, const float* dgap, salt_view dx, salt_view dres,
                                                                int accumulate_dres, int nparts, int nchunks, int pix_per_part, int pc_log2) {
-    constexpr int N = P16<T>::N;
+    constexpr int N = Piece<T, true>::N;
     const int hw = y.H * y.W;
     const Tile t = tile_of(nparts, nchunks, pix_per_part, hw, pc_log2, N);
     float g[N], dg[N];
@@ -226,20 +220,20 @@ __global__ __launch_bounds__(256) void se_res_bwd_apply_kernel(salt_view y, salt
     for (int pix = t.p0 + t.row; pix < t.p1; pix += t.rows) {
         const int64_t gp = (int64_t)t.b * hw + pix;
         float o[N], d[N], q[N];
-        P16<T>::ld((const T*)y.p + gp * y.cs + t.c, o);
-        P16<T>::ld((const T*)dy.p + gp * dy.cs + t.c, d);
+        Piece<T, true>::ld((const T*)y.p + gp * y.cs + t.c, o);
+        Piece<T, true>::ld((const T*)dy.p + gp * dy.cs + t.c, d);
 #pragma unroll
         for (int j = 0; j < N; ++j) d[j] = o[j] > 0.f ? d[j] : 0.f;
         T* pr = (T*)dres.p + gp * dres.cs + t.c;
         if (accumulate_dres) {
-            P16<T>::ld(pr, q);
+            Piece<T, true>::ld(pr, q);
 #pragma unroll
             for (int j = 0; j < N; ++j) q[j] += d[j];
-            P16<T>::st(pr, q);
-        } else P16<T>::st(pr, d);
+            Piece<T, true>::st(pr, q);
+        } else Piece<T, true>::st(pr, d);
 #pragma unroll
         for (int j = 0; j < N; ++j) q[j] = __fmaf_rn(d[j], g[j], dg[j]);
-        P16<T>::st((T*)dx.p + gp * dx.cs + t.c, q);
+        Piece<T, true>::st((T*)dx.p + gp * dx.cs + t.c, q);
     }
 }
 
@@ -293,7 +287,7 @@ template <typename T> bool plan_of(const salt_view& x, Plan* p, const char* who)
 
 template <typename T> bool layout_ok(const salt_view& v, const salt_view& like) {
     constexpr int VE = Elem<T>::VE;
-    return view_ok(v) && v.B == like.B && v.H == like.H && v.W == like.W && v.C == like.C && (v.cs % VE) == 0 && (reinterpret_cast<uintptr_t>(v.p) & 15) == 0 &&
+    return view_ok(v) && v.B == like.B && v.H == like.H && v.W == like.W && v.C == like.C && (v.cs % VE) == 0 && aligned16(v.p) &&
            (int64_t)v.B * v.H * v.W * v.cs < (1LL << 31);
 }
 
@@ -322,7 +316,7 @@ extern "C" int salt_se_res(const salt_se_res_args* a, void* stream) {
         Plan p;
         if (!plan_of<T>(a->x, &p, "se_res")) return SALT_E_UNSUPPORTED;
         if (R != C / 16) SALT_FAIL(SALT_E_UNSUPPORTED, "se_res: R = %d, C / 16 = %d is supported", R, C / 16);
-        if (reinterpret_cast<uintptr_t>(a->w2) & 15) SALT_FAIL(SALT_E_UNSUPPORTED, "se_res: w2 must be 16-byte aligned");
+        if (!aligned16(a->w2)) SALT_FAIL(SALT_E_UNSUPPORTED, "se_res: w2 must be 16-byte aligned");
         if (!layout_ok<T>(a->x, a->x) || !layout_ok<T>(a->res, a->x) || !layout_ok<T>(a->y, a->x))
             SALT_FAIL(SALT_E_UNSUPPORTED, "se_res: x / res / y must be 16-byte aligned views of one shape, cs a multiple of the 16-byte piece");
         if (a->nparts != p.nparts) SALT_FAIL(SALT_E_BADARG, "se_res: nparts %d, expected %d", a->nparts, p.nparts);

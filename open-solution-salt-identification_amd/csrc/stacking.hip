@@ -283,7 +283,7 @@ int stack_shape_check(const salt_stack_conv_args* a) {
 
 template <typename T>
 int stack_launch(const salt_stack_conv_args* a, StackKP p, hipStream_t st) {
-    constexpr int KS = StackT<T>::KS, PAD = StackT<T>::PAD, VE = Elem<T>::VE;
+    constexpr int KS = StackT<T>::KS, PAD = StackT<T>::PAD;
     const size_t es = sizeof(T);
     const bool train = a->y.p != nullptr;
     p.Kp = (a->M + KS - 1) / KS * KS;
@@ -299,10 +299,8 @@ int stack_launch(const salt_stack_conv_args* a, StackKP p, hipStream_t st) {
     const size_t lds = fixed + (size_t)9 * a->F * p.SWT * es;
     if (lds > 160 * 1024) SALT_FAIL(SALT_E_LDS, "stack_conv: needs %zu bytes of LDS", lds);
     if (train) {
-        if (!view_ok(a->y) || a->y.B != a->B || a->y.H != a->H || a->y.W != a->W || a->y.C != a->F || (a->y.cs % VE) || (reinterpret_cast<uintptr_t>(a->y.p) & 15))
-            SALT_FAIL(SALT_E_BADARG, "stack_conv: y must be an aligned [%d,%d,%d,%d] view", a->B, a->H, a->W, a->F);
-        if (!view_ok(a->xs) || a->xs.B != a->B || a->xs.H != a->H || a->xs.W != a->W || a->xs.C != p.Mpad || (a->xs.cs % VE) || (reinterpret_cast<uintptr_t>(a->xs.p) & 15))
-            SALT_FAIL(SALT_E_BADARG, "stack_conv: xs must be an aligned [%d,%d,%d,%d] view", a->B, a->H, a->W, p.Mpad);
+        SALT_TRY(view_check16("stack_conv", "y", a->y, a->dtype, a->B, a->H, a->W, a->F));
+        SALT_TRY(view_check16("stack_conv", "xs", a->xs, a->dtype, a->B, a->H, a->W, p.Mpad));
         if (!a->stats || !a->stats_cnt) SALT_FAIL(SALT_E_BADARG, "stack_conv: the train form needs the stats workspaces");
         p.y_cs = a->y.cs; p.xs_cs = a->xs.cs;
     }
@@ -347,7 +345,5 @@ extern "C" int salt_stack_conv(const salt_stack_conv_args* a, void* stream) {
 extern "C" int salt_stack_grad_unfold(const salt_stack_grad_unfold_args* a, void* stream) {
     if (!a || !a->gpad || !a->grad || a->F < 1 || a->M < 1 || a->Mpad < a->M) SALT_FAIL(SALT_E_BADARG, "stack_grad_unfold: bad args");
     const int total = a->F * a->M * 9;
-    hipLaunchKernelGGL(stack_grad_unfold_kernel, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream, a->gpad, a->F, a->M, a->Mpad, a->grad, a->accumulate);
-    SALT_CHECK_LAUNCH();
-    return SALT_OK;
+    return salt_launch(stack_grad_unfold_kernel, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream, a->gpad, a->F, a->M, a->Mpad, a->grad, a->accumulate);
 }

@@ -457,6 +457,28 @@ def test_dynamic_lds_limit_is_raised_in_one_place():
     assert users == ['common.h'], users
 
 
+def test_launches_and_shared_helpers_live_in_common_h():
+    """Every kernel launch goes through common.h's salt_launch / salt_launch_ev (no other file of csrc/ spells a launch or its check),
+    and the shared device helpers - Piece, Mma, the 64-byte-row swizzle - are defined there and nowhere else; their former copies
+    (Unit, P16) are gone."""
+    import glob
+    import re
+    src = {os.path.basename(fn): open(fn).read() for fn in glob.glob(os.path.join(PKG, 'csrc', '*.*'))
+           if os.path.isfile(fn) and fn.endswith(('.hip', '.h', '.py'))}
+    assert 'common.h' in src and len(src) > 20
+    for word in ('hipLaunchKernelGGL', 'hipExtLaunchKernelGGL', 'SALT_CHECK_LAUNCH'):
+        users = sorted(fn for fn, text in src.items() if word in text)
+        assert users == ['common.h'], (word, users)
+    swizzle = r'int\s+\w+\(int row, int slot\)\s*\{\s*return row \* 64'
+    for what, pattern in (('Piece', r'struct\s+Piece\b'), ('Mma', r'struct\s+Mma\b'), ('swizzle', swizzle)):
+        owners = sorted(fn for fn, text in src.items() if re.search(pattern, text))
+        assert owners == ['common.h'], (what, owners)
+    assert len(re.findall(swizzle, src['common.h'])) == 1
+    for gone in (r'struct\s+Unit\b', r'struct\s+P16\b'):
+        owners = sorted(fn for fn, text in src.items() if re.search(gone, text))
+        assert owners == [], (gone, owners)
+
+
 def test_builder_state_is_declared_not_probed_with_getattr_defaults():
     """The graph builder's peephole state is declared in the __init__ of its class (engine.py / runtime.py: neutral value + who writes
     and who reads it) and read as a plain attribute.  A getattr() WITH a default on one of these names means an attribute that only
