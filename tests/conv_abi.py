@@ -29,6 +29,7 @@ A dropped corner tap moves an element by about |x w| ~ A / K, i.e. >= 2^23 / K^2
 import ctypes
 import math
 
+import pytest
 import torch
 
 from op_reference import F64, GUARD, Placed, guard_fill, make_view, pad_fold, round_to    # noqa: F401  (re-exported for the tests)
@@ -206,6 +207,18 @@ def ratio(got, ref):
     return float(torch.nan_to_num(r, nan=float('inf'), posinf=float('inf')).max())
 
 
+def ratio_strict(got, ref):
+    """max |got - exact| / tol over ALL elements (NaN / inf in `got` -> inf; an element with tol = 0 must be exact)"""
+    d = (got.double() - ref['exact']).abs()
+    r = torch.where(ref['tol'] > 0, d / ref['tol'].clamp_min(1e-300), torch.where(d == 0, torch.zeros_like(d), torch.full_like(d, float('inf'))))
+    return float(torch.nan_to_num(r, nan=float('inf'), posinf=float('inf')).max())
+
+
+def store_tol(e, tol, dtype):
+    """tol of the value e after one storage rounding (the grouped and dense convolution references; _store above also rounds)"""
+    return tol + UBF * (e.abs() + tol) if dtype == 'bf16' else tol
+
+
 # ---------------------------------------------------------------- C-ABI
 def pack(w, dtype, tap_k, transpose=0):
     """w: fp32 master [D0][D1][KH][KW] on the device; tap_k [(kh, kw) | None] -> packed device tensor."""
@@ -277,3 +290,207 @@ def moments(y, dtype):
     eps = UBF * (1 + 2 * UBF) if dtype == 'bf16' else 0.0
     q = (y * y).sum(0)
     return y.sum(0), q, (eps + N * U32) * y.abs().sum(0), (2 * eps + eps * eps + 2 * N * U32) * q
+
+
+# ---------------------------------------------------------------- the case table of test_gpu_conv_abi.py / test_conv_reference_cpu.py
+BM = {1: 128, 2: 256, 3: 128, 4: 128, 5: 64}
+K3, K3R = k3_taps(0), k3_taps(1)
+K1 = [(0, 0, 0, 0)]
+K13 = [(0, kw, 0, kw - 1) for kw in range(3)]                     # a (1, 3) kernel, padding (0, 1)
+
+
+def case(name, kid, dtype, B, Cin, Cout, H, W, taps, **kw):
+    c = dict(name=name, kid=kid, dtype=dtype, B=B, Cin=Cin, Cout=Cout, H=H, W=W, taps=taps, transpose=0, in_step=1, pad_mode=0, OH=None, OW=None,
+             out_step=1, out_oy=0, out_ox=0, yH=None, yW=None, cfg=kid, xv=None, yv=None, bias=False, scale=False, shift=False, relu=False,
+             res=False, acc=False, fold=None, gen=None, regime=None, tile=None, seed=1, KH=None, KW=None, in_tf=None)
+    c.update(kw)
+    s = c['in_step']
+    if c['OH'] is None:
+        c['OH'], c['OW'] = ((H - 1) // s + 1, (W - 1) // s + 1) if not c['fold'] else (H + c['fold'][1], W + c['fold'][2])
+    if c['yH'] is None:
+        if c['fold']:
+            c['yH'], c['yW'] = H, W
+        else:
+            c['yH'], c['yW'] = c['OH'] * c['out_step'], c['OW'] * c['out_step']
+    if c['KH'] is None:
+        c['KH'], c['KW'] = max(t[0] for t in taps) + 1, max(t[1] for t in taps) + 1
+    c['xv'] = c['xv'] or (0, Cin)
+    c['yv'] = c['yv'] or (0, Cout)
+    return pytest.param(c, id=name)
+
+
+# forced configs whose halo does not fit the tile's loader budget fall back to config 5 (64-pixel tiles): asserted, not assumed
+HALO_FALLBACK = {(2, 'ragged'), (2, 'ragged-replicate'), (2, 'accumulate-ragged'), (2, '160-64-8x8-b5'), (2, 's2-k1-32-48'), (2, '4x4-b16'),
+                 (2, '2x2-b5'), (2, '3x4-b3'), (2, 's2-k3-17x31'), (1, 's2-k3-15x13')}
+CASES = []
+for dt in ('f32', 'bf16'):
+    for kid in (1, 2, 3, 4, 5):
+        def add(shape, *a, **kw):
+            k = kw.pop('runs', 5 if (kid, shape) in HALO_FALLBACK else kid)
+            CASES.append(case('%s-cfg%d-%s' % (dt, kid, shape), k, dt, *a, cfg=kid, **kw))
+        # ragged: scalar load_piece path (cs 13 / 10), partial tiles, partial batch tile
+        add('ragged', 3, 13, 10, 7, 5, K3, regime='nt9')
+        add('ragged-replicate', 3, 13, 10, 7, 5, K3R, pad_mode=1, regime='nt9')
+        add('ragged-1tap', 3, 13, 10, 7, 5, K1, regime='nt0')
+        # whole 16-byte pieces
+        add('40-72-33x17', 2, 40, 72, 33, 17, K3)
+        add('64-64-16x16', 2, 64, 64, 16, 16, K3)
+        add('160-64-8x8-b5', 5, 160, 64, 8, 8, K3R, pad_mode=1)
+        add('1x3-24-40', 2, 24, 40, 9, 11, K13, regime='nt0')
+        # stride 2: a 16 x 8 tile reads a 33 x 17 halo, the most a 128-pixel tile's loader holds; 8 x 8 tiles x 2 images do not fit
+        add('s2-k3-17x31', 2, 32, 48, 17, 31, K3, in_step=2)
+        if kid in (1, 5):
+            add('s2-k3-15x13', 2, 32, 48, 15, 13, K3, in_step=2)
+        add('s2-k1-32-48', 2, 32, 48, 8, 8, K1, in_step=2, regime='nt0')
+        # 1x1: Cin a multiple of four chunks -> 4 virtual taps (config 2 falls back to 1), else 1
+        add('1x1-vt4', 2, 128 if dt == 'bf16' else 64, 40, 9, 11, K1, runs=1 if kid == 2 else kid, regime='nt4' if dt == 'f32' or kid == 5 else 'ilv4')
+        add('1x1-vt1', 2, 96, 40, 9, 11, K1, regime='nt0')
+        # many images per tile
+        add('4x4-b16', 16, 24, 40, 4, 4, K3)
+        add('2x2-b5', 5, 24, 40, 2, 2, K3)
+        add('3x4-b3', 3, 24, 40, 3, 4, K3R, pad_mode=1)
+        # views: x at channel offset 4 of a wider buffer (bf16: 8 bytes past a 16-byte boundary), y a window with guard channels
+        add('x-misaligned', 2, 40, 24, 9, 11, K3, xv=(4, 56), regime='nt9')
+        add('y-window', 2, 40, 24, 9, 11, K3, yv=(8, 48))
+        add('y-window-ragged', 2, 24, 13, 9, 11, K3, yv=(3, 21))
+        # epilogue: the header's combinations, with scale in [0.5, 2] (both signs) and shift of the order of the output
+        add('bias-relu', 2, 24, 37, 9, 11, K3, bias=True, relu=True)
+        add('scale-shift', 2, 24, 37, 9, 11, K3, scale=True, shift=True)
+        add('bias-scale-shift-relu', 2, 24, 37, 9, 11, K3, bias=True, scale=True, shift=True, relu=True)
+        add('res-relu', 2, 24, 40, 9, 11, K3, scale=True, shift=True, relu=True, res=True)
+        add('res-full-tiles', 2, 32, 64, 16, 16, K3, bias=True, res=True)
+        add('accumulate', 2, 24, 40, 9, 11, K3, acc=True)
+        add('accumulate-ragged', 3, 13, 10, 7, 5, K3, acc=True)
+        add('accumulate-full-tiles', 2, 32, 64, 16, 16, K3, acc=True)
+
+# the interleaved loader's three halo budgets on config 2 (256-pixel tiles, MAXA_T 6) and 1 / 3 / 4 (128-pixel tiles, MAXA_T 3 | 9)
+CASES += [
+    case('bf16-cfg2-ilv6', 2, 'bf16', 1, 64, 64, 16, 16, K3, regime='ilv9-6'),
+    case('bf16-cfg1-ilv9', 1, 'bf16', 5, 160, 64, 8, 8, K3, regime='ilv9-9'),
+    case('bf16-cfg1-ilv3', 1, 'bf16', 2, 40, 72, 33, 17, K3, regime='ilv9-3'),
+    case('bf16-cfg4-ilv3', 4, 'bf16', 2, 64, 64, 16, 16, K3, regime='ilv9-3'),
+    case('bf16-cfg3-ilv9', 3, 'bf16', 16, 24, 40, 4, 4, K3, regime='ilv9-9'),
+]
+
+# ---- output placement: the four out_step = 2 launches of ConvTranspose2d k4 (4 taps each) and k3 (4, 2, 2, 1 taps)
+for dt in ('f32', 'bf16'):
+    for K in (4, 3):
+        for kid in ((1, 4, 5) if dt == 'f32' else (1, 4, 5, 6, 7, 8)):
+            for fy, fx, sel in convt_phases(K):
+                if kid >= 6 and len(sel) != 4:
+                    continue                                               # conv_glds_kernel: 9 or 4 taps
+                CASES.append(case('%s-cfg%d-convt-k%d-phase%d%d' % (dt, kid, K, fy, fx), kid, dt, 2, 32, 40, 9, 5, sel, transpose=1, KH=K, KW=K,
+                                  out_step=2, out_oy=fy, out_ox=fx, bias=True, seed=7))
+    # stride-2 data gradient of a k3 convolution, phase by phase, onto random y
+    for ay, ax, sel in dgrad_s2_phases(K3):
+        CASES.append(case('%s-cfg4-dgrad-s2-phase%d%d-accumulate' % (dt, ay, ax), 4, dt, 2, 40, 24, 5, 6, sel, transpose=1, KH=3, KW=3,
+                          out_step=2, out_oy=ay, out_ox=ax, acc=True, seed=9))
+    # stride-1 data gradient (mirrored taps, transposed weights) and the strip / fused folds of the replicate-padded one
+    CASES.append(case('%s-cfg1-dgrad-s1' % dt, 1, dt, 2, 40, 24, 9, 11, dgrad_taps(K3), transpose=1, acc=True))
+    for kid in (1, 4, 5):
+        CASES.append(case('%s-cfg%d-fold-strip' % (dt, kid), kid, dt, 2, 40, 24, 9, 7, dgrad_taps_extended(K3R, 2), transpose=1,
+                          fold=('strip', 2, 2)))
+    for kid, H_, W_, B_, gen in ((1, 8, 8, 2, 1), (1, 16, 16, 2, 1), (4, 16, 16, 2, 1), (1, 12, 20, 2, 1), (2, 12, 20, 1, None), (4, 5, 7, 3, 1),
+                                 (5, 8, 8, 2, None), (3, 16, 16, 2, 1)):
+        for acc in (False, True):
+            CASES.append(case('%s-cfg%d-fold-fused-%dx%d%s' % (dt, kid, H_ + 2, W_ + 2, '-accumulate' if acc else ''), kid, dt, B_, 40, 24,
+                              H_, W_, dgrad_taps_extended(K3R, 2), transpose=1, fold=('fused', 2, 2), gen=gen, acc=acc))
+
+# ---- input transform (bf16, 9 taps, whole aligned pieces; configs 1 - 4): the producer's BatchNorm apply (+ ReLU) in the loader
+for kid, B_, Ci, H_, W_, reg in ((1, 2, 40, 33, 17, 'ilv9-3'), (1, 5, 64, 8, 8, 'ilv9-9'), (2, 1, 64, 16, 16, 'ilv9-6'), (3, 2, 40, 9, 11, 'ilv9-3'),
+                                 (4, 2, 64, 16, 16, 'ilv9-3'), (4, 16, 24, 4, 4, 'ilv9-9')):
+    for tf in ('relu', 'affine'):
+        CASES.append(case('bf16-cfg%d-in-%s-%d-%dx%d' % (kid, tf, Ci, H_, W_), kid, 'bf16', B_, Ci, 40, H_, W_, K3, in_tf=tf, regime=reg))
+CASES.append(case('bf16-cfg1-in-relu-replicate', 1, 'bf16', 2, 40, 40, 9, 11, K3R, pad_mode=1, in_tf='relu', bias=True, relu=True))
+
+# ---- conv_glds_kernel (ids 6 - 8, bf16): 1, 2, 3 chunks of input channels against 2 | 4 K-slices; a ragged channel tile
+for kid in (6, 7, 8):
+    n = 'bf16-glds%d-' % kid
+    for Cin in (32, 64, 96):
+        CASES.append(case(n + '%d-40-17x9' % Cin, kid, 'bf16', 2, Cin, 40, 17, 9, K3))
+    CASES.append(case(n + '64-72-33x17-replicate', kid, 'bf16', 2, 64, 72, 33, 17, K3R, pad_mode=1))
+    CASES.append(case(n + 'accumulate', kid, 'bf16', 2, 64, 40, 17, 9, K3, acc=True))
+    CASES.append(case(n + 'res', kid, 'bf16', 2, 96, 40, 17, 9, K3, bias=True, scale=True, shift=True, relu=True, res=True))
+    CASES.append(case(n + 'bias-scale-shift-relu', kid, 'bf16', 2, 32, 40, 17, 9, K3, bias=True, scale=True, shift=True, relu=True))
+    CASES.append(case(n + 'y-window', kid, 'bf16', 2, 64, 40, 17, 9, K3, yv=(8, 56), xv=(8, 80)))
+    CASES.append(case(n + 'fold-fused-14x22', kid, 'bf16', 2, 64, 40, 12, 20, dgrad_taps_extended(K3R, 2), transpose=1, fold=('fused', 2, 2),
+                      gen=None if kid == 6 else 1))
+
+# ---- conv_ws_kernel (id 9): cfg = 9 | cap << 8
+CASES += [
+    case('ws-64-64-16x16-b1', 9, 'bf16', 1, 64, 64, 16, 16, K3),
+    case('ws-32-64-16x32', 9, 'bf16', 2, 32, 64, 16, 32, K3R, pad_mode=1),
+    case('ws-64-32-32x16-b3-cap1', 9, 'bf16', 3, 64, 32, 32, 16, K3, cfg=9 | (1 << 8)),
+    case('ws-64-128-two-blocks', 9, 'bf16', 2, 64, 128, 16, 16, K3, bias=True, scale=True, shift=True, relu=True),
+    case('ws-res', 9, 'bf16', 2, 64, 64, 16, 16, K3, scale=True, shift=True, relu=True, res=True),
+    case('ws-accumulate-ragged-grid', 9, 'bf16', 2, 64, 64, 24, 20, dgrad_taps(K3), transpose=1, acc=True, cfg=9 | (1 << 8)),
+    case('ws-views', 9, 'bf16', 2, 32, 64, 16, 16, K3, xv=(8, 48), yv=(16, 96)),
+    case('ws-64-64-replicate-24x20', 9, 'bf16', 2, 64, 64, 24, 20, K3R, pad_mode=1, bias=True, relu=True),
+    case('ws-64-32-replicate-cap1', 9, 'bf16', 3, 64, 32, 32, 16, K3R, pad_mode=1, cfg=9 | (1 << 8)),
+    case('ws-64-128-replicate-res', 9, 'bf16', 2, 64, 128, 16, 16, K3R, pad_mode=1, scale=True, shift=True, relu=True, res=True),
+    case('ws-32-64-replicate-accumulate', 9, 'bf16', 2, 32, 64, 16, 16, K3R, pad_mode=1, acc=True),
+    case('ws-fold-fused-18x18', 9, 'bf16', 2, 64, 64, 16, 16, dgrad_taps_extended(K3R, 2), transpose=1, fold=('fused', 2, 2)),
+    case('ws-fold-fused-18x18-accumulate', 9, 'bf16', 2, 32, 64, 16, 16, dgrad_taps_extended(K3R, 2), transpose=1, fold=('fused', 2, 2),
+         acc=True),
+]
+# ---- conv_ls_kernel (id 10): cfg = 10 | cap << 8 | NI << 16 | bit 20 two-tile items | bit 21 single tiles only
+CASES += [
+    case('ls-64-32-16x16-cap1', 10, 'bf16', 2, 64, 32, 16, 16, K3, cfg=10 | (1 << 8)),
+    case('ls-128-64-16x32-ni2', 10, 'bf16', 2, 128, 64, 16, 32, K3R, pad_mode=1, cfg=10 | (2 << 16)),
+    case('ls-128-64-ni1', 10, 'bf16', 2, 128, 64, 16, 16, K3, cfg=10 | (1 << 16), bias=True, relu=True),
+    case('ls-two-tile-items', 10, 'bf16', 4, 128, 64, 16, 32, K3, cfg=10 | (1 << 8) | (2 << 16) | (1 << 20), bias=True, scale=True, shift=True, relu=True),
+    case('ls-single-tiles-only', 10, 'bf16', 4, 128, 64, 16, 32, K3, cfg=10 | (1 << 8) | (2 << 16) | (1 << 21), bias=True, scale=True, shift=True, relu=True),
+    case('ls-res', 10, 'bf16', 2, 96, 96, 16, 16, K3, scale=True, shift=True, relu=True, res=True),
+    case('ls-accumulate', 10, 'bf16', 2, 64, 96, 16, 16, dgrad_taps(K3), transpose=1, acc=True),
+    case('ls-64-32-replicate-cap1', 10, 'bf16', 2, 64, 32, 16, 16, K3R, pad_mode=1, cfg=10 | (1 << 8)),
+    case('ls-96-96-replicate-res', 10, 'bf16', 2, 96, 96, 16, 16, K3R, pad_mode=1, scale=True, shift=True, relu=True, res=True),
+    case('ls-two-tile-items-replicate', 10, 'bf16', 4, 128, 64, 16, 32, K3R, pad_mode=1, cfg=10 | (1 << 8) | (2 << 16) | (1 << 20), bias=True, relu=True),
+    case('ls-views', 10, 'bf16', 2, 64, 32, 16, 16, K3, xv=(8, 80), yv=(16, 64)),
+]
+# ---- conv_thin_kernel (id 12, fp32)
+for ci, co in ((16, 16), (16, 32), (32, 16), (32, 32)):
+    CASES.append(case('thin-%d-%d-zero' % (ci, co), 12, 'f32', 2, ci, co, 16, 16, K3, bias=True))
+    CASES.append(case('thin-%d-%d-replicate' % (ci, co), 12, 'f32', 3, ci, co, 16, 32, K3R, pad_mode=1, scale=True, shift=True, relu=True))
+CASES.append(case('thin-accumulate', 12, 'f32', 2, 32, 16, 16, 16, dgrad_taps(K3), transpose=1, acc=True))
+# ---- conv_stem16_kernel (id 13): 16 taps over the 16 channels of the space-to-depth image -> 64
+STEM = [(kh, kw, kh - 2, kw - 2) for kh in range(4) for kw in range(4)]
+CASES.append(case('stem16-eval', 13, 'bf16', 1, 16, 64, 16, 16, STEM, scale=True, shift=True, relu=True))
+CASES.append(case('stem16-plain-b3', 13, 'bf16', 3, 16, 64, 16, 32, STEM))
+
+
+def _vec(C, seed, kind):
+    g = torch.Generator().manual_seed(seed)
+    if kind == 'scale':                                                    # [0.5, 2], both signs
+        return ((0.5 + 1.5 * torch.rand(C, generator=g)) * torch.where(torch.rand(C, generator=g) < 0.25, -1.0, 1.0)).double()
+    return torch.randn(C, generator=g).double()
+
+
+def build(c):
+    """Operands (CPU) and the float64 reference of a case."""
+    B, Cin, Cout, H, W = c['B'], c['Cin'], c['Cout'], c['H'], c['W']
+    taps = c['taps']
+    x = mk(B, Cin, H, W, 10 * c['seed']).permute(0, 2, 3, 1).contiguous()
+    D0, D1 = (Cin, Cout) if c['transpose'] else (Cout, Cin)
+    w = master_weight(D0, D1, c['KH'], c['KW'], Cin, len(taps), 10 * c['seed'] + 1)
+    tap_k, offs = [(t[0], t[1]) for t in taps], [(t[2], t[3]) for t in taps]
+    wt = tap_weights(w, tap_k, c['transpose'])
+    o = dict(x=x, w=w, tap_k=tap_k, offs=offs, wt=wt)
+    o['bias'] = _vec(Cout, 3, 'bias').float().double() if c['bias'] else None
+    o['scale'] = _vec(Cout, 4, 'scale').float().double() if c['scale'] else None
+    o['shift'] = _vec(Cout, 5, 'shift').float().double() if c['shift'] else None
+    fold = c['fold']
+    gH, gW = (c['yH'], c['yW']) if fold and fold[0] == 'fused' else (c['OH'], c['OW'])
+    o['res'] = mk(B, Cout, gH, gW, 10 * c['seed'] + 2).permute(0, 2, 3, 1).double() if c['res'] else None
+    o['old'] = mk(B, Cout, gH, gW, 10 * c['seed'] + 3).permute(0, 2, 3, 1).double() if c['acc'] else None
+    old = o['old']
+    if fold and fold[0] == 'strip' and old is not None:
+        raise AssertionError('strip cases here do not accumulate')
+    if c['in_tf']:
+        # multiples of 1/8 and 1/4: x in_scale + in_shift is exact in fp32 (no double rounding in the kernel's transform), in_shift != 0
+        # so that a transformed pad value would show
+        g = torch.Generator().manual_seed(77)
+        o['in_tf'] = (torch.randint(4, 17, (Cin,), generator=g).double() / 8, torch.randint(1, 9, (Cin,), generator=g).double() / 4 - 1.125,
+                      c['in_tf'] == 'relu')
+    o['ref'] = conv_ref(x, wt, offs, c['in_step'], c['pad_mode'], c['OH'], c['OW'], c['dtype'], o['bias'], o['scale'], o['shift'], c['relu'],
+                        o['res'], old, (fold[1], fold[2]) if fold and fold[0] == 'fused' else None, o.get('in_tf'))
+    return o

@@ -27,6 +27,8 @@ import math
 
 import torch
 
+from conv_abi import ratio_strict as ratio, store_tol as _store          # noqa: F401  (ratio is the tests' entry point)
+
 F64 = torch.float64
 U32, UBF = 2.0 ** -23, 2.0 ** -8
 
@@ -90,10 +92,6 @@ def dense_wgrad(dy, a):
 
 
 # ---------------------------------------------------------------- bounds
-def _store(e, tol, dtype):
-    return tol + UBF * (e.abs() + tol) if dtype == 'bf16' else tol
-
-
 def forward_ref(c, dtype, eval_epilogue, relu):
     """-> dict(exact, tol).  eval_epilogue: relu?(v scale + shift); else relu?(v) (the raw output of the train form, or a transition)"""
     a, _ = transform(c['x'], c['in_scale'], c['in_shift'], dtype)
@@ -146,10 +144,3 @@ def wgrad_ref(c, dtype, accumulate):
         e = e + c['gw_old']
         tol = tol + U32 * e.abs()
     return dict(exact=e, tol=tol)
-
-
-def ratio(got, ref):
-    """max |got - exact| / tol over ALL elements (NaN / inf in `got` -> inf; an element with tol = 0 must be exact)"""
-    d = (got.double() - ref['exact']).abs()
-    r = torch.where(ref['tol'] > 0, d / ref['tol'].clamp_min(1e-300), torch.where(d == 0, torch.zeros_like(d), torch.full_like(d, float('inf'))))
-    return float(torch.nan_to_num(r, nan=float('inf'), posinf=float('inf')).max())

@@ -9,6 +9,7 @@ from collections import OrderedDict
 import torch
 import torch.nn.functional as F
 
+import helpers
 from oracle import blocks as B
 from oracle import specs as OS
 
@@ -116,12 +117,7 @@ def spec_unet_densenet(depth=121, num_classes=2, use_hypercolumn=True):
 
 
 def expand_aliases(sd):
-    out = OrderedDict(sd)
-    for a, c in ALIASES.items():
-        for k, v in sd.items():
-            if k.startswith(c):
-                out[a + k[len(c):]] = v
-    return out
+    return helpers.expand_aliases(sd, ALIASES)
 
 
 def closed_form_state(spec):

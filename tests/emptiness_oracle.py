@@ -4,6 +4,7 @@ from collections import OrderedDict
 
 import torch.nn.functional as F
 
+import helpers
 from oracle import blocks as B
 from oracle import specs as OS
 
@@ -36,9 +37,4 @@ def spec_emptiness_classifier(depth=18, num_classes=2, with_fc=False):
 
 
 def expand_aliases(sd):
-    out = OrderedDict(sd)
-    for a, c in ALIASES.items():
-        for k, v in sd.items():
-            if k.startswith(c):
-                out[a + k[len(c):]] = v
-    return out
+    return helpers.expand_aliases(sd, ALIASES)

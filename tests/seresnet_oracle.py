@@ -8,6 +8,7 @@ from collections import OrderedDict
 import torch
 import torch.nn.functional as F
 
+import helpers
 from oracle import blocks as B
 from oracle import specs as OS
 
@@ -114,12 +115,7 @@ def spec_unet_seresnet(depth=50, num_classes=2, use_hypercolumn=True, with_last_
 
 
 def expand_aliases(sd):
-    out = OrderedDict(sd)
-    for a, c in ALIASES.items():
-        for k, v in sd.items():
-            if k.startswith(c):
-                out[a + k[len(c):]] = v
-    return out
+    return helpers.expand_aliases(sd, ALIASES)
 
 
 FC2_KEY = 'se_module.fc2.weight'

@@ -42,6 +42,7 @@ pixel of a weight gradient by 2^23 / N^2 bounds: 80 at the base shape of the tab
 shows; the cases with 10^4 pixels exist for the reduction kernels, where a wrong part is a whole tile."""
 import ctypes
 
+import pytest
 import torch
 
 from conv_abi import U32, UBF, _store, bits, last_error, master_weight, mk, ratio           # noqa: F401  (re-exported for the tests)
@@ -324,3 +325,254 @@ class Guarded:
 def worst(got, ref):
     """ratio() for a dict(exact, tol) of any shape."""
     return ratio(got.reshape(ref['exact'].shape), ref)
+
+
+# ================================================================ the case tables and operand builders of test_gpu_small_abi.py /
+# test_small_reference_cpu.py (host only)
+DTYPES = ('f32', 'bf16')
+FAKE = 1 << 24                            # a 16-byte aligned made-up address for the host-only queries
+
+
+def _vec(C, seed, kind='bias'):
+    """bf16-representable per-channel vectors; scale in [0.5, 2] with both signs."""
+    g = torch.Generator().manual_seed(seed)
+    if kind == 'scale':
+        v = (0.5 + 1.5 * torch.rand(C, generator=g)) * torch.where(torch.rand(C, generator=g) < 0.25, -1.0, 1.0)
+    else:
+        v = torch.randn(C, generator=g)
+    return v.bfloat16().double()
+
+
+def _ids(cases):
+    return [pytest.param(c, id=c['name']) for c in cases]
+
+
+# ---------------------------------------------------------------- salt_conv_first
+def first_case(name, dtype, Cin, H, W, K, s, p, Cout, B=2, yv=None, **kw):
+    c = dict(name='%s-%s' % (dtype, name), dtype=dtype, B=B, Cin=Cin, H=H, W=W, K=K, s=s, p=p, Cout=Cout, yv=yv or (0, Cout), bias=False,
+             scale=False, relu=False, stats=False, vec=None)
+    c.update(kw)
+    return c
+
+
+FIRST_CASES = []
+for _dt in DTYPES:
+    _ve = VE[_dt]
+    FIRST_CASES += [
+        # the ResNet stem on 2 x 2 ragged tiles (17 x 19 outputs): whole 16-channel blocks, a ragged second block, a single ragged block
+        first_case('7x7s2-cout64', _dt, 3, 34, 38, 7, 2, 3, 64, vec=True),
+        first_case('7x7s2-cout24', _dt, 3, 34, 38, 7, 2, 3, 24, vec=True),           # (block 0 is whole: vector stores; block 1 scalar)
+        first_case('7x7s2-cout10', _dt, 3, 34, 38, 7, 2, 3, 10, vec=False),
+        # the remaining K / stride / pad / Cin forms
+        first_case('3x3s1p1-cin1', _dt, 1, 19, 21, 3, 1, 1, 16, vec=True),
+        first_case('3x3s1p1-cin4', _dt, 4, 19, 21, 3, 1, 1, 10, vec=False),
+        first_case('1x1s1', _dt, 2, 17, 19, 1, 1, 0, 16, vec=True),
+        first_case('1x1s2', _dt, 2, 33, 37, 1, 2, 0, 16, vec=True),
+        first_case('5x5s2p2', _dt, 3, 33, 37, 5, 2, 2, 24, vec=True),
+        first_case('3x3s1p0', _dt, 2, 19, 21, 3, 1, 0, 16, vec=True),
+        # y as a channel slice of a wider buffer: the three terms of the vector-store predicate, one at a time
+        first_case('y-slice-aligned', _dt, 3, 34, 38, 7, 2, 3, 32, yv=(16, 56), vec=True),
+        first_case('y-slice-cs-odd', _dt, 3, 34, 38, 7, 2, 3, 32, yv=(0, 37), vec=False),
+        first_case('y-slice-misaligned', _dt, 3, 34, 38, 7, 2, 3, 32, yv=(2, 40), vec=False),
+        # each epilogue combination on its own (none: the cases above), on the ragged second block
+        first_case('bias', _dt, 3, 34, 38, 7, 2, 3, 24, bias=True, vec=True),
+        first_case('bias-cout10', _dt, 3, 34, 38, 7, 2, 3, 10, bias=True, vec=False),
+        first_case('scale-shift-relu', _dt, 3, 34, 38, 7, 2, 3, 24, scale=True, relu=True, vec=True),
+        first_case('bias-scale-shift', _dt, 3, 34, 38, 7, 2, 3, 24, bias=True, scale=True, vec=True),
+        # tile statistics on ragged tiles: counts 256, 48, 16 and 3 per image
+        first_case('stats', _dt, 3, 34, 38, 7, 2, 3, 24, stats=True, vec=True),
+        first_case('stats-epilogue', _dt, 3, 34, 38, 7, 2, 3, 24, bias=True, scale=True, relu=True, stats=True, vec=True),
+        first_case('stats-3x3', _dt, 1, 19, 21, 3, 1, 1, 10, bias=True, stats=True, vec=False, B=3),
+    ]
+
+
+def first_vec(c):
+    """conv_first_kernel's vector-store predicate for block 0 of the case, from the view alone."""
+    es = 4 if c['dtype'] == 'f32' else 2
+    c0, cs = c['yv']
+    return c['Cout'] >= 16 and cs % VE[c['dtype']] == 0 and (c0 * es) % 16 == 0
+
+
+def first_build(c):
+    x = mk(c['B'], c['Cin'], c['H'], c['W'], 11)
+    w = master_weight(c['Cout'], c['Cin'], c['K'], c['K'], c['Cin'], c['K'] * c['K'], 12)
+    o = dict(x=x, w=w, bias=_vec(c['Cout'], 3) if c['bias'] else None, scale=_vec(c['Cout'], 4, 'scale') if c['scale'] else None,
+             shift=_vec(c['Cout'], 5) if c['scale'] else None)
+    o['ref'] = conv_first_ref(x, w, c['s'], c['p'], c['dtype'], o['bias'], o['scale'], o['shift'], c['relu'])
+    return o
+
+
+# ---------------------------------------------------------------- salt_conv_first_wgrad
+MFMA = 0
+
+
+def wg_case(name, Cin, K, Cout, kid, B=1, H=None, W=None, s=1, p=None, OH=17, OW=19, dyv=None, rc=0, per=None, wrong_nparts=False):
+    """Default geometry: one image whose output is 17 x 19 (2 x 2 ragged tiles).  kid: salt_conv_first_wgrad_kernel_id, or -1 for a
+    refusal with return code rc."""
+    p = K // 2 if p is None else p
+    if H is None:
+        H, W = (OH - 1) * s + K - 2 * p, (OW - 1) * s + K - 2 * p
+    assert first_geom(H, W, K, s, p) == (OH, OW), name
+    return dict(name=name, B=B, Cin=Cin, H=H, W=W, K=K, s=s, p=p, Cout=Cout, kid=kid, OH=OH, OW=OW, dyv=dyv or (0, Cout), rc=rc, per=per,
+                wrong_nparts=wrong_nparts)
+
+
+WGRAD_CASES = [
+    wg_case('mfma-cin1-k3-cout16', 1, 3, 16, MFMA),
+    wg_case('mfma-cin1-k3-cout32', 1, 3, 32, MFMA),                          # two cb passes
+    wg_case('mfma-cin1-k4-cout16', 1, 4, 16, MFMA, p=1),                     # K K Cin exactly 16
+    wg_case('mfma-cin4-k2-cout48', 4, 2, 48, MFMA, p=0),
+    wg_case('mfma-cin3-k1-cout16', 3, 1, 16, MFMA),                          # 3 taps on, 13 off
+    wg_case('per1-cout10-cin1-k3', 1, 3, 10, 1, per=1),
+    wg_case('per4-cout24-cin3-k3', 3, 3, 24, 4, per=3),
+    wg_case('per12-cout64-cin1-k5', 1, 5, 64, 12, per=7),
+    wg_case('per40-cout64-cin3-k7', 3, 7, 64, 40, per=37),
+    wg_case('per40-cout50-cin4-k7', 4, 7, 50, 40, per=40),                   # per exactly MAXKK
+    # one group of threads (Cout > 128).  256 pixels x Cout floats of dy live in LDS: 160 KiB end at Cout 159, so Cout 200 and 256 (one
+    # group with 56 / no idle threads) are refused with SALT_E_LDS, and 144 / 128 are the widest forms that run
+    wg_case('one-group-cout200', 4, 3, 200, -1, rc=-3),
+    wg_case('one-group-cout256', 4, 3, 256, -1, rc=-3),
+    wg_case('one-group-cout144-112-idle', 4, 3, 144, 40, per=36),
+    wg_case('two-groups-cout128-none-idle', 4, 3, 128, 40, per=18),
+    wg_case('cout257', 4, 3, 257, -1, rc=-2),
+    wg_case('per49-cout64-cin4-k7', 4, 7, 64, -1, rc=-2),
+    # the reduction of the partials: narrow below 64 parts or above 4096 outputs, wide otherwise
+    wg_case('nparts63-narrow', 1, 3, 10, 1, B=7, OH=33, OW=35, per=1),
+    wg_case('nparts64-wide', 1, 3, 10, 1 | WIDE, B=4, OH=49, OW=51, per=1),
+    wg_case('nparts64-wide-mfma', 1, 3, 16, MFMA | WIDE, B=4, OH=49, OW=51),
+    wg_case('nparts320-wide', 1, 3, 10, 1 | WIDE, B=20, OH=49, OW=51, per=1),  # thread t adds parts t and t + 256
+    wg_case('nparts64-n9408-narrow', 3, 7, 64, 40, B=4, OH=49, OW=51, per=37),
+    wg_case('stride2-mfma', 1, 3, 16, MFMA, s=2, H=34, W=38),
+    wg_case('stride2-per40', 3, 7, 64, 40, s=2, H=34, W=38, per=37),
+    wg_case('dy-slice', 3, 3, 24, 4, dyv=(8, 40), per=3),
+    wg_case('dy-slice-mfma', 1, 3, 32, MFMA, dyv=(3, 37)),
+    wg_case('wrong-nparts', 1, 3, 16, -1, rc=-1, wrong_nparts=True),
+]
+
+
+def wg_nparts(c):
+    return c['B'] * cdiv(c['OH'], 16) * cdiv(c['OW'], 16)
+
+
+def wg_plan(c, dtype, x=FAKE, dy=FAKE, partials=FAKE, grad=FAKE, acc=0):
+    es = 4 if dtype == 'f32' else 2
+    dyv = view(dy + (c['dyv'][0] * es if dy == FAKE else 0), c['B'], c['OH'], c['OW'], c['Cout'], c['dyv'][1])
+    return first_wgrad_args(dtype, x, (c['B'], c['Cin'], c['H'], c['W']), c['K'], c['s'], c['p'], dyv, partials,
+                            wg_nparts(c) + int(c['wrong_nparts']), grad, acc)
+
+
+def wg_build(c, acc):
+    x = mk(c['B'], c['Cin'], c['H'], c['W'], 21)
+    dy = mk(c['B'], c['Cout'], c['OH'], c['OW'], 22).permute(0, 2, 3, 1).contiguous()
+    old = mk(c['Cout'], c['Cin'], c['K'], c['K'], 23).double() if acc else None
+    o = dict(x=x, dy=dy, old=old)
+    if c['kid'] >= 0:
+        o['ref'] = conv_first_wgrad_ref(x, dy, c['K'], c['s'], c['p'], old)
+    return o
+
+
+# ---------------------------------------------------------------- salt_head1x1
+def head_case(name, dtype, C, Cout, kid, B=2, H=7, W=9, xv=None):
+    return dict(name='%s-%s' % (dtype, name), dtype=dtype, B=B, H=H, W=W, C=C, Cout=Cout, kid=kid, xv=xv or (0, C))
+
+
+HEAD_CASES = []
+for _dt in DTYPES:
+    _ve = VE[_dt]
+    HEAD_CASES += [
+        head_case('co2-8x8-shift', _dt, 8 * _ve, 2, HEAD_VEC_CO2, H=8, W=8),              # H W a power of two: no division per pixel
+        head_case('co2-7x9-divide', _dt, 8 * _ve, 2, HEAD_VEC_CO2),
+        head_case('co2-units-below-256', _dt, 8 * _ve, 2, HEAD_VEC_CO2, B=1, H=3, W=5),   # the second pixel in flight is past the end
+        head_case('co2-cpv1', _dt, _ve, 2, HEAD_VEC_CO2),
+        head_case('co2-cpv64', _dt, 64 * _ve, 2, HEAD_VEC_CO2),
+        head_case('co2-x-slice', _dt, 8 * _ve, 2, HEAD_VEC_CO2, xv=(2 * _ve, 12 * _ve)),
+        head_case('vec-cout1', _dt, 8 * _ve, 1, HEAD_VEC),
+        head_case('vec-cout3', _dt, 8 * _ve, 3, HEAD_VEC),
+        head_case('vec-cout4', _dt, 8 * _ve, 4, HEAD_VEC, H=8, W=8),
+        head_case('vec-cpv1-cout3', _dt, _ve, 3, HEAD_VEC),
+        head_case('vec-cpv64-cout4', _dt, 64 * _ve, 4, HEAD_VEC),
+        head_case('scalar-c10-cout1', _dt, 10, 1, HEAD_SCALAR),
+        head_case('scalar-c10-cout2', _dt, 10, 2, HEAD_SCALAR),
+        head_case('scalar-c10-cout3', _dt, 10, 3, HEAD_SCALAR),
+        head_case('scalar-c10-cout4', _dt, 10, 4, HEAD_SCALAR),
+        head_case('scalar-cs-odd', _dt, 8 * _ve, 2, HEAD_SCALAR, xv=(0, 8 * _ve + 3)),
+        head_case('scalar-misaligned', _dt, 8 * _ve, 2, HEAD_SCALAR, xv=(2, 10 * _ve)),
+    ]
+HEAD_CASES += [
+    head_case('scalar-c24-cpv3', 'bf16', 24, 2, HEAD_SCALAR),                              # whole pieces, but not a power of two of them
+    head_case('scalar-c12-cpv3', 'f32', 12, 3, HEAD_SCALAR),
+    head_case('scalar-c512-cpv128', 'f32', 512, 2, HEAD_SCALAR),                           # more than 64 pieces
+    head_case('scalar-c1024-cpv128', 'bf16', 1024, 4, HEAD_SCALAR),
+]
+# above the 4096-block grid cap: 16640 pixels x 64 pieces = 4160 blocks' worth of units (17 MB of input)
+HEAD_GRID_CAP = head_case('co2-grid-cap', 'bf16', 512, 2, HEAD_VEC_CO2, B=1, H=128, W=130)
+
+
+def head_plan(c, out, x=FAKE, w=FAKE, bias=None, y=FAKE, gap=3):
+    es = 4 if c['dtype'] == 'f32' else 2
+    xv = view(x + (c['xv'][0] * es if x == FAKE else 0), c['B'], c['H'], c['W'], c['C'], c['xv'][1])
+    if out == 'nchw':
+        return head_args(c['dtype'], xv, w, bias, c['Cout'], y_nchw=y)
+    return head_args(c['dtype'], xv, w, bias, c['Cout'], y=view(y, c['B'], c['H'], c['W'], c['Cout'], c['Cout'] + 2 * gap))
+
+
+def head_build(c, seed=31):
+    x = mk(c['B'], c['C'], c['H'], c['W'], seed).permute(0, 2, 3, 1).contiguous()
+    w = master_weight(c['Cout'], c['C'], 1, 1, c['C'], 1, seed + 1).reshape(c['Cout'], c['C'])
+    return dict(x=x, w=w, bias=_vec(c['Cout'], seed + 2))
+
+
+# ---------------------------------------------------------------- salt_head1x1_bwd
+def hb_case(name, dtype, C, Cout, kid, B=1, H=4, W=5, xv=None, dxv=None):
+    return dict(name='%s-%s' % (dtype, name), dtype=dtype, B=B, H=H, W=W, C=C, Cout=Cout, kid=kid, xv=xv or (0, C), dxv=dxv or (0, C))
+
+
+HEAD_BWD_CASES = []
+for _dt in DTYPES:
+    _ve = VE[_dt]
+    HEAD_BWD_CASES += [
+        hb_case('vec-cpv1', _dt, _ve, 2, HEAD_VEC, B=2, H=7, W=9),
+        hb_case('vec-cpv3-r85', _dt, 3 * _ve, 3, HEAD_VEC, B=2, H=20, W=17),                 # one idle thread; 680 pixels in 11 parts of 62
+        hb_case('vec-cpv256-r1', _dt, 256 * _ve, 1, HEAD_VEC, H=3, W=5),
+        # R <= 21 rows of threads: a part of at most 64 pixels reaches the fourth pixel in flight (126 pixels: 2 parts of 63)
+        hb_case('vec-cpv16-r16', _dt, 16 * _ve, 4, HEAD_VEC, B=2, H=7, W=9),
+        hb_case('vec-cpv64-r4', _dt, 64 * _ve, 3, HEAD_VEC, B=2, H=7, W=9),
+        hb_case('vec-cpv8-ragged-part', _dt, 8 * _ve, 4, HEAD_VEC),                          # 20 pixels: no multiple of 4 R = 128
+        hb_case('vec-slices', _dt, 8 * _ve, 2, HEAD_VEC, xv=(_ve, 10 * _ve), dxv=(2 * _ve, 11 * _ve)),
+        hb_case('vec-129-pixels', _dt, 8 * _ve, 2, HEAD_VEC, H=3, W=43),                     # 64 k + 1 pixels: 3 parts of 43
+        hb_case('vec-260x260', _dt, _ve, 2, HEAD_VEC, H=260, W=260),                         # the cap: 1009 parts of 67 pixels
+        hb_case('scalar-c10', _dt, 10, 3, HEAD_SCALAR, B=2, H=7, W=9),
+        hb_case('scalar-dx-cs-odd', _dt, 8 * _ve, 2, HEAD_SCALAR, dxv=(0, 8 * _ve + 3)),
+        hb_case('scalar-x-misaligned', _dt, 8 * _ve, 4, HEAD_SCALAR, xv=(2, 10 * _ve)),
+        hb_case('scalar-260x260', _dt, 10, 1, HEAD_SCALAR, H=260, W=260),
+    ]
+HEAD_BWD_CASES += [
+    hb_case('scalar-c300-two-passes', 'bf16', 300, 2, HEAD_SCALAR, B=2, H=7, W=9),           # cn 256, then 44 (R = 5)
+    hb_case('scalar-c1028-cpv257', 'f32', 1028, 3, HEAD_SCALAR),                             # whole pieces, one too many
+    hb_case('scalar-c302-two-passes', 'f32', 302, 4, HEAD_SCALAR),                           # cn 256, then 46
+]
+
+
+def hb_plan(c, acc, gb, x=FAKE, dx=FAKE + (1 << 22), nparts=None):
+    es = 4 if c['dtype'] == 'f32' else 2
+    f = (lambda p, v: p + v[0] * es) if x == FAKE else (lambda p, v: p)
+    xv = view(f(x, c['xv']), c['B'], c['H'], c['W'], c['C'], c['xv'][1])
+    dxv = view(f(dx, c['dxv']), c['B'], c['H'], c['W'], c['C'], c['dxv'][1])
+    S = head_bwd_args(c['dtype'], xv, FAKE, c['Cout'], FAKE, dxv, acc, FAKE, 0, FAKE, FAKE if gb else None)
+    S.nparts = query('salt_head1x1_bwd_parts', S) if nparts is None else nparts
+    return S
+
+
+def hb_build(c, acc):
+    x = mk(c['B'], c['C'], c['H'], c['W'], 41).permute(0, 2, 3, 1).contiguous()
+    w = master_weight(c['Cout'], c['C'], 1, 1, c['Cout'], 1, 42).reshape(c['Cout'], c['C'])
+    dy = mk(c['B'], c['Cout'], c['H'], c['W'], 43)
+    old = mk(c['B'], c['C'], c['H'], c['W'], 44).permute(0, 2, 3, 1).contiguous() if acc else None
+    ref = head_bwd_ref(x.double(), w.double(), dy.double(), c['dtype'], old.double() if acc else None)
+    return dict(x=x, w=w, dy=dy, old=old, ref=ref)
+
+
+def _arbitrary(shape, seed):
+    """fp32 values with full mantissas (no two alike in practice), so that bf16 outputs exercise the rounding."""
+    g = torch.Generator().manual_seed(seed)
+    return torch.randn(*shape, generator=g) * (1.0 + torch.rand(*shape, generator=g))

@@ -9,7 +9,6 @@ import torch.nn.functional as F
 import conv_abi as CA
 from conv_abi import k3_taps
 from op_reference import pad_fold, round_to
-import test_gpu_conv_abi as T
 
 K3, K3R = k3_taps(0), k3_taps(1)
 
@@ -42,7 +41,7 @@ def _close(a, b):
 @pytest.mark.parametrize('k', [3, 1])
 def test_zero_pad_forward_is_conv2d(stride, k):
     x, w = _ops(2, 5, 7, 9, 6, k, k)
-    taps = K3 if k == 3 else T.K1
+    taps = K3 if k == 3 else CA.K1
     OH, OW = (9 - 1) // stride + 1, (6 - 1) // stride + 1
     want = F.conv2d(_nchw(x).double(), w.double(), stride=stride, padding=k // 2)
     _close(_sum(x, w, taps, 0, stride, 0, OH, OW), _nhwc(want))
@@ -50,7 +49,7 @@ def test_zero_pad_forward_is_conv2d(stride, k):
 
 def test_row_kernel_is_conv2d():
     x, w = _ops(2, 5, 7, 9, 6, 1, 3)
-    _close(_sum(x, w, T.K13, 0, 1, 0, 9, 6), _nhwc(F.conv2d(_nchw(x).double(), w.double(), padding=(0, 1))))
+    _close(_sum(x, w, CA.K13, 0, 1, 0, 9, 6), _nhwc(F.conv2d(_nchw(x).double(), w.double(), padding=(0, 1))))
 
 
 def test_replicate_pad_forward_is_pad_plus_valid_conv2d():
@@ -115,7 +114,7 @@ def test_extended_grid_dgrad_then_pad_fold_is_the_replicate_pad_input_gradient()
 def test_epilogue_order_and_storage_roundings():
     x, w = _ops(2, 5, 7, 9, 6, 3, 3)
     wt, offs = CA.tap_weights(w, [(t[0], t[1]) for t in K3], 0), [(t[2], t[3]) for t in K3]
-    b, s, h = T._vec(7, 3, 'bias'), T._vec(7, 4, 'scale'), T._vec(7, 5, 'shift')
+    b, s, h = CA._vec(7, 3, 'bias'), CA._vec(7, 4, 'scale'), CA._vec(7, 5, 'shift')
     res, old = _nhwc(CA.mk(2, 7, 9, 6, 8)).double(), _nhwc(CA.mk(2, 7, 9, 6, 9)).double()
     v = CA.conv_sum(x, wt, offs, 1, 0, 9, 6)[0]
     e = (v + b) * s + h
@@ -166,9 +165,9 @@ def _standin(c, o):
     return st(v)
 
 
-@pytest.mark.parametrize('c', T.CASES)
+@pytest.mark.parametrize('c', CA.CASES)
 def test_bound_lets_fp32_pass(c):
-    o = T.build(c)
+    o = CA.build(c)
     r = CA.ratio(_standin(c, o), o['ref'])
     assert r <= 1.0, 'fp32 stand-in at %.3f of the bound' % r
 
@@ -215,7 +214,7 @@ def test_bound_rejects_a_clamp_one_row_off(shape, dtype):
 def test_bound_rejects_bias_applied_after_scale(shape, dtype):
     x, wt, offs = _mutation_ops(shape, 0)
     B, Cin, H, W, Cout = shape
-    b, s, h = T._vec(Cout, 3, 'bias'), T._vec(Cout, 4, 'scale'), T._vec(Cout, 5, 'shift')
+    b, s, h = CA._vec(Cout, 3, 'bias'), CA._vec(Cout, 4, 'scale'), CA._vec(Cout, 5, 'shift')
     ref = CA.conv_ref(x, wt, offs, 1, 0, H, W, dtype, b, s, h, True)
     got = (ref['v'] * s + b + h).clamp_min(0)
     assert CA.ratio(round_to(got, dtype), ref) > 1.0

@@ -7,7 +7,7 @@ import torch
 import torch.nn.functional as F
 
 from helpers import golden, T, assert_close, rel_err, state_from_fixture
-import closed_form as CF
+from gpu_harness import BLOCKS, _fixture_state, _mods
 
 pytestmark = pytest.mark.gpu
 
@@ -15,22 +15,10 @@ TOL32 = 5e-5
 TOLBF = 4e-2
 
 
-def _mods():
-    from salt_amd import architectures as A
-    return A
-
-
-def _fixture_state(fx, module):
-    sd = {}
-    for k, v in module.state_dict().items():
-        sd[k] = CF.tensor_for(k, v.shape).to(v.dtype)
-    return sd
-
-
 def _emulated_bf16_grads(name, fx):
     """gradients of the ORACLE block with bf16 storage emulated (inputs, activations, their gradients, packed weights) on a fixture's
     inputs and closed-form state: {'gx': .., 'ge0': .., 'g:<param>': ..} - the yardstick of the bf16 backward bound below"""
-    from test_oracle_golden import BLOCKS as OBLOCKS, _run as orun
+    from helpers import ORACLE_BLOCKS as OBLOCKS, oracle_run as orun
     from oracle import blocks as OB
     sd = state_from_fixture(fx)
     extras = [T(fx['e0'])] if 'e0' in fx else []
@@ -44,20 +32,6 @@ def _emulated_bf16_grads(name, fx):
     for k, v in leaves.items():
         out['g:' + k] = v.grad if v.grad is not None else torch.zeros_like(v)
     return out
-
-
-BLOCKS = {
-    'F1_conv2dbnrelu_k33': (lambda A: A.Conv2dBnRelu(3, 8), lambda m: (lambda g, x: m.emit(g, x))),
-    'F1_conv2dbnrelu_k31': (lambda A: A.Conv2dBnRelu(3, 8, kernel_size=(3, 1)), lambda m: (lambda g, x: m.emit(g, x))),
-    'F1_conv2dbnrelu_k13': (lambda A: A.Conv2dBnRelu(3, 8, kernel_size=(1, 3)), lambda m: (lambda g, x: m.emit(g, x))),
-    'F2_convbnrelu': (lambda A: A.ConvBnRelu(3, 8), lambda m: (lambda g, x: m.emit(g, x))),
-    'F3_decoderv1': (lambda A: A.DecoderBlockV1(6, 8, 4), lambda m: (lambda g, x: m.emit(g, x))),
-    'F3_decoderv2_deconv': (lambda A: A.DecoderBlockV2(6, 8, 4, is_deconv=True), lambda m: (lambda g, x: m.emit(g, x))),
-    'F3_decoderv2_upsample': (lambda A: A.DecoderBlockV2(6, 8, 4, is_deconv=False), lambda m: (lambda g, x: m.emit(g, x))),
-    'F3_deconvconv2dbnrelu': (lambda A: A.DeconvConv2dBnRelu(6, 4), lambda m: (lambda g, x: m.emit(g, x))),
-    'F4_decoderblock_skip': (lambda A: A.DecoderBlock(13, 16, 32), lambda m: (lambda g, x, e: m.emit(g, x, e))),
-    'F4_decoderblock_noskip': (lambda A: A.DecoderBlock(8, 16, 32), lambda m: (lambda g, x: m.emit(g, x))),
-}
 
 
 @pytest.mark.parametrize('name', sorted(BLOCKS))

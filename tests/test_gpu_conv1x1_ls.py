@@ -232,7 +232,7 @@ def test_conv1x1_ls_train_statistics_vs_torch(case):
         bn.weight.copy_(1 + 0.1 * torch.randn(Cout, generator=g)); bn.bias.copy_(0.1 * torch.randn(Cout, generator=g))
     x = torch.randn(B, Cin, H, W, generator=g).bfloat16().float()
     mod.train()
-    from test_gpu_conv_ws import _force_cfg
+    from gpu_harness import _force_cfg
 
     def emit(gr, a):
         _force_cfg(gr, 11)                                        # (small tensors: the kernel is not picked by itself below half a tile per CU)

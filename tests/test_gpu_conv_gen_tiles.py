@@ -12,7 +12,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from helpers import assert_close
-from test_gpu_conv_ws import _force_cfg, _rand
+from gpu_harness import _force_cfg, _rand
 
 pytestmark = pytest.mark.gpu
 TOL32, TOLBF = 2e-4, 4e-2

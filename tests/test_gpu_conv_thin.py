@@ -9,7 +9,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from helpers import assert_close
-from test_gpu_conv_ws import _force_cfg, _kernel_ids, _rand
+from gpu_harness import _force_cfg, _kernel_ids, _rand
 
 pytestmark = pytest.mark.gpu
 TOL = 2e-4

@@ -4,38 +4,16 @@ BasicBlock convs of ResNet34 layer1 (architectures/encoders.py:6-45), Conv2dBnRe
 the same launch.  cfg = 9 | cap << 8 asks for the kernel wherever it applies and caps the workgroups per XCD, so that small tensors
 walk the whole pipeline: several tiles per workgroup, both wave groups, the halo DMA issued from the epilogue, the aliased
 transposition slices of the 64 -> 64 variant."""
-import ctypes
-
 import pytest
 import torch
 import torch.nn.functional as F
 from torch import nn
 
 from helpers import assert_close
+from gpu_harness import _force_cfg, _kernel_ids, _rand
 
 pytestmark = pytest.mark.gpu
 TOLBF = 4e-2
-
-
-def _rand(shape, seed, scale=1.0):
-    g = torch.Generator().manual_seed(seed)
-    return torch.randn(*shape, generator=g) * scale
-
-
-def _force_cfg(g, cfg):
-    orig = g._conv_launch
-
-    def launch(*args, **kw):
-        kw.setdefault('cfg', cfg)
-        return orig(*args, **kw)
-    g._conv_launch = launch
-    orig_parts = g._conv_parts
-    g._conv_parts = lambda *a_, **k_: orig_parts(*a_, cfg=cfg, **k_)
-
-
-def _kernel_ids(prog):
-    from salt_amd._abi import lib
-    return [lib.salt_conv_kernel_id(ctypes.byref(s)) for name, _, s in prog.ops if name == 'conv']
 
 
 def _ls(cap, ni):

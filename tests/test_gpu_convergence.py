@@ -44,7 +44,7 @@ def _oracle_run(X, T, sd0, spec, threads, val=None):
 def test_r34_hypercolumn_20_steps_hip_f32_and_bf16_track_the_oracle():
     import bench
     from oracle import specs as OS
-    from test_gpu_fused_step import _segmentation_model
+    from net_checks import segmentation_model
     img, msk = bench.synth_tiles(B * K, seed=4321)
     X, T = bench.preprocess(img, msk, True, 3)
     vi, vm = bench.synth_tiles(VAL, seed=999)
@@ -72,7 +72,7 @@ def test_r34_hypercolumn_20_steps_hip_f32_and_bf16_track_the_oracle():
 
     curves, ious = {}, {}
     for dtype in ('f32', 'bf16'):
-        m = _segmentation_model('UNetResNet', 'lovasz', dtype=dtype, lr=1e-4)
+        m = segmentation_model('UNetResNet', 'lovasz', dtype=dtype, lr=1e-4)
         m.model.load_state_dict({k: sd0[k] for k in m.model.state_dict() if k in sd0}, strict=False)
         m._to_device()
         m.model.train()

@@ -11,24 +11,25 @@ eval epilogue, plus 2^-8 (|value| + tol) per bf16 storage rounding; the BatchNor
 the two sums' own bounds (derivation in that file).  Statistics are held to the float64 moments of the stored output
 (conv_abi.moments)."""
 import ctypes
+import functools
 
 import pytest
 import torch
 
-import numpy as np
-
 from helpers import golden, T, assert_close
+import abi_ops
 import closed_form as CF
 import dense_op_reference as DR
 import densenet_oracle as DO
-from test_gpu_models import _fill_closed_form
-from test_gpu_seresnet import Act, Vec, raw, call, _abi, _margin, DEV, F64, SENTINEL, TOL32, TOLBF
-from test_gpu_seresnext import merge_partials, check_moments
+import net_checks as NC
+from abi_ops import Act, Vec, raw, call, _abi, merge_partials, check_moments, DEV, F64, SENTINEL
 
 pytestmark = pytest.mark.gpu
+TOL32, TOLBF = 5e-5, 4e-2                   # tests/test_gpu_blocks.py: the F2 / F4 block bounds
 CODE = {'f32': 0, 'bf16': 1}
 _CASES, _REFS = {}, {}
 RATIOS = {}          # {(shape, dtype): {output: worst error / bound}}: the table of DESIGN 19
+held = functools.partial(abi_ops.held, ratio=DR.ratio, ratios=RATIOS)
 
 
 def case_of(shape):
@@ -50,14 +51,6 @@ def ref_of(shape, dtype, what, flag):
         else:
             _REFS[key] = DR.wgrad_ref(c, dtype, flag)
     return _REFS[key]
-
-
-def held(got, ref, what, case, key):
-    r = DR.ratio(got, ref)
-    per = RATIOS.setdefault(case, {})
-    per[key] = max(per.get(key, 0.0), r)
-    print('%s: worst error / bound %.3f' % (what, r))
-    assert r <= 1.0, '%s: error at %.3f of the bound' % (what, r)
 
 
 def dev(c, name):
@@ -415,7 +408,7 @@ N_DENSE = sum(DO.CFG[121]) + 3          # one dense_conv per layer and per trans
 
 def _net(dtype='f32'):
     from salt_amd import architectures as A
-    net = _fill_closed_form(A.UNetDenseNet(121, 2, dropout_2d=0.0, pretrained=False, use_hypercolumn=True))
+    net = NC.fill_closed_form(A.UNetDenseNet(121, 2, dropout_2d=0.0, pretrained=False, use_hypercolumn=True))
     return net.set_compute_dtype(dtype).to(DEV)
 
 
@@ -436,52 +429,26 @@ def test_eval_logits_and_masks_match_reference():
     net = _net().eval()
     with torch.no_grad():
         logits = net(x).cpu()
-    e = assert_close(logits, fx['eval_logits'], 1e-3, 'eval logits')
-    safe = _margin(fx)
-    mine, ref = (logits[:, 1] > 0).numpy(), fx['eval_logits'][:, 1] > 0
-    print('densenet eval rel err %.3e' % e, 'pixels left out', int((~safe).sum()), 'mask differences', int((mine != ref).sum()))
-    assert np.array_equal(mine[safe], ref[safe]) and ref.any() and not ref.all()
+    ref = NC.check_eval_masks(logits, fx, 'densenet eval', logits_tol=1e-3)
+    assert ref.any() and not ref.all()
     cn = net.engine().net(tuple(x.shape), False)
     ops = [o[0] for o in cn.fwd.ops]
     assert ops.count('dense_conv') == N_DENSE and 'dense_moments' not in ops and 'dense_bn_prep' not in ops and 'bn_finalize' not in ops
     _no_prefix_copy(net, cn)
-    # hipGraph replay of the eval program equals the eager run
-    st = torch.cuda.Stream()
-    torch.cuda.synchronize()
-    cn.fwd.capture(st)
-    with torch.cuda.stream(st):
-        cn.logits.zero_()
-        cn.x.copy_(x)
-        cn.fwd.replay(st)
-    st.synchronize()
-    assert torch.equal(cn.logits.cpu(), logits)
-    cn.fwd.release_graph()
-    # bf16 storage: within 4 x what bf16 storage costs the test-side oracle, and the same masks wherever the fp32 logit clears that
-    net16 = _net('bf16').eval()
-    with torch.no_grad():
-        l16 = net16(x).float().cpu()
-    assert bool(torch.isfinite(l16).all())
-    guard = 4 * float(fx['ref_bf16_storage_vs_f32_maxabs'])
-    err16 = float((l16 - logits).abs().max())
-    safe16 = (logits[:, 1].abs() > guard).numpy()
-    print('densenet eval bf16 max |bf16 - f32| %.3e' % err16, 'guard %.3e' % guard, 'pixels under the guard', int((~safe16).sum()))
-    assert err16 <= guard
-    assert np.array_equal((l16[:, 1] > 0).numpy()[safe16], (logits[:, 1] > 0).numpy()[safe16])
+    NC.check_eval_graph_replay(cn, x, logits)
+    NC.check_bf16_eval_guard(_net('bf16').eval(), x, logits, fx, 'densenet eval bf16', guard_factor=4)
 
 
 def test_one_training_step_matches_reference():
-    """zero_grad -> forward -> lovasz -> backward -> Adam(lr 1e-4, L2 1e-4) as models.py:105-136, with the bounds
-    tests/test_gpu_seresnext.py uses for F18: gradient norms (and sums) of tensors with 16 elements and more within 1e-2 relative,
-    tensors under 16 elements within 1e-6 of the largest gradient norm."""
-    from salt_amd.optim import FusedAdam, weight_regularization
-    from salt_amd import losses
+    """zero_grad -> forward -> lovasz -> backward -> Adam(lr 1e-4, L2 1e-4) as models.py:105-136, by the procedures of
+    tests/net_checks.py with the bounds tests/test_gpu_seresnext.py uses for F18: gradient norms (and sums) of tensors with 16 elements
+    and more within 1e-2 relative, tensors under 16 elements within 1e-6 of the largest gradient norm."""
     fx = golden(NET_FX)
     assert float(fx['ref_f32_vs_f64_gradnorm_rel']) <= 2.5e-3 and float(fx['ref_f32_vs_f64_small_abs']) <= 2.5e-7
     net = _net()
     net.train()
-    opt = FusedAdam(weight_regularization(net, True, 1e-4), lr=1e-4, model=net)
-    out = net(T(fx['x']).to(DEV))
-    cn = net.engine().net(tuple(fx['x'].shape), True)
+    opt, out, eng, own, idx = NC.train_step_prologue(net, [T(fx['x']).to(DEV)], fx, logits_tol=2e-3, loss_tol=2e-3)
+    cn = eng.net(tuple(fx['x'].shape), True)
     ops = [o[0] for o in cn.fwd.ops]
     bops = [(o[0], s) for o, s in zip(cn.bwd.ops, cn.bwd.streams)]
     names = [o for o, _ in bops]
@@ -489,120 +456,40 @@ def test_one_training_step_matches_reference():
     assert names.count('dense_conv_dgrad') == names.count('dense_conv_wgrad') == N_DENSE
     assert all(s == 1 for o, s in bops if o == 'dense_conv_wgrad')          # the weight gradient rides the side stream
     _no_prefix_copy(net, cn)
-    assert_close(out.detach().cpu(), fx['train_logits'], 2e-3, 'train logits')
-    loss = losses.lovasz_loss(out, T(fx['t']).to(DEV)) * 1.0
-    loss.backward()
-    ref = float(fx['train_loss'])
-    assert abs(float(loss.detach()) - ref) < 2e-3 * max(1.0, abs(ref)), (float(loss.detach()), ref)
-    idx = {n: i for i, n in enumerate(fx['param_names'].tolist())}
-    eng = net.engine()
-    dead = set(net.dead_parameter_names())
-    own = dict(net.named_parameters())
-    gmax = float(fx['grad_norm'][fx['param_has_grad']].max())
-    checked, small, worst, worst_sum, worst_small = 0, 0, (0.0, ''), (0.0, ''), (0.0, '')
-    for k, p in own.items():
-        i = idx[k]
-        has = bool(fx['param_has_grad'][i])
-        assert has == (k not in dead), k
-        if has and (fx['grad_norm'][i] > 1e-4 or p.numel() < 16):          # (every tensor under 16 elements: the absolute bound needs no norm)
-            off, n = eng.grad_range(p)
-            g = eng.grads[off:off + n].double()
-            if n < 16:
-                e = max(abs(float(g.norm()) - fx['grad_norm'][i]), abs(float(g.sum()) - fx['grad_sum'][i])) / gmax
-                worst_small = max(worst_small, (e, k))
-                small += 1
-                continue
-            worst = max(worst, (abs(float(g.norm()) - fx['grad_norm'][i]) / fx['grad_norm'][i], k))
-            worst_sum = max(worst_sum, (abs(float(g.sum()) - fx['grad_sum'][i]) / (fx['grad_norm'][i] * n ** 0.5), k))
-            checked += 1
-    print('densenet train: checked', checked, '+', small, 'small of', len(eng.live_params), 'worst grad norm', worst, 'worst grad sum', worst_sum,
-          'worst small tensor', worst_small)
-    # under 16 elements: five spatial-SE biases, the five 8-element channel-SE biases of the 128-wide decoder, the two-element head bias
-    assert checked > 300 and small == 11 and worst[0] < 1e-2, (checked, small, worst)
-    assert worst_sum[0] < 1e-2, worst_sum
-    assert worst_small[0] < 1e-6, worst_small
+    # under 16 elements (every one of them: the absolute bound needs no norm): five spatial-SE biases, the five 8-element channel-SE
+    # biases of the 128-wide decoder, the two-element head bias
+    NC.check_grad_tally(net, eng, own, idx, fx, 'densenet train:', include_small_below_norm_floor=True, min_checked=300, n_small=11,
+                        norm_tol=1e-2, sum_tol=1e-2, small_tol=1e-6, verbose=False)
     # full gradients at 2e-2, for every tensor the generator recorded: those whose reference gradient is itself within 5e-3 of float64
     # (the early encoder's are not: transition1.conv.weight of the reference is 1.3e-2 off in fp32, this library 1.9e-2)
     full = fx['fullgrad_keys'].tolist()
     assert len(full) >= 8 and float(fx['fullgrad_ref_f32_vs_f64'].max()) <= 5e-3
     assert any('denselayer' in k and k.endswith('conv1.weight') for k in full) and any(k.endswith('norm1.weight') for k in full)
     assert any(k.endswith('norm1.bias') for k in full) and any('transition' in k and k.endswith('conv.weight') for k in full)
-    for k in full:
-        p = own[k]
-        off, n = eng.grad_range(p)
-        e = assert_close(eng.grads[off:off + n].view(p.shape).cpu(), fx['fullgrad:' + k], 2e-2, k)
-        print('densenet full gradient %s: %.3e' % (k, e))
-    opt.step()
-    torch.cuda.synchronize()
-    for k, p in own.items():
-        i = idx[k]
-        if fx['param_has_grad'][i] and fx['grad_norm'][i] > 1e-4:
-            pn, ps = float(p.detach().double().norm()), float(p.detach().double().sum())
-            assert abs(pn - fx['post_norm'][i]) <= 1e-4 * max(fx['post_norm'][i], 1e-3), (k, pn, fx['post_norm'][i])
-            assert abs(ps - fx['post_sum'][i]) <= 1e-4 * max(fx['post_norm'][i] * p.numel() ** 0.5, 1e-3), (k, ps, fx['post_sum'][i])
-    # every layer's running statistics come out as if it had computed them itself
-    sd = net.state_dict()
+    NC.check_full_grads(eng, own, fx, full, tol=2e-2, verbose=True)
+    # every layer's running statistics come out as if it had computed them itself; norm5 is dead in the U-Net: the reference never
+    # runs it either
     assert len(fx['bn_keys']) > 2 * N_DENSE
-    for k, s in zip(fx['bn_keys'].tolist(), fx['bn_sum'].tolist()):
-        if 'norm5' in k:
-            continue                                                               # dead in the U-Net: the reference never runs it either
-        assert abs(float(sd[k].double().sum()) - s) <= 1e-3 * max(1.0, abs(s)), k
+    sd = NC.check_after_adam(opt, net, own, idx, fx, norm_tol=1e-4, sum_tol=1e-4, bn_tol=1e-3, skip_bn='norm5')
     assert int(sd['encoders.encoder.features.denseblock3.denselayer24.norm1.num_batches_tracked']) == 1
 
 
 # ------------------------------------------------------------------------------------------------ trainer
 def _model(dtype='bf16', lr=1e-3, cfg=None):
-    from salt_amd.models import SegmentationModel
-    arch = {'model_params': {'architecture': 'UNetDenseNet', 'out_channels': 2, 'activation': 'sigmoid', 'loss': 'lovasz', 'compute_dtype': dtype},
-            'optimizer_params': {'lr': lr}, 'regularizer_params': {'regularize': True, 'weight_decay_conv2d': 1e-4}}
-    return SegmentationModel(arch, {'epochs': 1}, cfg or {})
+    return NC.family_model('UNetDenseNet', dtype, lr, 1, cfg)
 
 
 def test_step_graph_replay_equals_eager_steps(deterministic_sums):
-    """the procedure of tests/test_gpu_fused_step.py::test_step_graph_replay_equals_eager_steps at [2,3,64,64]: the training step captured
-    into ONE hipGraph (two-stream forward and backward, loss, Adam) and replayed reproduces the eagerly launched steps bit for bit
-    under the fixed summation order"""
-    results = {}
-    for mode in ('eager', 'graph'):
-        torch.manual_seed(11)
-        m = _model()
-        m.step_graph = mode == 'graph'
-        m._to_device()
-        m.model.train()
-        g = torch.Generator().manual_seed(5)
-        X = torch.randn(2, 3, 64, 64, generator=g)
-        M = (torch.rand(2, 1, 64, 64, generator=g) > 0.6).float()
-        Tt = torch.cat([1 - M, M], 1)
-        ls = [float(m._fit_loop([X + 0.01 * i, Tt])['sum']) for i in range(4)]        # step 0 eager, step 1 captures, 2.. replay
-        torch.cuda.synchronize()
-        eng = m.model.engine()
-        results[mode] = (ls, eng.flat.clone(), eng.grads.clone(), sum(len(n.__dict__.get('_step_graphs', {})) for n in eng.nets.values()))
-    assert results['graph'][3] == 1 and results['eager'][3] == 0
-    assert results['eager'][0] == results['graph'][0] and all(np.isfinite(results['eager'][0]))
-    assert torch.equal(results['eager'][2], results['graph'][2]) and torch.equal(results['eager'][1], results['graph'][1])
+    """the procedure of tests/net_checks.py::step_graph_equals_eager at [2,3,64,64]: the training step captured into ONE hipGraph
+    (two-stream forward and backward, loss, Adam) and replayed reproduces the eagerly launched steps bit for bit under the fixed
+    summation order"""
+    NC.step_graph_equals_eager(_model, lambda: NC.noise_batch(5, 2, 64), steps=4)
 
 
 def test_fit_two_steps():
     """SegmentationModel.fit for two steps at [2,3,64,64]: the unchanged trainer (fused step) on the new architecture"""
-    from salt_amd import architectures as A, callbacks as C
+    from salt_amd import architectures as A
+    m, values = NC.fit_steps(lambda cfg: _model(cfg=cfg), A.UNetDenseNet, NC.square_batch(3), 2)
+    print('densenet fit losses', values)
 
-    class Losses(C.Callback):
-        def __init__(self):
-            super().__init__()
-            self.values = []
 
-        def on_batch_end(self, metrics, *a, **k):
-            self.values.append(float(metrics['sum']))
-            self.batch_id += 1
-    torch.manual_seed(0)
-    rec = Losses()
-    m = _model(cfg={'callbacks': [rec]})
-    assert isinstance(m.model, A.UNetDenseNet)
-    g = torch.Generator().manual_seed(3)
-    X = torch.randn(2, 3, 64, 64, generator=g)
-    M = torch.zeros(2, 1, 64, 64)
-    M[:, :, 16:48, 8:40] = 1.0
-    X = X * 0.3 + M
-    m.fit(([[X, torch.cat([1 - M, M], 1)]] * 2, 2))
-    print('densenet fit losses', rec.values)
-    assert len(rec.values) == 2 and all(np.isfinite(rec.values))

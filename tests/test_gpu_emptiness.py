@@ -2,7 +2,6 @@
 plain fp64 reference of emptiness_op_reference.py (every placement, guard patterns, both dtypes), the reference's own F15 fixtures
 through the graph and through the whole network (eval, one training step), the trainer surface with the AUC monitor, and the fused /
 autograd-bridge / hipGraph steps on [B,2,1,1] logits."""
-import ctypes
 
 import numpy as np
 import pytest
@@ -12,14 +11,11 @@ from helpers import golden, T, assert_close
 import closed_form as CF
 import emptiness_op_reference as ER
 from emptiness_op_reference import Placed, VIEW_CASES, VARIANTS
-from test_gpu_models import _fill_closed_form
-from test_gpu_ops_streaming import call, close, code, gen, out_buf, rnd, _abi
+import net_checks as NC
+from abi_ops import Vec, raw, call, close, code, gen, rnd, _abi, DEV, F64, SENTINEL
 
 pytestmark = pytest.mark.gpu
-DEV = 'cuda:0'
-F64 = torch.float64
 TOL32 = 5e-5                    # tests/test_gpu_blocks.py: fp32 block bound
-SENTINEL = -12345.5
 
 # (B, H, W, C, K): one window / several / ragged rows and columns / C that is no multiple of 16 / the workload's C = 512 (four pixel
 # rows per workgroup) / 2048 channels (more pieces than threads in f32) / C > 256 pieces off, K = 8
@@ -30,32 +26,6 @@ def placement(variant, C, dtype):
     """op_reference.VARIANTS 'a' / 'b' / 'c' carried over to C channels: contiguous; a 16-byte aligned slice of a wider buffer; a slice
     that starts 8 bytes past a 16-byte boundary (scalar path)."""
     return {'a': (0, C, C), 'b': (8, C, C + 24), 'c': (2 if dtype == 'f32' else 4, C, C + 24)}[variant]
-
-
-class Guarded:
-    """n fp32 values on the device between two runs of 64 sentinel values."""
-
-    def __init__(self, n, fill=float('nan')):
-        self.buf = torch.full((n + 128,), SENTINEL, dtype=torch.float32, device=DEV)
-        self.win = self.buf[64:64 + n]
-        self.win.fill_(fill)
-
-    def ptr(self):
-        return self.win.data_ptr()
-
-    def get(self, shape):
-        b = self.buf.cpu()
-        assert bool((b[:64] == SENTINEL).all()) and bool((b[-64:] == SENTINEL).all()), 'write outside an fp32 output'
-        return b[64:-64].reshape(shape).to(F64)
-
-
-def raw(name, **kw):
-    abi = _abi()
-    fn, S = abi.OP_FUNCS[name]
-    args = abi.fill(S(), **kw)
-    rc = fn(ctypes.byref(args), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
-    torch.cuda.synchronize()
-    return rc
 
 
 def head_case(dtype, shape, vx, vdx, with_bias, accumulate, what):
@@ -72,7 +42,7 @@ def head_case(dtype, shape, vx, vdx, with_bias, accumulate, what):
     bd = bias.float().to(DEV) if with_bias else None
     px = Placed((B, H, W), vx, dtype, DEV, x)
     before = px.buf.clone()
-    logits, pooled, logits_eval = Guarded(B * K * OH * OW), Guarded(B * OH * OW * C), Guarded(B * K * OH * OW)
+    logits, pooled, logits_eval = Vec(B * K * OH * OW), Vec(B * OH * OW * C), Vec(B * K * OH * OW)
     fields = dict(dtype=code(dtype), x=px.view, w=wd.data_ptr(), bias=bd.data_ptr() if with_bias else None, K=K)
     call('salt_pool_head', logits_nchw=logits.ptr(), pooled=pooled.ptr(), **fields)
     call('salt_pool_head', logits_nchw=logits_eval.ptr(), pooled=None, **fields)
@@ -87,7 +57,7 @@ def head_case(dtype, shape, vx, vdx, with_bias, accumulate, what):
     sc = (B, H, W, C)
     old = rnd(sc, g, dtype) if accumulate else torch.full(sc, float('nan'), dtype=F64)
     pdx = Placed((B, H, W), vdx, dtype, DEV, old)
-    gw, gb = Guarded(K * C), Guarded(K)
+    gw, gb = Vec(K * C), Vec(K)
     bw = dict(dtype=code(dtype), w=wd.data_ptr(), K=K, dlogits_nchw=dld.data_ptr(), pooled=pooled.ptr(), accumulate=accumulate)
     call('salt_pool_head_bwd', dx=pdx.view, gw=gw.ptr(), gb=gb.ptr() if with_bias else None, **bw)
     pdx.check(what + ' dx')
@@ -105,7 +75,7 @@ def head_case(dtype, shape, vx, vdx, with_bias, accumulate, what):
     else:
         assert bool(torch.isnan(got_gb).all()), what + ': gb written although NULL was passed'
     # dx.p == NULL: no data gradient, the same parameter gradients, bit for bit (and run to run)
-    gw2, gb2 = Guarded(K * C), Guarded(K)
+    gw2, gb2 = Vec(K * C), Vec(K)
     call('salt_pool_head_bwd', dx=shaped_view(None, B, H, W, C, C), gw=gw2.ptr(), gb=gb2.ptr() if with_bias else None, **bw)
     assert torch.equal(got_gw, gw2.get((K, C))), what + ': gw is not reproducible'
     if with_bias:
@@ -145,7 +115,7 @@ def test_bad_arguments_are_refused_and_launch_nothing():
     B, H, W, C, K = 2, 8, 8, 16, 2
     x = torch.randn(B, H, W, C, device=DEV)
     w, bias = torch.randn(K, C, device=DEV), torch.randn(K, device=DEV)
-    logits, pooled = Guarded(B * 8, fill=SENTINEL), Guarded(B * C, fill=SENTINEL)
+    logits, pooled = Vec(B * 8, fill=SENTINEL), Vec(B * C, fill=SENTINEL)
     okf = dict(dtype=0, x=shaped_view(x.data_ptr(), B, H, W, C), w=w.data_ptr(), bias=bias.data_ptr(), K=K, logits_nchw=logits.ptr(), pooled=pooled.ptr())
     for what, bad in (('K=0', dict(K=0)), ('K=9', dict(K=9)), ('H=7', dict(x=shaped_view(x.data_ptr(), B, 7, W, C))),
                       ('W=7', dict(x=shaped_view(x.data_ptr(), B, H, 7, C))), ('NULL x', dict(x=shaped_view(None, B, H, W, C))),
@@ -156,7 +126,7 @@ def test_bad_arguments_are_refused_and_launch_nothing():
         assert bool((logits.get((B * 8,)) == SENTINEL).all()) and bool((pooled.get((B * C,)) == SENTINEL).all()), what
     dl = torch.randn(B, K, 1, 1, device=DEV)
     dx = torch.full((B, H, W, C), SENTINEL, device=DEV)
-    gw, gb = Guarded(K * C, fill=SENTINEL), Guarded(K, fill=SENTINEL)
+    gw, gb = Vec(K * C, fill=SENTINEL), Vec(K, fill=SENTINEL)
     pooled_ok = torch.randn(B, 1, 1, C, device=DEV)
     ok = dict(dtype=0, dx=shaped_view(dx.data_ptr(), B, H, W, C), w=w.data_ptr(), K=K, dlogits_nchw=dl.data_ptr(), pooled=pooled_ok.data_ptr(),
               accumulate=0, gw=gw.ptr(), gb=gb.ptr())
@@ -235,7 +205,7 @@ def fixture_input(fx):
 
 def _net(depth, dtype='f32'):
     from salt_amd import architectures as A
-    return _fill_closed_form(A.EmptinessClassifier(2, depth)).set_compute_dtype(dtype).to(DEV)
+    return NC.fill_closed_form(A.EmptinessClassifier(2, depth)).set_compute_dtype(dtype).to(DEV)
 
 
 @pytest.mark.parametrize('name,depth', NETS)
@@ -267,26 +237,16 @@ def test_eval_logits_and_decisions_match_reference(name, depth):
 
 @pytest.mark.parametrize('name', [n for n, _ in NETS[:2]])
 def test_one_training_step_matches_reference(name):
-    """zero_grad -> forward -> lovasz -> backward -> Adam(lr 1e-4, L2 1e-4) as models.py:105-136; procedure and tolerances of
+    """zero_grad -> forward -> lovasz -> backward -> Adam(lr 1e-4, L2 1e-4) as models.py:105-136; prologue, full gradients and the
+    post-step checks by the procedures of tests/net_checks.py, tolerances of
     tests/test_gpu_depth.py::test_one_training_step_matches_reference.  Every live tensor is checked: 62 for ResNet18 (60 of the encoder
     plus the classifier's weight and bias)."""
-    from salt_amd.optim import FusedAdam, weight_regularization
-    from salt_amd import losses
     fx = golden(name)
     assert float(fx['ref_f32_vs_f64_gradnorm_rel']) <= 2.5e-3             # the reference's own error: a quarter of the 1e-2 below
     net = _net(18)
     net.train()
-    opt = FusedAdam(weight_regularization(net, True, 1e-4), lr=1e-4, model=net)
-    out = net(fixture_input(fx).to(DEV))
-    assert_close(out.detach().cpu(), fx['train_logits'], 2e-3, 'train logits')
-    loss = losses.lovasz_loss(out, T(fx['t']).to(DEV)) * 1.0
-    loss.backward()
-    ref = float(fx['train_loss'])
-    assert abs(float(loss) - ref) < 2e-3 * max(1.0, abs(ref)), (float(loss), ref)
-    idx = {n: i for i, n in enumerate(fx['param_names'].tolist())}
-    eng = net.engine()
+    opt, out, eng, own, idx = NC.train_step_prologue(net, [fixture_input(fx).to(DEV)], fx, logits_tol=2e-3, loss_tol=2e-3)
     dead = set(net.dead_parameter_names())
-    own = dict(net.named_parameters())
     checked, worst, worst_sum = 0, (0.0, ''), (0.0, '')
     for k, p in own.items():
         i = idx[k]
@@ -302,30 +262,13 @@ def test_one_training_step_matches_reference(name):
     assert checked == len(eng.live_params) == 62, (checked, len(eng.live_params))
     assert worst[0] < 1e-2, worst
     assert worst_sum[0] < 1e-2, worst_sum
-    for k in ('fullgrad:classifier.1.weight', 'fullgrad:classifier.1.bias'):
-        p = own[k[9:]]
-        off, n = eng.grad_range(p)
-        e = assert_close(eng.grads[off:off + n].view(p.shape).cpu(), fx[k], 2e-2, k)
-        print('  ', k, '%.3e' % e)
-    opt.step()
-    torch.cuda.synchronize()
-    for k, p in own.items():
-        i = idx[k]
-        if fx['param_has_grad'][i] and fx['grad_norm'][i] > 1e-4:
-            pn, ps = float(p.detach().double().norm()), float(p.detach().double().sum())
-            assert abs(pn - fx['post_norm'][i]) <= 1e-4 * max(fx['post_norm'][i], 1e-3), (k, pn, fx['post_norm'][i])
-            assert abs(ps - fx['post_sum'][i]) <= 1e-4 * max(fx['post_norm'][i] * p.numel() ** 0.5, 1e-3), (k, ps, fx['post_sum'][i])
-    sd = net.state_dict()
-    for k, s in zip(fx['bn_keys'].tolist(), fx['bn_sum'].tolist()):
-        assert abs(float(sd[k].double().sum()) - s) <= 1e-3 * max(1.0, abs(s)), k
+    NC.check_full_grads(eng, own, fx, ['classifier.1.weight', 'classifier.1.bias'], tol=2e-2, verbose=True)
+    NC.check_after_adam(opt, net, own, idx, fx, norm_tol=1e-4, sum_tol=1e-4, bn_tol=1e-3, skip_bn=None)
 
 
 # ------------------------------------------------------------------------------------------------ trainer
 def _model(loss='lovasz', dtype='bf16', lr=1e-3, cfg=None, epochs=1):
-    from salt_amd.models import SegmentationModel
-    arch = {'model_params': {'architecture': 'EmptinessClassifier', 'out_channels': 2, 'activation': 'sigmoid', 'loss': loss, 'compute_dtype': dtype},
-            'optimizer_params': {'lr': lr}, 'regularizer_params': {'regularize': True, 'weight_decay_conv2d': 1e-4}}
-    return SegmentationModel(arch, {'epochs': epochs}, cfg or {})
+    return NC.family_model('EmptinessClassifier', dtype, lr, epochs, cfg, loss=loss)
 
 
 def _tiles(n, seed):
@@ -343,16 +286,7 @@ def _tiles(n, seed):
 
 def test_fit_transform_persist_load_with_the_auc_monitor(tmp_path):
     from salt_amd import callbacks as C, input_pipeline as IP
-
-    class Losses(C.Callback):
-        def __init__(self):
-            super().__init__()
-            self.values = []
-
-        def on_batch_end(self, metrics, *a, **k):
-            self.values.append(metrics['sum'])
-            self.batch_id += 1
-    rec = Losses()
+    rec = NC.Losses()
     ck = str(tmp_path / 'ck' / 'best.torch')
     cfg = {'callbacks': [rec],
            'model_checkpoint': {'filepath': ck, 'epoch_every': 1, 'metric_name': 'auc', 'minimize': False},

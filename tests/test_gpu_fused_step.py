@@ -13,19 +13,11 @@ import torch
 
 from helpers import golden, T, assert_close
 import closed_form as CF
-from test_gpu_models import _fill_closed_form, _grad_report
+from net_checks import fill_closed_form, grad_report, segmentation_model
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda:0'
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _segmentation_model(architecture, loss='lovasz', dtype='f32', lr=1e-4):
-    from salt_amd.models import SegmentationModel
-    arch = {'model_params': {'architecture': architecture, 'out_channels': 2, 'activation': 'sigmoid', 'loss': loss, 'compute_dtype': dtype},
-            'optimizer_params': {'lr': lr}, 'regularizer_params': {'regularize': True, 'weight_decay_conv2d': 1e-4}}
-    m = SegmentationModel(arch, {'epochs': 1}, {})
-    return m
 
 
 @pytest.mark.parametrize('tag,architecture', [('unet_resnet34_hyper', 'UNetResNet'), ('ternaus_resnet34_deconv', 'TernausUNetResNet')])
@@ -34,8 +26,8 @@ def test_fit_loop_fused_step_matches_reference_golden(tag, architecture):
     post-Adam weight norms and BatchNorm running-statistics sums exactly as test_one_training_step_matches_reference asserts
     them for the autograd-bridge path."""
     fx = golden('F8_' + tag)
-    m = _segmentation_model(architecture)
-    _fill_closed_form(m.model)
+    m = segmentation_model(architecture)
+    fill_closed_form(m.model)
     m._to_device()
     m.model.train()
     net = m.model
@@ -82,7 +74,7 @@ def test_fit_loop_fused_step_matches_oracle_step(loss):
     Adam + L2): loss value, every parameter gradient (relative L2 / cosine), and the updated weights."""
     from oracle import nets as ON, specs as OS, losses as OL
     torch.manual_seed(5)
-    m = _segmentation_model('UNetResNet', loss)
+    m = segmentation_model('UNetResNet', loss)
     spec = OS.SPECS['UNetResNet'](with_fc=True)
     sd = OS.init_state(spec, seed=7)
     m.model.load_state_dict({k: sd[k] for k in m.model.state_dict() if k in sd}, strict=False)
@@ -102,7 +94,7 @@ def test_fit_loop_fused_step_matches_oracle_step(loss):
     torch.cuda.synchronize()
     assert abs(float(metrics['sum']) - float(loss_r)) < 1e-4 * max(1.0, abs(float(loss_r)))
     # Lovasz: g_k = J_k - J_(k-1) carries ~1e-3 relative fp32 cancellation noise in torch itself (test_gpu_models.py)
-    worst, cos, n = _grad_report(m.model, {k: sd[k].grad for k in keys})
+    worst, cos, n = grad_report(m.model, {k: sd[k].grad for k in keys})
     assert n > 120 and worst[0] < 5e-2 and cos > 0.9999, (worst, cos, n)
     # the oracle's Adam + L2 step on the oracle's gradients vs the fused Adam kernel on the HIP gradients
     params = [sd[k] for k in keys]
@@ -150,7 +142,7 @@ def test_grad_scale_half_on_doubled_gradients_equals_plain_step(branch, determin
     results = {}
     for mode in ('plain', 'two'):
         torch.manual_seed(11)
-        m = _segmentation_model('UNetResNet', 'lovasz', dtype='bf16', lr=1e-3)
+        m = segmentation_model('UNetResNet', 'lovasz', dtype='bf16', lr=1e-3)
         if branch == 'bridge':
             m.loss_function = [('mask', lambda o, t: losses.lovasz_loss(o, t), 1.0)]
         if mode == 'two':
@@ -184,7 +176,7 @@ def test_bf16_whole_network_vs_fp32_oracle_c2_shape():
     from oracle import nets as ON, specs as OS, losses as OL, blocks as OB
     from salt_amd import losses as HL
     torch.manual_seed(5)
-    m = _segmentation_model('UNetResNet', 'bce_dice', dtype='bf16')
+    m = segmentation_model('UNetResNet', 'bce_dice', dtype='bf16')
     spec = OS.SPECS['UNetResNet'](with_fc=True)
     sd = OS.init_state(spec, seed=7)
     m.model.load_state_dict({k: sd[k] for k in m.model.state_dict() if k in sd}, strict=False)
@@ -226,7 +218,7 @@ def test_bf16_whole_network_vs_fp32_oracle_c2_shape():
     cnet = m.model.engine().net((32, 3, 128, 128), True)
     logits = cnet.logits.cpu()
     e_train, e_train_emu = rel_l2(logits, out_r), rel_l2(out_e, out_r)
-    worst, cos, n = _grad_report(m.model, g_r)
+    worst, cos, n = grad_report(m.model, g_r)
     flat_r = torch.cat([g_r[k].double().reshape(-1) for k in keys])
     flat_e = torch.cat([g_e[k].double().reshape(-1) for k in keys])
     cos_emu = float((flat_r * flat_e).sum() / (flat_r.norm() * flat_e.norm()))
@@ -263,7 +255,7 @@ def test_step_graph_replay_equals_eager_steps(deterministic_sums):
     results = {}
     for mode in ('eager', 'graph'):
         torch.manual_seed(11)
-        m = _segmentation_model('UNetResNet', 'lovasz', dtype='bf16', lr=1e-3)
+        m = segmentation_model('UNetResNet', 'lovasz', dtype='bf16', lr=1e-3)
         m.step_graph = mode == 'graph'
         m._to_device()
         m.model.train()
@@ -353,7 +345,7 @@ def test_planar_hypercolumn_equals_interleaved(monkeypatch):
         if mode == 'interleaved':
             monkeypatch.setenv('SALT_NO_PLANAR', '1')
         torch.manual_seed(11)
-        m = _segmentation_model('UNetResNet', 'lovasz', dtype='bf16', lr=1e-3)
+        m = segmentation_model('UNetResNet', 'lovasz', dtype='bf16', lr=1e-3)
         m._to_device()
         g = torch.Generator().manual_seed(5)
         X = torch.randn(4, 3, 128, 128, generator=g)
@@ -394,7 +386,7 @@ def test_fused_step_with_an_unbindable_input_equals_the_contiguous_float32_step(
     results = {}
     for mode in ('plain', case):
         torch.manual_seed(11)
-        m = _segmentation_model('UNetResNet', 'lovasz', dtype='bf16', lr=1e-3)
+        m = segmentation_model('UNetResNet', 'lovasz', dtype='bf16', lr=1e-3)
         m._to_device()
         m.model.train()
         Xd = X.to(DEV)

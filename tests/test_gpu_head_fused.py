@@ -109,13 +109,13 @@ def test_head_bn_ops_vs_torch(case, dtype):
 def test_fused_final_block_equals_separate_launches(dtype, monkeypatch):
     """The shipped training step (SegmentationModel._fit_loop) with the fused final block against SALT_HEAD_BN=0: same operands, same
     rounding points, other summation partitions - logits, loss, every parameter after two steps."""
-    from test_gpu_fused_step import _segmentation_model
+    from net_checks import segmentation_model
     results = {}
     for mode in ('fused', 'separate'):
         if mode == 'separate':
             monkeypatch.setenv('SALT_HEAD_BN', '0')
         torch.manual_seed(21)
-        m = _segmentation_model('UNetResNet', 'lovasz', dtype=dtype, lr=1e-3)
+        m = segmentation_model('UNetResNet', 'lovasz', dtype=dtype, lr=1e-3)
         m._to_device()
         m.model.train()
         g = torch.Generator().manual_seed(5)
@@ -159,7 +159,7 @@ def test_scse_applies_the_producer_batchnorm_itself(dtype, monkeypatch):
     tests/test_gpu_blocks.py (F4_decoderblock_*, which runs the fused default)."""
     from gpu_harness import BlockRun, load_into
     from helpers import golden, T
-    from test_gpu_blocks import BLOCKS, _fixture_state, _mods
+    from gpu_harness import BLOCKS, _fixture_state, _mods
     A = _mods()
     fx = golden('F4_decoderblock_skip_train')
     make, emit = BLOCKS['F4_decoderblock_skip']
@@ -219,12 +219,12 @@ def test_conv_bn_relu_final_blocks_fuse_through_graph_head(arch, dtype, monkeypa
     travel through the fp64 shards (the vanilla U-Net of BASELINE C0 / C1; the k4 transposed convolutions in front of unet_models' heads
     keep the per-tile partials protocol and the separate launches): one training step with the fusion against SALT_HEAD_BN=0 - same
     loss, same gradients to summation order, one operator fewer in each direction."""
-    from test_gpu_fused_step import _segmentation_model
+    from net_checks import segmentation_model
     res = {}
     for mode in ('fused', 'separate'):
         monkeypatch.setenv('SALT_HEAD_BN', '1' if mode == 'fused' else '0')
         torch.manual_seed(31)
-        m = _segmentation_model(arch, 'bce_dice', dtype=dtype, lr=1e-3)
+        m = segmentation_model(arch, 'bce_dice', dtype=dtype, lr=1e-3)
         m._to_device()
         m.model.train()
         ch = 1 if arch == 'VanillaUNet' else 3

@@ -14,14 +14,9 @@ import torch.nn.functional as F
 from torch import nn
 
 from helpers import assert_close
+from abi_ops import _abi, DEV
 
 pytestmark = pytest.mark.gpu
-DEV = 'cuda:0'
-
-
-def _abi():
-    from salt_amd import _abi
-    return _abi
 
 
 def _view(t, C=None):

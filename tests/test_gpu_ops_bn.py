@@ -4,7 +4,7 @@ N == 1), salt_bn_fold, the consumer-side finalize of salt_affine_act (fin_acc) a
 with and without ticket, caller-written partials / shards), its mask sources, da_bias, dres, the accumulate flags, the two channel
 blocks of a 301-channel scalar reduction, the grid-stride loop of the apply pass and the secondary sums.
 
-Tolerances (none measured on the kernels): elementwise outputs as in test_gpu_ops_streaming.py; per-channel reductions 1.5e-4 of the
+Tolerances (none measured on the kernels): elementwise outputs as in test_gpu_ops_streaming.py (close() of abi_ops.py); per-channel reductions 1.5e-4 of the
 vector's max where sums are formed in fp32 tiles (tol * 3 of test_gpu_blocks.py for dgamma / dbeta), 1e-6 where the kernels work in fp64
 from caller-given partials or shards."""
 import ctypes
@@ -14,7 +14,7 @@ import torch
 
 import op_reference as R
 from op_reference import Placed, VIEW_CASES, VARIANTS
-from test_gpu_ops_streaming import _abi, call, code, gen, rnd, close, null_view, DEV, F64, NAN, VIEWS_IDS
+from abi_ops import _abi, call, code, gen, rnd, close, null_view, DEV, F64, NAN, VIEWS_IDS
 
 pytestmark = pytest.mark.gpu
 TOL_TILE, TOL_F64 = 1.5e-4, 1e-6

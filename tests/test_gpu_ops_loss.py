@@ -12,7 +12,7 @@ import pytest
 import torch
 
 import op_reference as R
-from test_gpu_ops_streaming import _abi, call, gen, DEV, F64, NAN
+from abi_ops import _abi, call, gen, DEV, F64, NAN
 
 pytestmark = pytest.mark.gpu
 

@@ -6,7 +6,6 @@ odd sizes, all four pad sides, and the grid-stride loops of affine_act.
 Tolerances (none measured on the kernels): selections / permutations exact; f32 5e-5 of max|ref| (TOL32 of test_gpu_blocks.py); bf16
 one rounding of an fp32 result: 2**-8 |ref| + 5e-5 max|ref| per element; bilinear as in test_gpu_bilinear_rows.py."""
 import ctypes
-import zlib
 
 import pytest
 import torch
@@ -14,73 +13,15 @@ import torch.nn.functional as F
 
 import op_reference as R
 from op_reference import Placed, VIEW_CASES, VARIANTS
+from abi_ops import _abi, call, code, gen, rnd, close, shape_c, out_buf, null_view, DEV, F64, NAN, VIEWS_IDS
 
 pytestmark = pytest.mark.gpu
-DEV = 'cuda:0'
-F64 = torch.float64
 DTYPES = ['f32', 'bf16']
 SHAPES = [(2, 6, 8), (3, 7, 5), (1, 1, 1), (2, 2, 2)]
-NAN = float('nan')
-
-
-def _abi():
-    import salt_amd  # noqa: F401
-    from salt_amd import _abi
-    return _abi
-
-
-def call(name, **kw):
-    abi = _abi()
-    fn, S = abi.OP_FUNCS[name]
-    args = abi.fill(S(), **kw)
-    rc = fn(ctypes.byref(args), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
-    abi.check(rc, name)
-    torch.cuda.synchronize()
-
-
-def code(dtype):
-    return 1 if dtype == 'bf16' else 0
-
-
-def gen(*seed):
-    return torch.Generator().manual_seed(zlib.crc32(repr(seed).encode()))
-
-
-def rnd(shape, g, dtype, scale=1.0):
-    return R.round_to(torch.randn(shape, generator=g, dtype=F64) * scale, dtype)
 
 
 def ints(shape, g):
     return torch.randint(-3, 4, shape, generator=g).to(F64)            # small integers: exact in bf16, many ties
-
-
-def close(got, ref, dtype, what=''):
-    """f32: |got - ref| <= 5e-5 max|ref|;  bf16: <= 2**-8 |ref| + 5e-5 max|ref| per element."""
-    assert got.shape == ref.shape, (what, got.shape, ref.shape)
-    assert bool(torch.isfinite(got).all()), '%s: non-finite output' % what
-    mx = float(ref.abs().max()) if ref.numel() else 0.0
-    bound = 5e-5 * mx + (2.0 ** -8 * ref.abs() if dtype == 'bf16' else 0.0)
-    err = (got - ref).abs()
-    print('%s [%s]: max err %.3e, max|ref| %.3e' % (what, dtype, float(err.max()), mx))
-    assert bool((err <= bound).all()), '%s [%s]: max err %.3e (max|ref| %.3e), %d elements over the bound' % (
-        what, dtype, float(err.max()), mx, int((err > bound).sum()))
-
-
-def shape_c(shape, variant, dtype):
-    return tuple(shape) + (VARIANTS[variant][dtype][1],)
-
-
-def out_buf(shape, variant, dtype, accumulate, g):
-    """Output window: random contents for accumulate = 1 (returned as `old`), NaN for accumulate = 0."""
-    old = rnd(shape_c(shape, variant, dtype), g, dtype) if accumulate else torch.full(shape_c(shape, variant, dtype), NAN, dtype=F64)
-    return Placed(shape, variant, dtype, DEV, old), old
-
-
-VIEWS_IDS = ['%s-%s' % v for v in VIEW_CASES]
-
-
-def null_view():
-    return _abi().STRUCTS['salt_view']()
 
 
 # ---------------------------------------------------------------- relu_bwd / add / layout

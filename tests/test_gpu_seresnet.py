@@ -11,7 +11,6 @@ that the float32 evaluation takes every ReLU decision like float64 and no pre-ac
 that do are excluded, capped at 0.5 %."""
 import ctypes
 
-import numpy as np
 import pytest
 import torch
 
@@ -19,81 +18,15 @@ from helpers import golden, T, assert_close, rel_err
 import closed_form as CF
 import se_res_op_reference as SR
 import seresnet_oracle as SO
-from test_gpu_models import _fill_closed_form
+import net_checks as NC
+from abi_ops import Act, Vec, raw, call, _abi, DEV, F64, SENTINEL
 
 pytestmark = pytest.mark.gpu
-DEV = 'cuda:0'
-F64 = torch.float64
-SENTINEL = -12345.5
 TOL32, TOLBF = 5e-5, 4e-2                   # tests/test_gpu_blocks.py: the F2 / F4 block bounds
 
 # (B, H, W, C): fewer pixels than pixel rows of a workgroup; an odd, non-square map; a 1x1 map and a 2x2 map at C = 2048 (four channel
 # chunks per pixel part, the FC streaming its 1 MB matrices); several row groups per workgroup; 256 pixels (one part) at C = 1024
 SHAPES = [(2, 4, 4, 256), (3, 3, 5, 256), (1, 1, 1, 2048), (2, 2, 2, 2048), (2, 8, 8, 512), (2, 16, 16, 1024)]
-TDT = {'f32': torch.float32, 'bf16': torch.bfloat16}
-
-
-def _abi():
-    import salt_amd  # noqa: F401
-    from salt_amd import _abi
-    return _abi
-
-
-def raw(name, **kw):
-    abi = _abi()
-    fn, S = abi.OP_FUNCS[name]
-    args = abi.fill(S(), **kw)
-    rc = fn(ctypes.byref(args), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
-    torch.cuda.synchronize()
-    return rc
-
-
-def call(name, **kw):
-    rc = raw(name, **kw)
-    _abi().check(rc, name)
-
-
-class Vec:
-    """n fp32 (or fp64) values on the device between two runs of 64 sentinel values."""
-
-    def __init__(self, n, fill=float('nan'), dtype=torch.float32):
-        self.buf = torch.full((n + 128,), SENTINEL, dtype=dtype, device=DEV)
-        self.win = self.buf[64:64 + n]
-        self.win.fill_(fill)
-
-    def ptr(self):
-        return self.win.data_ptr()
-
-    def get(self, shape):
-        b = self.buf.cpu()
-        assert bool((b[:64] == SENTINEL).all()) and bool((b[-64:] == SENTINEL).all()), 'write outside an fp32 output'
-        return b[64:-64].reshape(shape).to(F64)
-
-
-class Act:
-    """[B,H,W,C] activation in ``dtype`` storage on the device: contiguous, or (``sliced``) channels [32, 32 + C) of rows C + 96 wide whose
-    other channels hold a sentinel.  ``check`` asserts that nothing outside the window changed."""
-
-    def __init__(self, data, dtype, sliced):
-        from salt_amd.engine import shaped_view
-        B, H, W, C = data.shape
-        self.C, self.c0, self.cs = C, (32 if sliced else 0), (C + 96 if sliced else C)
-        self.sentinel = float(torch.tensor(SENTINEL, dtype=TDT[dtype]).float())          # as the storage dtype holds it
-        self.buf = torch.full((B * H * W * self.cs + 128,), SENTINEL, dtype=TDT[dtype], device=DEV)
-        self.rows = self.buf[64:64 + B * H * W * self.cs].view(B, H, W, self.cs)
-        self.rows[..., self.c0:self.c0 + C] = data.to(TDT[dtype]).to(DEV)
-        self.view = shaped_view(self.rows.data_ptr() + self.c0 * self.buf.element_size(), B, H, W, C, self.cs)
-
-    def get(self):
-        return self.rows[..., self.c0:self.c0 + self.C].cpu().to(F64)
-
-    def check(self, what):
-        b, r = self.buf.cpu().float(), self.rows.cpu().float()
-        ok = bool((b[:64] == self.sentinel).all()) and bool((b[-64:] == self.sentinel).all())
-        ok = ok and bool((r[..., :self.c0] == self.sentinel).all()) and bool((r[..., self.c0 + self.C:] == self.sentinel).all())
-        assert ok, '%s: write outside the view' % what
-
-
 _CASES = {}
 
 
@@ -380,19 +313,12 @@ def test_bottleneck_protocols_agree_with_golden(env, monkeypatch):
 # ------------------------------------------------------------------------------------------------ whole network
 def _net(depth, fx, dtype='f32'):
     from salt_amd import architectures as A
-    net = _fill_closed_form(A.UNetSeResNet(depth, 2, dropout_2d=0.0, pretrained=False, use_hypercolumn=True))
+    net = NC.fill_closed_form(A.UNetSeResNet(depth, 2, dropout_2d=0.0, pretrained=False, use_hypercolumn=True))
     with torch.no_grad():
         for k, p in net.named_parameters():
             if k.endswith(SO.FC2_KEY):
                 p.mul_(float(fx['fc2_scale']))
     return net.set_compute_dtype(dtype).to(DEV)
-
-
-def _margin(fx):
-    ref = fx['eval_logits'][:, 1]
-    under = np.abs(ref) < 10 * float(fx['ref_f32_vs_f64_maxabs'])
-    assert int(under.sum()) == int(fx['margin_pixels']) <= 0.001 * ref.size
-    return ~under
 
 
 @pytest.mark.parametrize('name,depth', [('F17_unet_seresnet50_hyper', 50), ('F17_unet_seresnet101_hyper', 101)])
@@ -402,40 +328,26 @@ def test_eval_logits_and_masks_match_reference(name, depth):
     net = _net(depth, fx).eval()
     with torch.no_grad():
         logits = net(x).cpu()
-    e = assert_close(logits, fx['eval_logits'], 1e-3, 'eval logits')
-    safe = _margin(fx)
-    mine, ref = (logits[:, 1] > 0).numpy(), fx['eval_logits'][:, 1] > 0
-    print('seresnet eval', name, 'rel err %.3e' % e, 'pixels left out', int((~safe).sum()), 'mask differences', int((mine != ref).sum()))
-    assert np.array_equal(mine[safe], ref[safe])
+    NC.check_eval_masks(logits, fx, 'seresnet eval ' + name, logits_tol=1e-3)
     ops = [o[0] for o in net.engine().net(tuple(x.shape), False).fwd.ops]
     assert ops.count('se_res') == sum(SO.COUNTS[depth])
     if depth != 50:
         return
     # bf16 storage: within 4 x what bf16 storage costs the test-side oracle (the guard factor of tests/test_gpu_emptiness.py), and the same
     # masks wherever the fp32 logit clears that
-    net16 = _net(depth, fx, 'bf16').eval()
-    with torch.no_grad():
-        l16 = net16(x).float().cpu()
-    assert bool(torch.isfinite(l16).all())
-    guard = 4 * float(fx['ref_bf16_storage_vs_f32_maxabs'])
-    err16 = float((l16 - logits).abs().max())
-    safe16 = (logits[:, 1].abs() > guard).numpy()
-    print('seresnet eval bf16', name, 'max |bf16 - f32| %.3e' % err16, 'guard %.3e' % guard, 'pixels under the guard', int((~safe16).sum()))
-    assert err16 <= guard
-    assert np.array_equal((l16[:, 1] > 0).numpy()[safe16], (logits[:, 1] > 0).numpy()[safe16])
+    NC.check_bf16_eval_guard(_net(depth, fx, 'bf16').eval(), x, logits, fx, 'seresnet eval bf16 ' + name, guard_factor=4)
 
 
 @pytest.mark.parametrize('form', ['default', 'stored'])
 def test_one_training_step_matches_reference(form, monkeypatch):
-    """zero_grad -> forward -> lovasz -> backward -> Adam(lr 1e-4, L2 1e-4) as models.py:105-136; procedure of
-    tests/test_gpu_emptiness.py::test_one_training_step_matches_reference.  Gradient norms (and sums) of tensors with 16 elements and more:
-    within 1e-2 relative, four times what the fixture records for the reference's own float32 run against float64.  Tensors under 16
-    elements - the one-element spatial-SE biases (and the two-element head bias), sums over every pixel that cancel almost completely (norm 6e-4 next to 35 for the stem) -
-    are bounded absolutely, within 1e-6 of the largest gradient norm, as tests/test_gpu_models.py:139-144 bounds them; the fixture records
-    the reference's own figure for them as well and it has to be a quarter of that.
+    """zero_grad -> forward -> lovasz -> backward -> Adam(lr 1e-4, L2 1e-4) as models.py:105-136, by the procedures of
+    tests/net_checks.py.  Gradient norms (and sums) of tensors with 16 elements and more: within 1e-2 relative, four times what the
+    fixture records for the reference's own float32 run against float64.  Tensors under 16 elements - the one-element spatial-SE
+    biases (and the two-element head bias), sums over every pixel that cancel almost completely (norm 6e-4 next to 35 for the stem) -
+    are bounded absolutely, within 1e-6 of the largest gradient norm, as the deep branch of
+    tests/test_gpu_models.py::test_one_training_step_matches_reference bounds them; the fixture records the reference's own figure
+    for them as well and it has to be a quarter of that.
     form 'stored' (SALT_SE_RES_IN_BN=0: the SE tail reads the materialised BatchNorm output): the same step, the same bounds."""
-    from salt_amd.optim import FusedAdam, weight_regularization
-    from salt_amd import losses
     if form == 'stored':
         monkeypatch.setenv('SALT_SE_RES_IN_BN', '0')
     fx = golden('F17_unet_seresnet50_hyper')
@@ -443,100 +355,33 @@ def test_one_training_step_matches_reference(form, monkeypatch):
     assert float(fx['ref_f32_vs_f64_small_abs']) <= 2.5e-7                # likewise, of the 1e-6 of the largest norm below
     net = _net(50, fx)
     net.train()
-    opt = FusedAdam(weight_regularization(net, True, 1e-4), lr=1e-4, model=net)
-    out = net(T(fx['x']).to(DEV))
-    ops = [o[0] for o in net.engine().net(tuple(fx['x'].shape), True).fwd.ops]
-    n_act = ops.count('affine_act')
-    print('seresnet train [%s]: forward program: %d se_res, %d affine_act' % (form, ops.count('se_res'), n_act))
+    opt, out, eng, own, idx = NC.train_step_prologue(net, [T(fx['x']).to(DEV)], fx, logits_tol=2e-3, loss_tol=2e-3)
+    ops = [o[0] for o in eng.net(tuple(fx['x'].shape), True).fwd.ops]
+    print('seresnet train [%s]: forward program: %d se_res, %d affine_act' % (form, ops.count('se_res'), ops.count('affine_act')))
     assert ops.count('se_res') == 16
-    assert_close(out.detach().cpu(), fx['train_logits'], 2e-3, 'train logits')
-    loss = losses.lovasz_loss(out, T(fx['t']).to(DEV)) * 1.0
-    loss.backward()
-    ref = float(fx['train_loss'])
-    assert abs(float(loss.detach()) - ref) < 2e-3 * max(1.0, abs(ref)), (float(loss.detach()), ref)
-    idx = {n: i for i, n in enumerate(fx['param_names'].tolist())}
-    eng = net.engine()
-    dead = set(net.dead_parameter_names())
-    own = dict(net.named_parameters())
-    gmax = float(fx['grad_norm'][fx['param_has_grad']].max())
-    checked, small, worst, worst_sum, worst_small = 0, 0, (0.0, ''), (0.0, ''), (0.0, '')
-    for k, p in own.items():
-        i = idx[k]
-        has = bool(fx['param_has_grad'][i])
-        assert has == (k not in dead), k
-        if has and fx['grad_norm'][i] > 1e-4:
-            off, n = eng.grad_range(p)
-            g = eng.grads[off:off + n].double()
-            if n < 16:
-                e = max(abs(float(g.norm()) - fx['grad_norm'][i]), abs(float(g.sum()) - fx['grad_sum'][i])) / gmax
-                print('  small tensor %s: %.3e of the largest norm (%.3e relative)' % (k, e, e * gmax / fx['grad_norm'][i]))
-                worst_small = max(worst_small, (e, k))
-                small += 1
-                continue
-            worst = max(worst, (abs(float(g.norm()) - fx['grad_norm'][i]) / fx['grad_norm'][i], k))
-            worst_sum = max(worst_sum, (abs(float(g.sum()) - fx['grad_sum'][i]) / (fx['grad_norm'][i] * n ** 0.5), k))
-            checked += 1
-    print('seresnet train [%s]: checked' % form, checked, '+', small, 'small of', len(eng.live_params), 'worst grad norm', worst, 'worst grad sum',
-          worst_sum, 'worst small tensor', worst_small)
-    assert checked > 200 and small == 6 and worst[0] < 1e-2, (checked, small, worst)          # five spatial-SE biases and the two-element head bias
-    assert worst_sum[0] < 1e-2, worst_sum
-    assert worst_small[0] < 1e-6, worst_small
-    n_full = 0
-    for k in fx:
-        if k.startswith('fullgrad:'):
-            p = own[k[9:]]
-            off, n = eng.grad_range(p)
-            e = assert_close(eng.grads[off:off + n].view(p.shape).cpu(), fx[k], 2e-2, k)
-            print('  ', k, '%.3e' % e)
-            n_full += 1
-    assert n_full == 8
-    opt.step()
-    torch.cuda.synchronize()
-    for k, p in own.items():
-        i = idx[k]
-        if fx['param_has_grad'][i] and fx['grad_norm'][i] > 1e-4:
-            pn, ps = float(p.detach().double().norm()), float(p.detach().double().sum())
-            assert abs(pn - fx['post_norm'][i]) <= 1e-4 * max(fx['post_norm'][i], 1e-3), (k, pn, fx['post_norm'][i])
-            assert abs(ps - fx['post_sum'][i]) <= 1e-4 * max(fx['post_norm'][i] * p.numel() ** 0.5, 1e-3), (k, ps, fx['post_sum'][i])
-    sd = net.state_dict()
-    for k, s in zip(fx['bn_keys'].tolist(), fx['bn_sum'].tolist()):
-        assert abs(float(sd[k].double().sum()) - s) <= 1e-3 * max(1.0, abs(s)), k
+    # small tensors: five spatial-SE biases and the two-element head bias
+    NC.check_grad_tally(net, eng, own, idx, fx, 'seresnet train [%s]:' % form, include_small_below_norm_floor=False, min_checked=200, n_small=6,
+                        norm_tol=1e-2, sum_tol=1e-2, small_tol=1e-6, verbose=True)
+    full = [k[9:] for k in fx if k.startswith('fullgrad:')]
+    assert len(full) == 8
+    NC.check_full_grads(eng, own, fx, full, tol=2e-2, verbose=True)
+    NC.check_after_adam(opt, net, own, idx, fx, norm_tol=1e-4, sum_tol=1e-4, bn_tol=1e-3, skip_bn=None)
 
 
 # ------------------------------------------------------------------------------------------------ trainer
 def _model(dtype='bf16', lr=1e-3, epochs=1, cfg=None):
-    from salt_amd.models import SegmentationModel
-    arch = {'model_params': {'architecture': 'UNetSeResNet', 'out_channels': 2, 'activation': 'sigmoid', 'loss': 'lovasz', 'compute_dtype': dtype},
-            'optimizer_params': {'lr': lr}, 'regularizer_params': {'regularize': True, 'weight_decay_conv2d': 1e-4}}
-    return SegmentationModel(arch, {'epochs': epochs}, cfg or {})
+    return NC.family_model('UNetSeResNet', dtype, lr, epochs, cfg)
 
 
 def test_fit_persist_load_and_tta(tmp_path):
     """SegmentationModel.fit for 3 steps at [2,3,64,64] (the fused step, unchanged trainer), persist -> load with and without the
     'module.' prefix -> same outputs, predict_tta = mean of the four flips done by hand."""
-    from salt_amd import architectures as A, callbacks as C, inference as I
-
-    class Losses(C.Callback):
-        def __init__(self):
-            super().__init__()
-            self.values = []
-
-        def on_batch_end(self, metrics, *a, **k):
-            self.values.append(float(metrics['sum']))
-            self.batch_id += 1
-    torch.manual_seed(0)
-    rec = Losses()
-    m = _model(dtype='f32', cfg={'callbacks': [rec]})
-    assert isinstance(m.model, A.UNetSeResNet) and m.model.encoders.encoder.layer3[5].se_module.fc1.weight.shape == (64, 1024, 1, 1)
-    g = torch.Generator().manual_seed(3)
-    X = torch.randn(2, 3, 64, 64, generator=g)
-    M = torch.zeros(2, 1, 64, 64)
-    M[:, :, 16:48, 8:40] = 1.0
-    X = X * 0.3 + M
-    Tt = torch.cat([1 - M, M], 1)
-    m.fit(([[X, Tt]] * 3, 3))
-    print('seresnet fit losses', rec.values)
-    assert len(rec.values) == 3 and all(np.isfinite(rec.values)) and rec.values[2] < rec.values[0]
+    from salt_amd import architectures as A, inference as I
+    X, Tt = NC.square_batch(3)
+    m, values = NC.fit_steps(lambda cfg: _model(dtype='f32', cfg=cfg), A.UNetSeResNet, (X, Tt), 3)
+    assert m.model.encoders.encoder.layer3[5].se_module.fc1.weight.shape == (64, 1024, 1, 1)
+    print('seresnet fit losses', values)
+    assert values[2] < values[0]
     ck = str(tmp_path / 'ck.torch')
     m.persist(ck)
     sd = torch.load(ck, map_location='cpu')

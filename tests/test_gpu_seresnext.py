@@ -9,23 +9,25 @@ tol = K 2^-23 sum |x||w| per element with K = 9 Cg (forward, data gradient) or t
 |scale| plus 4 * 2^-23 * (largest epilogue intermediate) for the eval epilogue, plus 2^-8 (|value| + tol) per bf16 storage rounding.
 Statistics are held to the float64 moments of the stored output (conv_abi.moments)."""
 import ctypes
+import functools
 
-import numpy as np
 import pytest
 import torch
 
 from helpers import golden, T, assert_close, rel_err
+import abi_ops
 import closed_form as CF
-import conv_abi as CA
 import gconv_op_reference as GR
+import net_checks as NC
 import seresnext_oracle as SX
-from test_gpu_models import _fill_closed_form
-from test_gpu_seresnet import Act, Vec, raw, call, _abi, _margin, DEV, F64, SENTINEL, TOL32, TOLBF
+from abi_ops import Act, Vec, raw, call, _abi, merge_partials, check_moments, DEV, F64, SENTINEL
 
 pytestmark = pytest.mark.gpu
+TOL32, TOLBF = 5e-5, 4e-2                   # tests/test_gpu_blocks.py: the F2 / F4 block bounds
 CODE = {'f32': 0, 'bf16': 1}
 _CASES = {}
 RATIOS = {}          # {(shape, dtype): {output: worst error / bound}}: the table of DESIGN 17
+held = functools.partial(abi_ops.held, ratio=GR.ratio, ratios=RATIOS)
 
 
 def case_of(shape):
@@ -46,32 +48,6 @@ def ref_of(shape, dtype, what, flag):
         _REFS[key] = (GR.forward_ref(c, dtype, flag, flag) if what == 'fwd' else GR.dgrad_ref(c, dtype, flag) if what == 'dgrad'
                       else GR.wgrad_ref(c, flag))
     return _REFS[key]
-
-
-def held(got, ref, what, case, key):
-    r = GR.ratio(got, ref)
-    per = RATIOS.setdefault(case, {})
-    per[key] = max(per.get(key, 0.0), r)
-    print('%s: worst error / bound %.3f' % (what, r))
-    assert r <= 1.0, '%s: error at %.3f of the bound' % (what, r)
-
-
-def merge_partials(stats, cnt):
-    """Chan's merge of per-tile (sum, M2 about the tile mean, count) in float64 -> (N, S, Q = M2 + S^2 / N)"""
-    N = float(cnt.sum())
-    S = stats[:, 0].sum(0)
-    mean = S / N
-    M2 = (stats[:, 1] + cnt[:, None] * (stats[:, 0] / cnt[:, None] - mean) ** 2).sum(0)
-    return N, S, M2 + S * S / N
-
-
-def check_moments(what, got, dtype, n, s, q):
-    y = got.reshape(-1, got.shape[-1])
-    assert n == y.shape[0], '%s: count %r for %d pixels' % (what, n, y.shape[0])
-    rs, rq, ts, tq = CA.moments(y, dtype)
-    r1, r2 = float(((s - rs).abs() / ts.clamp_min(1e-300)).max()), float(((q - rq).abs() / tq.clamp_min(1e-300)).max())
-    print('%s: sum at %.3f, sum of squares at %.3f of the bound' % (what, r1, r2))
-    assert r1 <= 1.0 and r2 <= 1.0, '%s: sum at %.3f, sum of squares at %.3f of the bound' % (what, r1, r2)
 
 
 def run_forward(shape, dtype, sliced, form):
@@ -312,7 +288,7 @@ def test_bottleneck_partials_protocols_agree_with_golden(fin, monkeypatch):
 # ------------------------------------------------------------------------------------------------ whole network
 def _net(depth, fx, dtype='f32'):
     from salt_amd import architectures as A
-    net = _fill_closed_form(A.UNetSeResNetXt(depth, 2, dropout_2d=0.0, pretrained=False, use_hypercolumn=True))
+    net = NC.fill_closed_form(A.UNetSeResNetXt(depth, 2, dropout_2d=0.0, pretrained=False, use_hypercolumn=True))
     with torch.no_grad():
         for k, p in net.named_parameters():
             if k.endswith(SX.SO.FC2_KEY):
@@ -327,161 +303,52 @@ def test_eval_logits_and_masks_match_reference(name, depth):
     net = _net(depth, fx).eval()
     with torch.no_grad():
         logits = net(x).cpu()
-    e = assert_close(logits, fx['eval_logits'], 1e-3, 'eval logits')
-    safe = _margin(fx)
-    mine, ref = (logits[:, 1] > 0).numpy(), fx['eval_logits'][:, 1] > 0
-    print('seresnext eval', name, 'rel err %.3e' % e, 'pixels left out', int((~safe).sum()), 'mask differences', int((mine != ref).sum()))
-    assert np.array_equal(mine[safe], ref[safe])
+    NC.check_eval_masks(logits, fx, 'seresnext eval ' + name, logits_tol=1e-3)
     cn = net.engine().net(tuple(x.shape), False)
     ops = [o[0] for o in cn.fwd.ops]
     assert ops.count('gconv') == ops.count('se_res') == sum(SX.COUNTS[depth])
     if depth != 50:
         return
-    # hipGraph replay of the eval program equals the eager run
-    st = torch.cuda.Stream()
-    torch.cuda.synchronize()
-    cn.fwd.capture(st)
-    with torch.cuda.stream(st):
-        cn.logits.zero_()
-        cn.x.copy_(x)
-        cn.fwd.replay(st)
-    st.synchronize()
-    assert torch.equal(cn.logits.cpu(), logits)
-    cn.fwd.release_graph()
-    # bf16 storage: within 4 x what bf16 storage costs the test-side oracle, and the same masks wherever the fp32 logit clears that
-    net16 = _net(depth, fx, 'bf16').eval()
-    with torch.no_grad():
-        l16 = net16(x).float().cpu()
-    assert bool(torch.isfinite(l16).all())
-    guard = 4 * float(fx['ref_bf16_storage_vs_f32_maxabs'])
-    err16 = float((l16 - logits).abs().max())
-    safe16 = (logits[:, 1].abs() > guard).numpy()
-    print('seresnext eval bf16', name, 'max |bf16 - f32| %.3e' % err16, 'guard %.3e' % guard, 'pixels under the guard', int((~safe16).sum()))
-    assert err16 <= guard
-    assert np.array_equal((l16[:, 1] > 0).numpy()[safe16], (logits[:, 1] > 0).numpy()[safe16])
+    NC.check_eval_graph_replay(cn, x, logits)
+    NC.check_bf16_eval_guard(_net(depth, fx, 'bf16').eval(), x, logits, fx, 'seresnext eval bf16 ' + name, guard_factor=4)
 
 
 def test_one_training_step_matches_reference():
-    """zero_grad -> forward -> lovasz -> backward -> Adam(lr 1e-4, L2 1e-4) as models.py:105-136, with the bounds
-    tests/test_gpu_seresnet.py uses for F17: gradient norms (and sums) of tensors with 16 elements and more within 1e-2 relative,
-    tensors under 16 elements within 1e-6 of the largest gradient norm."""
-    from salt_amd.optim import FusedAdam, weight_regularization
-    from salt_amd import losses
+    """zero_grad -> forward -> lovasz -> backward -> Adam(lr 1e-4, L2 1e-4) as models.py:105-136, by the procedures of
+    tests/net_checks.py with the bounds tests/test_gpu_seresnet.py uses for F17: gradient norms (and sums) of tensors with 16 elements
+    and more within 1e-2 relative, tensors under 16 elements within 1e-6 of the largest gradient norm."""
     fx = golden('F18_unet_seresnext50_hyper')
     assert float(fx['ref_f32_vs_f64_gradnorm_rel']) <= 2.5e-3 and float(fx['ref_f32_vs_f64_small_abs']) <= 2.5e-7
     net = _net(50, fx)
     net.train()
-    opt = FusedAdam(weight_regularization(net, True, 1e-4), lr=1e-4, model=net)
-    out = net(T(fx['x']).to(DEV))
-    cn = net.engine().net(tuple(fx['x'].shape), True)
+    opt, out, eng, own, idx = NC.train_step_prologue(net, [T(fx['x']).to(DEV)], fx, logits_tol=2e-3, loss_tol=2e-3)
+    cn = eng.net(tuple(fx['x'].shape), True)
     ops = [o[0] for o in cn.fwd.ops]
     bops = [o[0] for o in cn.bwd.ops]
     assert ops.count('gconv') == 16 and ops.count('se_res') == 16 and bops.count('gconv_dgrad') == 16 and bops.count('gconv_wgrad') == 16
-    assert_close(out.detach().cpu(), fx['train_logits'], 2e-3, 'train logits')
-    loss = losses.lovasz_loss(out, T(fx['t']).to(DEV)) * 1.0
-    loss.backward()
-    ref = float(fx['train_loss'])
-    assert abs(float(loss.detach()) - ref) < 2e-3 * max(1.0, abs(ref)), (float(loss.detach()), ref)
-    idx = {n: i for i, n in enumerate(fx['param_names'].tolist())}
-    eng = net.engine()
-    dead = set(net.dead_parameter_names())
-    own = dict(net.named_parameters())
-    gmax = float(fx['grad_norm'][fx['param_has_grad']].max())
-    checked, small, worst, worst_sum, worst_small = 0, 0, (0.0, ''), (0.0, ''), (0.0, '')
-    for k, p in own.items():
-        i = idx[k]
-        has = bool(fx['param_has_grad'][i])
-        assert has == (k not in dead), k
-        if has and (fx['grad_norm'][i] > 1e-4 or p.numel() < 16):          # (every tensor under 16 elements: the absolute bound needs no norm)
-            off, n = eng.grad_range(p)
-            g = eng.grads[off:off + n].double()
-            if n < 16:
-                e = max(abs(float(g.norm()) - fx['grad_norm'][i]), abs(float(g.sum()) - fx['grad_sum'][i])) / gmax
-                worst_small = max(worst_small, (e, k))
-                small += 1
-                continue
-            worst = max(worst, (abs(float(g.norm()) - fx['grad_norm'][i]) / fx['grad_norm'][i], k))
-            worst_sum = max(worst_sum, (abs(float(g.sum()) - fx['grad_sum'][i]) / (fx['grad_norm'][i] * n ** 0.5), k))
-            checked += 1
-    print('seresnext train: checked', checked, '+', small, 'small of', len(eng.live_params), 'worst grad norm', worst, 'worst grad sum', worst_sum,
-          'worst small tensor', worst_small)
-    assert checked > 200 and small == 6 and worst[0] < 1e-2, (checked, small, worst)          # five spatial-SE biases and the two-element head bias
-    assert worst_sum[0] < 1e-2, worst_sum
-    assert worst_small[0] < 1e-6, worst_small
-    n_full = 0
-    for k in fx:
-        if k.startswith('fullgrad:'):
-            p = own[k[9:]]
-            off, n = eng.grad_range(p)
-            assert_close(eng.grads[off:off + n].view(p.shape).cpu(), fx[k], 2e-2, k)
-            n_full += 1
-    assert n_full == 8
-    opt.step()
-    torch.cuda.synchronize()
-    for k, p in own.items():
-        i = idx[k]
-        if fx['param_has_grad'][i] and fx['grad_norm'][i] > 1e-4:
-            pn, ps = float(p.detach().double().norm()), float(p.detach().double().sum())
-            assert abs(pn - fx['post_norm'][i]) <= 1e-4 * max(fx['post_norm'][i], 1e-3), (k, pn, fx['post_norm'][i])
-            assert abs(ps - fx['post_sum'][i]) <= 1e-4 * max(fx['post_norm'][i] * p.numel() ** 0.5, 1e-3), (k, ps, fx['post_sum'][i])
-    sd = net.state_dict()
-    for k, s in zip(fx['bn_keys'].tolist(), fx['bn_sum'].tolist()):
-        assert abs(float(sd[k].double().sum()) - s) <= 1e-3 * max(1.0, abs(s)), k
+    # small tensors (every one under 16 elements: the absolute bound needs no norm): five spatial-SE biases and the two-element head bias
+    NC.check_grad_tally(net, eng, own, idx, fx, 'seresnext train:', include_small_below_norm_floor=True, min_checked=200, n_small=6,
+                        norm_tol=1e-2, sum_tol=1e-2, small_tol=1e-6, verbose=False)
+    full = [k[9:] for k in fx if k.startswith('fullgrad:')]
+    assert len(full) == 8
+    NC.check_full_grads(eng, own, fx, full, tol=2e-2, verbose=False)
+    NC.check_after_adam(opt, net, own, idx, fx, norm_tol=1e-4, sum_tol=1e-4, bn_tol=1e-3, skip_bn=None)
 
 
 # ------------------------------------------------------------------------------------------------ trainer
 def _model(dtype='bf16', lr=1e-3, cfg=None):
-    from salt_amd.models import SegmentationModel
-    arch = {'model_params': {'architecture': 'UNetSeResNetXt', 'out_channels': 2, 'activation': 'sigmoid', 'loss': 'lovasz', 'compute_dtype': dtype},
-            'optimizer_params': {'lr': lr}, 'regularizer_params': {'regularize': True, 'weight_decay_conv2d': 1e-4}}
-    return SegmentationModel(arch, {'epochs': 1}, cfg or {})
+    return NC.family_model('UNetSeResNetXt', dtype, lr, 1, cfg)
 
 
 def test_step_graph_replay_equals_eager_steps(deterministic_sums):
-    """the procedure of tests/test_gpu_fused_step.py::test_step_graph_replay_equals_eager_steps at [2,3,64,64]: the training step with its
-    48 grouped-convolution entries captured into ONE hipGraph (two-stream forward and backward, loss, Adam) and replayed reproduces the
-    eagerly launched steps bit for bit under the fixed summation order"""
-    results = {}
-    for mode in ('eager', 'graph'):
-        torch.manual_seed(11)
-        m = _model()
-        m.step_graph = mode == 'graph'
-        m._to_device()
-        m.model.train()
-        g = torch.Generator().manual_seed(5)
-        X = torch.randn(2, 3, 64, 64, generator=g)
-        M = (torch.rand(2, 1, 64, 64, generator=g) > 0.6).float()
-        Tt = torch.cat([1 - M, M], 1)
-        ls = [float(m._fit_loop([X + 0.01 * i, Tt])['sum']) for i in range(4)]        # step 0 eager, step 1 captures, 2.. replay
-        torch.cuda.synchronize()
-        eng = m.model.engine()
-        results[mode] = (ls, eng.flat.clone(), eng.grads.clone(), sum(len(n.__dict__.get('_step_graphs', {})) for n in eng.nets.values()))
-    assert results['graph'][3] == 1 and results['eager'][3] == 0
-    assert results['eager'][0] == results['graph'][0] and all(np.isfinite(results['eager'][0]))
-    assert torch.equal(results['eager'][2], results['graph'][2]) and torch.equal(results['eager'][1], results['graph'][1])
+    """the procedure of tests/net_checks.py::step_graph_equals_eager at [2,3,64,64]: the training step with its 48 grouped-convolution
+    entries captured into ONE hipGraph (two-stream forward and backward, loss, Adam) and replayed reproduces the eagerly launched steps
+    bit for bit under the fixed summation order"""
+    NC.step_graph_equals_eager(_model, lambda: NC.noise_batch(5, 2, 64), steps=4)
 
 
 def test_fit_two_steps():
     """SegmentationModel.fit for two steps at [2,3,64,64]: the unchanged trainer (fused step) on the new architecture"""
-    from salt_amd import architectures as A, callbacks as C
-
-    class Losses(C.Callback):
-        def __init__(self):
-            super().__init__()
-            self.values = []
-
-        def on_batch_end(self, metrics, *a, **k):
-            self.values.append(float(metrics['sum']))
-            self.batch_id += 1
-    torch.manual_seed(0)
-    rec = Losses()
-    m = _model(cfg={'callbacks': [rec]})
-    assert isinstance(m.model, A.UNetSeResNetXt)
-    g = torch.Generator().manual_seed(3)
-    X = torch.randn(2, 3, 64, 64, generator=g)
-    M = torch.zeros(2, 1, 64, 64)
-    M[:, :, 16:48, 8:40] = 1.0
-    X = X * 0.3 + M
-    m.fit(([[X, torch.cat([1 - M, M], 1)]] * 2, 2))
-    print('seresnext fit losses', rec.values)
-    assert len(rec.values) == 2 and all(np.isfinite(rec.values))
+    from salt_amd import architectures as A
+    m, values = NC.fit_steps(lambda cfg: _model(cfg=cfg), A.UNetSeResNetXt, NC.square_batch(3), 2)
+    print('seresnext fit losses', values)

@@ -2,7 +2,7 @@
 against the float64 operator reference tests/stacking_op_reference.py, StackingFCN / StackingFCNWithDepth against the F16 fixtures the
 reference's own modules produced, and the trainer / inference surface.
 
-Operator tolerances are close() of test_gpu_ops_streaming.py on inputs already rounded to the compute dtype (f32: 5e-5 max|ref|;
+Operator tolerances are close() of abi_ops.py on inputs already rounded to the compute dtype (f32: 5e-5 max|ref|;
 bf16: 2^-8 |ref| + 5e-5 max|ref|).  The BatchNorm statistics are defined on the STORED y (saltnet.h), so they are compared - at the fp32
 bound in both dtypes - with the float64 statistics of the y the kernel wrote; y itself is compared with the reference."""
 import ctypes
@@ -15,25 +15,17 @@ import closed_form as CF
 import stacking_op_reference as SR
 from helpers import golden, T, assert_close
 from op_reference import round_to
-from test_gpu_ops_streaming import call, close, code, gen
+import net_checks as NC
+from abi_ops import _abi, call, close, code, gen, DEV, F64, TDT
 
 pytestmark = pytest.mark.gpu
-DEV = 'cuda:0'
-F64 = torch.float64
 DTYPES = ['f32', 'bf16']
-TDT = {'f32': torch.float32, 'bf16': torch.bfloat16}
 # (B, M, F, K, H, W): smaller than a tile | ragged both ways, several tiles, padded channels | exact tiles | ... ; the last one is the
 # largest supported case, the only one where fp32 stages the weights in two channel chunks (M > 48 with F = 64)
 SHAPES = [(1, 1, 16, 1, 8, 8), (2, 5, 32, 2, 19, 37), (2, 16, 16, 2, 16, 64), (1, 20, 32, 2, 33, 17), (2, 32, 32, 2, 32, 32),
           (1, 40, 64, 4, 9, 70), (1, 64, 32, 2, 16, 16), (1, 64, 64, 2, 9, 20)]
 GUARD = 64                       # sentinel elements on both sides of every output window (a multiple of 16 bytes in both dtypes)
 SENT = 1024.0                    # exact in bf16
-
-
-def _abi():
-    import salt_amd  # noqa: F401
-    from salt_amd import _abi
-    return _abi
 
 
 class Window:
@@ -369,12 +361,7 @@ def test_bf16_training_step_runs_and_tracks_fp32(name, with_depth, deterministic
 
 # ------------------------------------------------------------------------------------------------ trainer / inference surface
 def _model(with_depth, dtype='f32', lr=1e-3, cfg=None, epochs=1, **extra):
-    from salt_amd import models
-    cls = models.SegmentationModelWithDepth if with_depth else models.SegmentationModel
-    arch = {'model_params': dict({'architecture': 'StackingFCNWithDepth' if with_depth else 'StackingFCN', 'out_channels': 2,
-                                  'activation': 'sigmoid', 'loss': 'lovasz', 'compute_dtype': dtype, 'input_model_nr': 5}, **extra),
-            'optimizer_params': {'lr': lr}, 'regularizer_params': {'regularize': True, 'weight_decay_conv2d': 1e-4}}
-    return cls(arch, {'epochs': epochs}, cfg or {})
+    return NC.family_model('StackingFCNWithDepth' if with_depth else 'StackingFCN', dtype, lr, epochs, cfg, **dict({'input_model_nr': 5}, **extra))
 
 
 def _stacks(n, seed, size=32):
@@ -425,7 +412,8 @@ def test_fit_transform_persist_load(with_depth, tmp_path):
 
 @pytest.mark.parametrize('with_depth', [False, True], ids=['StackingFCN', 'StackingFCNWithDepth'])
 def test_step_graph_replay_equals_eager_steps(with_depth, deterministic_sums):
-    """tests/test_gpu_fused_step.py::test_step_graph_replay_equals_eager_steps on the stacking networks: the same comparison, bit for bit."""
+    """tests/test_gpu_fused_step.py::test_step_graph_replay_equals_eager_steps on the stacking networks: the same comparison (with the
+    state dicts and the step count, which tests/net_checks.py::step_graph_equals_eager does not compare), bit for bit."""
     results = {}
     for mode in ('eager', 'graph'):
         torch.manual_seed(11)

@@ -6,22 +6,10 @@ import numpy as np
 import pytest
 import torch
 
+from gpu_harness import _data
+
 pytestmark = pytest.mark.gpu
 DEV = 'cuda:0'
-
-
-def _data(n, seed):
-    g = torch.Generator().manual_seed(seed)
-    yy, xx = torch.meshgrid(torch.arange(128), torch.arange(128), indexing='ij')
-    X = torch.randn(n, 1, 128, 128, generator=g) * 0.3
-    M = torch.zeros(n, 1, 128, 128)
-    for i in range(n):
-        if i % 3 == 0:
-            continue
-        cy, cx, r = [int(v) for v in torch.randint(30, 98, (3,), generator=g)]
-        M[i, 0] = (((yy - cy) ** 2 + (xx - cx) ** 2) < (r // 2) ** 2).float()
-    X = X + 0.9 * M
-    return X, torch.cat([1 - M, M], 1)
 
 
 def test_fit_with_reference_callback_stack(tmp_path):

@@ -510,3 +510,26 @@ def test_builder_state_is_declared_not_probed_with_getattr_defaults():
             assigned[cls.name] = {t.attr for t in targets if isinstance(t, ast.Attribute) and isinstance(t.value, ast.Name) and t.value.id == 'self'}
     for cls, ns in declared.items():
         assert not set(ns) - assigned[cls], '%s.__init__ does not declare %s' % (cls, sorted(set(ns) - assigned[cls]))
+
+
+def test_no_test_module_is_imported_and_the_abi_handle_is_defined_once():
+    """Helpers shared between test modules live in plain modules (abi_ops, net_checks, gpu_harness, helpers, conv_abi, small_abi, ...): no
+    module under tests/ imports a test_* module, and the lazy C-ABI handle `_abi` is defined in abi_ops.py and small_abi.py only."""
+    tests = os.path.join(ROOT, 'tests')
+    files = sorted(f for f in os.listdir(tests) if f.endswith('.py'))
+    assert len(files) > 60
+    defines_abi = []
+    for f in files:
+        with open(os.path.join(tests, f)) as fh:
+            tree = ast.parse(fh.read(), f)
+        for node in ast.walk(tree):
+            names = []
+            if isinstance(node, ast.Import):
+                names = [a.name for a in node.names]
+            elif isinstance(node, ast.ImportFrom):
+                names = [node.module or '']
+            for n in names:
+                assert not n.split('.')[-1].startswith('test_') and not n.startswith('test_'), '%s:%d imports %s' % (f, node.lineno, n)
+            if isinstance(node, ast.FunctionDef) and node.name == '_abi':
+                defines_abi.append(f)
+    assert sorted(defines_abi) == ['abi_ops.py', 'small_abi.py'], defines_abi

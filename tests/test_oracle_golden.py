@@ -5,37 +5,11 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from helpers import golden, T, state_from_fixture, assert_close
+from helpers import golden, T, state_from_fixture, assert_close, ORACLE_BLOCKS as BLOCKS, oracle_run as _run
 import closed_form as CF
 from oracle import blocks as OB, nets as ON, losses as OL, metrics as OM, specs as OS
 
 TOL = 2e-5
-
-
-def _run(fn, sd, x, extras=()):
-    x = x.clone().requires_grad_(True)
-    extras = [e.clone().requires_grad_(True) for e in extras]
-    leaves = {k: v for k, v in sd.items() if v.dtype.is_floating_point and not k.endswith(('running_mean', 'running_var'))}
-    for v in leaves.values():
-        v.requires_grad_(True)
-    y = fn(x, *extras)
-    return x, extras, leaves, y
-
-
-BLOCKS = {
-    'F1_conv2dbnrelu_k33': lambda sd, tr: (lambda x: OB.conv2d_bn_relu(sd, '', x, tr)),
-    'F1_conv2dbnrelu_k31': lambda sd, tr: (lambda x: OB.conv2d_bn_relu(sd, '', x, tr)),
-    'F1_conv2dbnrelu_k13': lambda sd, tr: (lambda x: OB.conv2d_bn_relu(sd, '', x, tr)),
-    'F2_convbnrelu': lambda sd, tr: (lambda x: OB.conv_bn_relu(sd, '', x, tr)),
-    'F3_decoderv1': lambda sd, tr: (lambda x: OB.decoder_block_v1(sd, '', x, tr)),
-    'F3_decoderv2_deconv': lambda sd, tr: (lambda x: OB.decoder_block_v2(sd, '', x, tr, True)),
-    'F3_decoderv2_upsample': lambda sd, tr: (lambda x: OB.decoder_block_v2(sd, '', x, tr, False)),
-    'F3_deconvconv2dbnrelu': lambda sd, tr: (lambda x: OB.deconv_conv2d_bn_relu(sd, '', x, tr)),
-    'F4_decoderblock_skip': lambda sd, tr: (lambda x, e: OB.decoder_block(sd, '', x, e, tr)),
-    'F4_decoderblock_noskip': lambda sd, tr: (lambda x: OB.decoder_block(sd, '', x, None, tr)),
-    'F4_channel_se': lambda sd, tr: (lambda x: OB.channel_se(sd, '', x)),
-    'F4_spatial_se': lambda sd, tr: (lambda x: OB.spatial_se(sd, '', x)),
-}
 
 
 @pytest.mark.parametrize('name', sorted(BLOCKS))

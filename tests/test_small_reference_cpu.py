@@ -1,6 +1,6 @@
 """small_abi.py's float64 references and bounds, on the CPU: every reference is pinned against torch in double (F.conv2d, autograd,
 F.pixel_unshuffle), the stem's three index maps against each other exactly on integer values (the space-to-depth identity and the
-adjoint property), the tables of test_gpu_small_abi.py against the library's host-only queries (which kernel every case takes, part
+adjoint property), the case tables of small_abi.py (run on the GPU by test_gpu_small_abi.py) against the library's host-only queries (which kernel every case takes, part
 counts, taps per thread), and an fp32 stand-in for a kernel passes the bounds on every case while six result-side mutations do not."""
 import pytest
 import torch
@@ -8,7 +8,6 @@ import torch.nn.functional as F
 
 import conv_abi as CA
 import small_abi as SA
-import test_gpu_small_abi as T
 
 F64 = torch.float64
 
@@ -22,8 +21,8 @@ def _nhwc(t):
     return t.permute(0, 2, 3, 1).contiguous()
 
 
-FIRST_FORMS = sorted({(c['K'], c['s'], c['p'], c['Cin'], c['H'], c['W']) for c in T.FIRST_CASES})
-WGRAD_FORMS = sorted({(c['K'], c['s'], c['p'], c['Cin'], c['H'], c['W']) for c in T.WGRAD_CASES if c['kid'] >= 0 and c['B'] == 1})
+FIRST_FORMS = sorted({(c['K'], c['s'], c['p'], c['Cin'], c['H'], c['W']) for c in SA.FIRST_CASES})
+WGRAD_FORMS = sorted({(c['K'], c['s'], c['p'], c['Cin'], c['H'], c['W']) for c in SA.WGRAD_CASES if c['kid'] >= 0 and c['B'] == 1})
 
 
 # ---------------------------------------------------------------- references against torch
@@ -39,7 +38,7 @@ def test_conv_first_sum_is_conv2d(K, s, p, Cin, H, W):
 
 def test_conv_first_epilogue_order_and_statistics():
     x, w = SA.mk(2, 3, 34, 38, 1), SA.master_weight(24, 3, 7, 7, 3, 49, 2)
-    b, sc, sh = T._vec(24, 3), T._vec(24, 4, 'scale'), T._vec(24, 5)
+    b, sc, sh = SA._vec(24, 3), SA._vec(24, 4, 'scale'), SA._vec(24, 5)
     v = _nhwc(F.conv2d(x.double(), w.double(), stride=2, padding=3))
     r = SA.conv_first_ref(x, w, 2, 3, 'bf16', b, sc, sh, True)
     _close(r['exact'], ((v + b) * sc + sh).clamp_min(0))
@@ -74,7 +73,7 @@ def test_head_references_are_autograd(Cout):
     B, H, W, C = 2, 5, 7, 12
     x = _nhwc(SA.mk(B, C, H, W, 6)).double()
     w = SA.master_weight(Cout, C, 1, 1, C, 1, 7).reshape(Cout, C).double()
-    bias, dy, old = T._vec(Cout, 8), SA.mk(B, Cout, H, W, 9).double(), _nhwc(SA.mk(B, C, H, W, 10)).double()
+    bias, dy, old = SA._vec(Cout, 8), SA.mk(B, Cout, H, W, 9).double(), _nhwc(SA.mk(B, C, H, W, 10)).double()
     xr, wr, br = x.clone().requires_grad_(True), w.clone().requires_grad_(True), bias.clone().requires_grad_(True)
     y = F.conv2d(xr.permute(0, 3, 1, 2), wr.reshape(Cout, C, 1, 1), br)
     _close(SA.head_ref(x, w, bias)['exact'], _nhwc(y.detach()))
@@ -104,7 +103,7 @@ def test_head_parts_arithmetic():
 # ---------------------------------------------------------------- the stem's index maps
 @pytest.mark.parametrize('Cin', [1, 2, 3, 4])
 def test_s2d_is_pixel_unshuffle_with_the_headers_channel_order(Cin):
-    x = T._arbitrary((2, Cin, 6, 10), 11)
+    x = SA._arbitrary((2, Cin, 6, 10), 11)
     z = SA.s2d_ref(x)
     pu = F.pixel_unshuffle(x, 2)                                             # channel c 4 + ph 2 + pw
     for c in range(Cin):
@@ -150,16 +149,16 @@ def _unique(cases):
 
 
 def test_first_cases_take_the_store_path_they_name():
-    _unique(T.FIRST_CASES)
-    for c in T.FIRST_CASES:
-        assert T.first_vec(c) == c['vec'], c['name']
-        y = SA.view(T.FAKE, c['B'], 1, 1, c['Cout'], c['yv'][1])
-        S = SA.first_args(c['dtype'], T.FAKE, (c['B'], c['Cin'], c['H'], c['W']), T.FAKE, c['K'], c['s'], c['p'], y)
+    _unique(SA.FIRST_CASES)
+    for c in SA.FIRST_CASES:
+        assert SA.first_vec(c) == c['vec'], c['name']
+        y = SA.view(SA.FAKE, c['B'], 1, 1, c['Cout'], c['yv'][1])
+        S = SA.first_args(c['dtype'], SA.FAKE, (c['B'], c['Cin'], c['H'], c['W']), SA.FAKE, c['K'], c['s'], c['p'], y)
         OH, OW = SA.first_geom(c['H'], c['W'], c['K'], c['s'], c['p'])
         assert 16 < OH <= 32 and 16 < OW <= 32, 'ragged 2 x 2 tiles'
         assert SA.query('salt_conv_first_stats_parts', S) == 4 * c['B']
     # the predicate's three terms fail one at a time
-    by = {c['name']: c for c in T.FIRST_CASES}
+    by = {c['name']: c for c in SA.FIRST_CASES}
     for dt, es in (('f32', 4), ('bf16', 2)):
         c0, cs = by[dt + '-y-slice-cs-odd']['yv']
         assert cs % SA.VE[dt] != 0 and c0 == 0
@@ -169,64 +168,64 @@ def test_first_cases_take_the_store_path_they_name():
         assert cs % SA.VE[dt] == 0 and (c0 * es) % 16 == 0 and c0 > 0
 
 
-@pytest.mark.parametrize('dtype', T.DTYPES)
+@pytest.mark.parametrize('dtype', SA.DTYPES)
 def test_wgrad_cases_land_on_the_instantiation_they_name(dtype):
-    _unique(T.WGRAD_CASES)
+    _unique(SA.WGRAD_CASES)
     seen = set()
-    for c in T.WGRAD_CASES:
-        S = T.wg_plan(c, dtype)
+    for c in SA.WGRAD_CASES:
+        S = SA.wg_plan(c, dtype)
         kid = SA.query('salt_conv_first_wgrad_kernel_id', S)
         assert kid == c['kid'], '%s: id %d (%s)' % (c['name'], kid, SA.last_error() if kid < 0 else 'ok')
         if kid < 0:
             continue
         seen.add(kid)
-        nparts, n = T.wg_nparts(c), c['Cout'] * c['Cin'] * c['K'] * c['K']
+        nparts, n = SA.wg_nparts(c), c['Cout'] * c['Cin'] * c['K'] * c['K']
         assert SA.query('salt_conv_first_wgrad_parts', S) == nparts
         assert bool(kid & SA.WIDE) == (nparts >= 64 and n <= 4096), c['name']
         kkc = c['Cin'] * c['K'] * c['K']
-        if kid & 255 == T.MFMA:
+        if kid & 255 == SA.MFMA:
             assert c['Cout'] % 16 == 0 and kkc <= 16
         else:
             groups = 256 // c['Cout']
             assert SA.cdiv(kkc, groups) == c['per'] <= (kid & 255), c['name']
             assert c['per'] > {1: 0, 4: 1, 12: 4, 40: 12}[kid & 255], 'the smallest instantiation that holds `per`'
     assert seen == {0, 1, 4, 12, 40, 256, 257}
-    by = {c['name']: c for c in T.WGRAD_CASES}
-    assert T.wg_nparts(by['nparts63-narrow']) == 63 and T.wg_nparts(by['nparts64-wide']) == 64 and T.wg_nparts(by['nparts320-wide']) == 320
+    by = {c['name']: c for c in SA.WGRAD_CASES}
+    assert SA.wg_nparts(by['nparts63-narrow']) == 63 and SA.wg_nparts(by['nparts64-wide']) == 64 and SA.wg_nparts(by['nparts320-wide']) == 320
     assert 256 - 144 == 112 and 256 // 144 == 1 and 256 // 128 == 2 and 256 % 128 == 0
 
 
 def test_head_cases_land_on_the_kernel_they_name():
-    _unique(T.HEAD_CASES)
+    _unique(SA.HEAD_CASES)
     seen = set()
-    for c in T.HEAD_CASES + [T.HEAD_GRID_CAP]:
+    for c in SA.HEAD_CASES + [SA.HEAD_GRID_CAP]:
         for out in ('nchw', 'view'):
-            kid = SA.query('salt_head1x1_kernel_id', T.head_plan(c, out))
+            kid = SA.query('salt_head1x1_kernel_id', SA.head_plan(c, out))
             assert kid == c['kid'], '%s: kernel %d' % (c['name'], kid)
         cpv = c['C'] // SA.VE[c['dtype']] if c['C'] % SA.VE[c['dtype']] == 0 else None
         seen.add((c['dtype'], c['kid'], cpv))
-    for dt in T.DTYPES:
-        for kid in (T.HEAD_VEC, T.HEAD_VEC_CO2):
+    for dt in SA.DTYPES:
+        for kid in (SA.HEAD_VEC, SA.HEAD_VEC_CO2):
             assert {(dt, kid, 1), (dt, kid, 8), (dt, kid, 64)} <= seen
-        assert (dt, T.HEAD_SCALAR, 3) in seen and (dt, T.HEAD_SCALAR, 128) in seen and (dt, T.HEAD_SCALAR, None) in seen
-    c = T.HEAD_GRID_CAP
+        assert (dt, SA.HEAD_SCALAR, 3) in seen and (dt, SA.HEAD_SCALAR, 128) in seen and (dt, SA.HEAD_SCALAR, None) in seen
+    c = SA.HEAD_GRID_CAP
     units = c['B'] * c['H'] * c['W'] * (c['C'] // 8)
     assert 4096 < SA.cdiv(units, 256) < 2 * 4096 and c['B'] * c['H'] * c['W'] * c['C'] * 2 < 20 << 20
-    assert SA.query('salt_head1x1_kernel_id', SA.head_args('f32', SA.view(T.FAKE, 1, 2, 2, 8, 8), T.FAKE, None, 5, y_nchw=T.FAKE)) == -1
+    assert SA.query('salt_head1x1_kernel_id', SA.head_args('f32', SA.view(SA.FAKE, 1, 2, 2, 8, 8), SA.FAKE, None, 5, y_nchw=SA.FAKE)) == -1
 
 
 def test_head_bwd_cases_land_on_the_kernel_they_name():
-    _unique(T.HEAD_BWD_CASES)
+    _unique(SA.HEAD_BWD_CASES)
     parts = set()
-    for c in T.HEAD_BWD_CASES:
-        S = T.hb_plan(c, 0, True)
+    for c in SA.HEAD_BWD_CASES:
+        S = SA.hb_plan(c, 0, True)
         npix = c['B'] * c['H'] * c['W']
         assert S.nparts == SA.head_parts(npix), c['name']
         parts.add(S.nparts)
         kid = SA.query('salt_head1x1_bwd_kernel_id', S)
         assert kid == c['kid'], '%s: kernel %d (%s)' % (c['name'], kid, SA.last_error() if kid < 0 else 'ok')
-        assert SA.query('salt_head1x1_bwd_kernel_id', T.hb_plan(c, 1, False, nparts=S.nparts + 1)) == -1
-        if kid == T.HEAD_VEC:
+        assert SA.query('salt_head1x1_bwd_kernel_id', SA.hb_plan(c, 1, False, nparts=S.nparts + 1)) == -1
+        if kid == SA.HEAD_VEC:
             assert c['C'] % SA.VE[c['dtype']] == 0 and c['C'] // SA.VE[c['dtype']] <= 256
     assert {1, 3, 11, 1009} <= parts
 
@@ -236,11 +235,11 @@ def _st(dtype):
     return (lambda t: t.bfloat16().float()) if dtype == 'bf16' else (lambda t: t)
 
 
-@pytest.mark.parametrize('c', T._ids(T.FIRST_CASES))
+@pytest.mark.parametrize('c', SA._ids(SA.FIRST_CASES))
 def test_conv_first_bound_lets_fp32_pass(c):
     """torch's fp32 convolution (another order than the reference's), fp32 epilogue, one storage rounding; the statistics from the
     unrounded fp32 values with torch's fp32 sums."""
-    o = T.first_build(c)
+    o = SA.first_build(c)
     y = F.conv2d(o['x'], o['w'], stride=c['s'], padding=c['p']).permute(0, 2, 3, 1)
     if c['bias']:
         y = y + o['bias'].float()
@@ -263,26 +262,26 @@ def test_conv_first_bound_lets_fp32_pass(c):
                     k += 1
 
 
-@pytest.mark.parametrize('dtype', T.DTYPES)
-@pytest.mark.parametrize('c', T._ids([c for c in T.WGRAD_CASES if c['kid'] >= 0]))
+@pytest.mark.parametrize('dtype', SA.DTYPES)
+@pytest.mark.parametrize('c', SA._ids([c for c in SA.WGRAD_CASES if c['kid'] >= 0]))
 def test_conv_first_wgrad_bound_lets_fp32_pass(c, dtype):
-    o = T.wg_build(c, 1)
+    o = SA.wg_build(c, 1)
     w = torch.zeros(c['Cout'], c['Cin'], c['K'], c['K'], requires_grad=True)
     F.conv2d(o['x'], w, stride=c['s'], padding=c['p']).backward(o['dy'].permute(0, 3, 1, 2))
     assert SA.worst((w.grad + o['old'].float()).double(), o['ref']) <= 1.0
 
 
-@pytest.mark.parametrize('c', T._ids(T.HEAD_CASES))
+@pytest.mark.parametrize('c', SA._ids(SA.HEAD_CASES))
 def test_head_bound_lets_fp32_pass(c):
-    o = T.head_build(c)
+    o = SA.head_build(c)
     y = o['x'].matmul(o['w'].t()) + o['bias'].float()
     assert SA.ratio(y, SA.head_ref(o['x'].double(), o['w'].double(), o['bias'])) <= 1.0
     assert SA.ratio(_st(c['dtype'])(y), SA.head_ref(o['x'].double(), o['w'].double(), o['bias'], c['dtype'])) <= 1.0
 
 
-@pytest.mark.parametrize('c', T._ids([c for c in T.HEAD_BWD_CASES if c['H'] < 100]))
+@pytest.mark.parametrize('c', SA._ids([c for c in SA.HEAD_BWD_CASES if c['H'] < 100]))
 def test_head_bwd_bound_lets_fp32_pass(c):
-    o = T.hb_build(c, 1)
+    o = SA.hb_build(c, 1)
     st = _st(c['dtype'])
     g = o['dy'].permute(0, 2, 3, 1)
     dx = st(st(g.matmul(o['w'])) + o['old'])                                 # the new term rounded before the old one is added: allowed
@@ -293,11 +292,11 @@ def test_head_bwd_bound_lets_fp32_pass(c):
 
 
 # ---------------------------------------------------------------- ... and reject a wrong result
-@pytest.mark.parametrize('dtype', T.DTYPES)
+@pytest.mark.parametrize('dtype', SA.DTYPES)
 def test_bounds_reject_wrong_results(dtype):
     st = _st(dtype)
-    c = next(c for c in T.FIRST_CASES if c['name'] == dtype + '-bias-cout10')
-    o = T.first_build(c)
+    c = next(c for c in SA.FIRST_CASES if c['name'] == dtype + '-bias-cout10')
+    o = SA.first_build(c)
     ref = o['ref']
     assert SA.ratio(st(ref['exact'].float()), ref) <= 1.0
     got = ref['exact'].clone()
@@ -307,15 +306,15 @@ def test_bounds_reject_wrong_results(dtype):
     got[0, 0, 0] -= o['w'][:, 2, 6, 6].double() * float(o['x'][0, 2, 3, 3])  # the last tap at the corner pixel
     assert SA.ratio(st(got.float()), ref) > 1.0
     # weight gradient: pixel 255 of the first tile left out
-    c = next(c for c in T.WGRAD_CASES if c['name'] == 'per4-cout24-cin3-k3')
-    o = T.wg_build(c, 0)
+    c = next(c for c in SA.WGRAD_CASES if c['name'] == 'per4-cout24-cin3-k3')
+    o = SA.wg_build(c, 0)
     dy = o['dy'].clone()
     dy[0, 15, 15] = 0
     bad = SA.conv_first_wgrad_ref(o['x'], dy, c['K'], c['s'], c['p'])['exact']
     assert SA.worst(bad.float().double(), o['ref']) > 1.0 and SA.worst(o['ref']['exact'].float().double(), o['ref']) <= 1.0
     # head backward: every fourth pixel missing from gb; one output's term missing from dx at one pixel
-    c = next(c for c in T.HEAD_BWD_CASES if c['name'] == dtype + '-vec-cpv8-ragged-part')
-    o = T.hb_build(c, 0)
+    c = next(c for c in SA.HEAD_BWD_CASES if c['name'] == dtype + '-vec-cpv8-ragged-part')
+    o = SA.hb_build(c, 0)
     g = o['dy'].double().permute(0, 2, 3, 1).reshape(-1, c['Cout'])
     assert SA.worst((g.sum(0) - g[3::4].sum(0)).float().double(), o['ref']['gb']) > 1.0
     dx = o['ref']['dx']['exact'].clone()
