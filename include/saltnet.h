@@ -1475,6 +1475,117 @@ typedef struct {
 } salt_dense_bn_prep_args;
 int salt_dense_bn_prep(const salt_dense_bn_prep_args*, void* stream);
 
+/* ------------------------------------------------------------------ pyramid pooling at low resolution (csrc/psp.hip): the middle of
+ * the reference's PSPNet (architectures/pspnet.py: PSPModule, PSPUpsample).  PSPModule pools its input x [B,h,w,C] to s x s bins for every
+ * pyramid size s, runs a 1x1 convolution per size, resizes the results back to h x w, concatenates them with x and runs the 1x1
+ * `bottleneck` + ReLU over the 5 C channels.  A 1x1 convolution commutes with the bilinear resize, so with W_b = bottleneck.weight in
+ * input-channel blocks (the stages in order, then x):
+ *     q_k = W_b[:, k C : (k + 1) C] (W_k pool_k(x))        at s_k x s_k
+ *     f   = W_b[:, n C : (n + 1) C] x                      at h x w
+ *     y   = relu(f + bias + sum_k resize_{s_k -> (h, w)}(q_k))
+ * The contractions are salt_conv launches on weight slices; the operators here are what is left: the pooling, the merge and their
+ * adjoints, and PSPUpsample's BatchNorm apply + PReLU.
+ *
+ * Shapes of the four psp operators: h, w <= 32; C a multiple of 8 (both dtypes); 1..4 pyramid sizes, each in 1..6; every view 16-byte
+ * aligned with cs a multiple of 4 (f32) / 8 (bf16), channel slices of wider buffers included.  Anything else is SALT_E_UNSUPPORTED /
+ * SALT_E_BADARG with a salt_last_error text and nothing is launched.  All sums are fp32 in a fixed order, no atomics: a rerun gives
+ * the same bits.  Stage k of a pooled tensor is a view [B, s_k, s_k, C] of its own.
+ *
+ * Bins follow torch's AdaptiveAvgPool2d: rows [floor(i h / s), ceil((i + 1) h / s)), columns likewise; bins overlap where s does not
+ * divide h and repeat pixels where s > h.  p_k[b,i,j,c] = (sum of the window's pixels in row-major order) / area. */
+#define SALT_PSP_MAX_STAGES 4
+typedef struct {
+    int dtype;
+    salt_view x;              /* [B,h,w,C] */
+    int nsizes;
+    int sizes[SALT_PSP_MAX_STAGES];
+    salt_view p[SALT_PSP_MAX_STAGES];   /* out: stage k [B,s_k,s_k,C] */
+} salt_psp_pool_args;
+int salt_psp_pool(const salt_psp_pool_args*, void* stream);
+
+/* dx[b,y,x,c] (+)= sum_k sum_{bins of stage k that contain (y, x)} dp_k[bin] / area(bin): a gather per pixel - stages, bin rows, bin
+ * columns ascending. */
+typedef struct {
+    int dtype;
+    int nsizes;
+    int sizes[SALT_PSP_MAX_STAGES];
+    salt_view dp[SALT_PSP_MAX_STAGES];  /* stage k [B,s_k,s_k,C] */
+    salt_view dx;             /* out [B,h,w,C] */
+    int accumulate;           /* dx += */
+} salt_psp_pool_bwd_args;
+int salt_psp_pool_bwd(const salt_psp_pool_bwd_args*, void* stream);
+
+/* y = relu(f + bias + sum_k resize(q_k)).  The resize is torch's size-based bilinear interpolation (F.upsample(size=(h, w),
+ * mode='bilinear')), source index of destination d along an axis of n destinations and s sources, PINNED in fp32:
+ *     align_corners 0:  src = max(0, (s / n) (d + 0.5) - 0.5)          align_corners 1:  src = ((s - 1) / (n - 1)) d   (0 for n = 1)
+ *     i0 = min(int(src), s - 1)    i1 = min(i0 + 1, s - 1)    w1 = src - i0    w0 = 1 - w1
+ * one division, one product and one subtraction, each rounded once.  A tap's weight is the rounded product of its row and column
+ * weight. */
+typedef struct {
+    int dtype;
+    salt_view f;              /* [B,h,w,C] */
+    const float* bias;        /* [C] or NULL */
+    int nsizes;
+    int sizes[SALT_PSP_MAX_STAGES];
+    salt_view q[SALT_PSP_MAX_STAGES];   /* stage k [B,s_k,s_k,C] */
+    int align_corners;
+    salt_view y;              /* out [B,h,w,C] */
+} salt_psp_merge_args;
+int salt_psp_merge(const salt_psp_merge_args*, void* stream);
+
+/* From dy and the stored y:  g = dy [y > 0] -> df (df may be dy itself);  dq_k[bin] = sum_pixels weight_k(pixel, bin) g[pixel], a gather
+ * per bin with the pixels in row-major order (weight_k: the dense resize matrix, a source that both taps of a clamped destination hit
+ * gets the rounded sum w0 + w1);  dbias[c] (+)= sum_b partials[b][c], partials[b][c] = sum_pixels g[b,pixel,c], images ascending. */
+typedef struct {
+    int dtype;
+    salt_view dy;             /* [B,h,w,C] */
+    salt_view y;              /* [B,h,w,C] forward output */
+    int nsizes;
+    int sizes[SALT_PSP_MAX_STAGES];
+    int align_corners;
+    salt_view df;             /* out [B,h,w,C] */
+    salt_view dq[SALT_PSP_MAX_STAGES];  /* out: stage k [B,s_k,s_k,C] */
+    float* partials;          /* workspace [nparts][C] fp32 */
+    int nparts;               /* as returned by salt_psp_merge_bwd_parts */
+    float* dbias;             /* out [C], or NULL */
+    int accumulate_dbias;     /* dbias += */
+} salt_psp_merge_bwd_args;
+int salt_psp_merge_bwd(const salt_psp_merge_bwd_args*, void* stream);
+int salt_psp_merge_bwd_parts(const salt_psp_merge_bwd_args*);   /* dy's shape is read */
+
+/* PSPUpsample's BatchNorm2d apply + nn.PReLU() (one learnable slope, read from device memory) in one pass over the raw convolution
+ * output; the normalised value is never stored.  THE PRE-ACTIVATION IS PINNED for both operators:
+ *     u = fmaf(y, scale[c], shift[c])     (scale == shift == NULL: u = y - the convolution's epilogue already applied a folded BatchNorm)
+ *     a = u > 0 ? u : alpha u
+ * Any B, H, W; C a multiple of 8; 16-byte aligned views as above.  a may be y itself. */
+typedef struct {
+    int dtype;
+    salt_view y;              /* [B,H,W,C] */
+    const float* scale;       /* [C] or NULL (then shift is NULL too) */
+    const float* shift;
+    const float* alpha;       /* [1] */
+    salt_view a;              /* out [B,H,W,C] */
+} salt_bn_prelu_args;
+int salt_bn_prelu(const salt_bn_prelu_args*, void* stream);
+
+/* du = da (u > 0 ? 1 : alpha) (du may be da itself; salt_bn_bwd with relu = 0 then runs on du);  dalpha (+)= sum da min(u, 0): every
+ * workgroup reduces its share in a fixed order into partials[workgroup], a second launch adds the partials in a fixed order. */
+typedef struct {
+    int dtype;
+    salt_view da;             /* [B,H,W,C] */
+    salt_view y;              /* [B,H,W,C] raw convolution output */
+    const float* scale;
+    const float* shift;
+    const float* alpha;
+    salt_view du;             /* out [B,H,W,C] */
+    float* partials;          /* workspace [nparts] fp32 */
+    int nparts;               /* as returned by salt_bn_prelu_bwd_parts */
+    float* dalpha;            /* out [1] */
+    int accumulate_dalpha;    /* dalpha += */
+} salt_bn_prelu_bwd_args;
+int salt_bn_prelu_bwd(const salt_bn_prelu_bwd_args*, void* stream);
+int salt_bn_prelu_bwd_parts(const salt_bn_prelu_bwd_args*);   /* y's shape and dtype are read */
+
 #ifdef __cplusplus
 }
 #endif

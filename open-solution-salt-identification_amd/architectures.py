@@ -22,6 +22,7 @@ Reference classes mirrored (paths relative to the reference's common_blocks/):
   torchvision / pretrainedmodels densenet.py (un-vendored dependency, layout RESTATED from the public source, not executed): DenseNet /
   _DenseBlock / _DenseLayer / _Transition as densenet121 / 169 / 201 build them
   architectures/encoders.py:121-164 DenseNetEncoders;  architectures/unet.py:238-307 UNetDenseNet
+  architectures/pspnet.py:9-28 PSPModule · :31-42 PSPUpsample · :45-105 PSPNet
 """
 import math
 
@@ -840,6 +841,98 @@ class UNetDenseNet(UNetResNet):
             if i < 3:
                 x = getattr(f, 'transition%d' % (i + 1)).emit(g, block, table, slots[i + 1].slice(0, c // 2))
         return slots
+
+
+class PSPModule(EmitOnly):
+    """architectures/pspnet.py:9-28: per pyramid size AdaptiveAvgPool2d(s) -> bias-free 1x1 convolution -> bilinear resize back to (h, w);
+    the results and the input concatenated; 1x1 ``bottleneck`` with bias; ReLU.  Executed by Graph.psp without the concatenation."""
+
+    def __init__(self, features, out_features=1024, sizes=(1, 2, 3, 6)):
+        super().__init__()
+        self.stages = nn.ModuleList([self._make_stage(features, size) for size in sizes])
+        self.bottleneck = nn.Conv2d(features * (len(sizes) + 1), out_features, kernel_size=1)
+        self.relu = nn.ReLU()
+
+    def _make_stage(self, features, size):
+        return nn.Sequential(nn.AdaptiveAvgPool2d(output_size=(size, size)), nn.Conv2d(features, features, kernel_size=1, bias=False))
+
+    def emit(self, g, x):
+        return g.psp(x, self, name='PSPModule')
+
+
+class PSPUpsample(EmitOnly):
+    """architectures/pspnet.py:31-42: bilinear x2, then Conv2d(3x3, padding 1) -> BatchNorm2d -> nn.PReLU() (one slope)."""
+
+    def __init__(self, in_channels, out_channels):
+        super().__init__()
+        self.conv = nn.Sequential(nn.Conv2d(in_channels, out_channels, 3, padding=1), nn.BatchNorm2d(out_channels), nn.PReLU())
+
+    def emit(self, g, x, out=None):
+        return g.conv_bn_prelu(g.upsample(x, 2, name='PSPUpsample.up'), self.conv[0], self.conv[1], self.conv[2], out=out, name='PSPUpsample')
+
+
+class PSPNet(HipNetwork):
+    """architectures.pspnet.PSPNet (pspnet.py:45-105): ResNet18 / 34 encoders without the stem pool, PSPModule on encoder5 (a /16 map),
+    four PSPUpsamples 1024 -> 512 -> 256 -> 128 -> 64 back to the input resolution, the hypercolumn [up1 | up2 x2 | up3 x4 | up4 x8] (960
+    channels, materialised) and UNetResNet's final block.  F.dropout2d is an identity as everywhere in this file (torch 0.3.1 defaults to
+    training=False): ``dropout_2d`` is accepted and ignored."""
+
+    def __init__(self, encoder_depth, num_classes=2, sizes=(1, 2, 3, 6), deep_features_size=1024, dropout_2d=0.2, pretrained=False,
+                 use_hypercolumn=False, pool0=False):
+        super().__init__()
+        if encoder_depth in (50, 101, 152):
+            # pspnet.py:77-78 sizes ``final`` for 15 * 2048 // 8 = 3840 channels while the four PSPUpsamples still deliver 960: the
+            # reference itself cannot run these depths
+            raise NotImplementedError('PSPNet: depth %d is not built: the reference sizes final for 3840 hypercolumn channels and its '
+                                      'up-sampling path delivers 960' % encoder_depth)
+        if encoder_depth not in (18, 34):
+            raise NotImplementedError('only 18, 34, 50, 101, 152 version of Resnet are implemented')
+        if not use_hypercolumn:
+            # pspnet.py:101-103 hands up4 (deep_features_size // 2 channels at 1/8 resolution) to a final block built for 64
+            raise SaltError('PSPNet: use_hypercolumn=False does not run in the reference either (final expects 64 channels and gets up4\'s %d)'
+                            % (deep_features_size // 2))
+        if pool0:
+            raise SaltError('PSPNet: pool0=True is not built')
+        if tuple(sizes) != (1, 2, 3, 6) or deep_features_size != 1024:
+            raise SaltError('PSPNet: sizes %s / deep_features_size %d are not built ((1, 2, 3, 6) and 1024 are: final expects 960 channels)'
+                            % (tuple(sizes), deep_features_size))
+        self.num_classes, self.dropout_2d, self.use_hypercolumn = num_classes, dropout_2d, use_hypercolumn
+        self.encoders = ResNetEncoders(encoder_depth, pretrained=pretrained, pool0=pool0)
+        b = 512
+        self.psp = PSPModule(b, deep_features_size, sizes)
+        self.up4 = PSPUpsample(deep_features_size, deep_features_size // 2)
+        self.up3 = PSPUpsample(deep_features_size // 2, deep_features_size // 4)
+        self.up2 = PSPUpsample(deep_features_size // 4, deep_features_size // 8)
+        self.up1 = PSPUpsample(deep_features_size // 8, deep_features_size // 16)
+        self.final = nn.Sequential(Conv2dBnRelu(15 * b // 8, b // 8), nn.Conv2d(b // 8, num_classes, kernel_size=1, padding=0))
+
+    def dead_parameter_names(self):
+        return ['encoders.encoder.fc.weight', 'encoders.encoder.fc.bias']
+
+    def output_shape(self, shape):
+        B, _, H, W = shape
+        if H % 16 or W % 16 or H > 512 or W > 512:
+            raise SaltError('PSPNet needs tiles whose sides are multiples of 16 up to 512 (got %dx%d): encoder5 is the /16 map and '
+                            'salt_psp_pool takes at most 32x32 pixels' % (H, W))
+        return (B, self.num_classes, H, W)
+
+    def emit(self, g, x_nchw, logits):
+        B, _, H, W = self.output_shape(tuple(x_nchw.shape))
+        enc = self.encoders.encoder
+        x = g.conv_first(x_nchw, enc.conv1, enc.bn1, relu=True, name='stem')
+        for layer in (enc.layer1, enc.layer2, enc.layer3, enc.layer4):
+            x = emit_blocks(g, layer, x)
+        u4 = self.up4.emit(g, self.psp.emit(g, x))
+        u3 = self.up3.emit(g, u4)
+        u2 = self.up2.emit(g, u3)
+        d = u2.C // 2
+        hyper = g.new_act(B, H, W, d + u2.C + u3.C + u4.C, 'hypercolumn')
+        # the reference computes up x2(up2) twice, inside up1 and for the hypercolumn: here the hypercolumn's slice IS up1's input
+        up2x = g.upsample(u2, 2, out=hyper.slice(d, u2.C))
+        g.conv_bn_prelu(up2x, self.up1.conv[0], self.up1.conv[1], self.up1.conv[2], out=hyper.slice(0, d), name='PSPUpsample')
+        g.upsample(u3, 4, out=hyper.slice(d + u2.C, u3.C))
+        g.upsample(u4, 8, out=hyper.slice(d + u2.C + u3.C, u4.C))
+        g.head(self.final[0].emit(g, hyper), self.final[1], logits)
 
 
 class DepthChannelExcitation(EmitOnly):

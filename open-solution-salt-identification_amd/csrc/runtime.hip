@@ -20,7 +20,7 @@ void salt_set_error(const char* fmt, ...) {
 
 extern "C" const char* salt_last_error(void) { return g_err; }
 
-extern "C" int salt_abi_version(void) { return 30; }
+extern "C" int salt_abi_version(void) { return 31; }
 
 extern "C" int salt_device_info(int* cu_count, int* lds_bytes, char* arch_name, int arch_name_len) {
     int dev = 0;
@@ -338,7 +338,13 @@ extern "C" int salt_abi_struct_sizes(int* out, int n) {
     (int)sizeof(salt_dense_conv_dgrad_args),
     (int)sizeof(salt_dense_conv_wgrad_args),
     (int)sizeof(salt_dense_moments_args),
-    (int)sizeof(salt_dense_bn_prep_args)};
+    (int)sizeof(salt_dense_bn_prep_args),
+    (int)sizeof(salt_psp_pool_args),
+    (int)sizeof(salt_psp_pool_bwd_args),
+    (int)sizeof(salt_psp_merge_args),
+    (int)sizeof(salt_psp_merge_bwd_args),
+    (int)sizeof(salt_bn_prelu_args),
+    (int)sizeof(salt_bn_prelu_bwd_args)};
     const int m = (int)(sizeof(sizes) / sizeof(sizes[0]));
     for (int i = 0; i < n && i < m; ++i) out[i] = sizes[i];
     return m;

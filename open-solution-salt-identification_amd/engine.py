@@ -1547,6 +1547,134 @@ class Graph:
         self.tape.append(backward)
         return out
 
+    # ------------------------------------------------------------------ PSPNet: pyramid pooling at low resolution (csrc/psp.hip)
+    def _conv1x1_slice(self, x, conv, c0, name=''):
+        """y = W[:, c0 : c0 + x.C] x for the 1x1 convolution ``conv`` (no bias: the merge adds it once) - one block of input channels of
+        a weight whose other blocks meet other tensors.  Backward: that block of conv.weight.grad and the data gradient into dL/dx."""
+        Cout, D1, KH, KW = conv.weight.shape
+        d1, one = (c0, x.C), [(0, 0)]
+        y = self.new_act(x.B, x.H, x.W, Cout, name)
+        self._conv_launch(self.fwd, x.view(), self.engine.packed(conv, one, transposed=False, d1=d1).data_ptr(), one, 1, 0, y.view(), x.H, x.W)
+        if self.train:
+            def backward():
+                if not y.grad_ready():
+                    raise SaltError('%s: dL/dy was never written (psp_merge must consume it)' % name)
+                self._wgrad(y.gview(), x.view(), one, one, 1, 0, conv.weight, KH, KW, b_slice=(c0, D1))
+                self._dgrad(conv, x, y, [(0, 0, 0, 0)], 1, False, KH, KW, d1=d1)
+            self.tape.append(backward)
+        return y
+
+    def psp(self, x, module, name='psp'):
+        """PSPModule (architectures/pspnet.py:9-28) without its 5 C-wide concatenation: a 1x1 convolution commutes with the bilinear
+        resize, so every pyramid stage meets its block of ``bottleneck.weight`` at s x s bins and the merge adds the resized results to
+        the block that x meets at h x w (saltnet.h: salt_psp_pool / salt_psp_merge).  Forward: pool, the stage convolutions, one slice
+        convolution per stage and one for x, merge.  Backward, in reverse: salt_psp_merge_bwd (dL/df, every dL/dq, the bottleneck's bias
+        gradient), the slice convolutions (their blocks of bottleneck.weight.grad; dL/dx from the x block), the stage convolutions, and
+        salt_psp_pool_bwd, which adds to dL/dx."""
+        sizes = [int(st[0].output_size[0] if isinstance(st[0].output_size, (tuple, list)) else st[0].output_size) for st in module.stages]
+        bott, n, C = module.bottleneck, len(module.stages), x.C
+        Cout = bott.weight.shape[0]
+        if tuple(bott.weight.shape) != (Cout, (n + 1) * C, 1, 1) or any(tuple(st[1].weight.shape) != (C, C, 1, 1) or st[1].bias is not None for st in module.stages):
+            raise SaltError('psp %s: bottleneck %s over %d stages of %d channels (bias-free 1x1 stage convolutions are expected)'
+                            % (name, tuple(bott.weight.shape), n, C))
+        if not 1 <= n <= 4 or any(not 1 <= s <= 6 for s in sizes) or x.H > 32 or x.W > 32 or C % 8 or Cout % 8:
+            raise SaltError('psp %s: sizes %s on a %dx%d map, %d -> %d channels (salt_psp_pool: up to 4 sizes in 1..6, at most 32x32 pixels, '
+                            'channels in multiples of 8)' % (name, sizes, x.H, x.W, C, Cout))
+        if x.on_side and self.fwd.default_stream == 0:
+            self.join()
+        ac = int(bool(getattr(getattr(self.engine, 'module', None), 'align_corners', False)))
+        # A 1 x 1 stage is stored as ONE image of B pixels, [1,1,B,C] - the same memory as [B,1,1,C]: salt_conv's tile arithmetic divides by
+        # the pixels of a tile's image through a 32-bit reciprocal that does not exist for 1, and sends every image of a batch of 1 x 1 maps
+        # to image 0.  The convolutions here are 1x1, so which pixels form an image is theirs to ignore; the psp operators get the per-image view.
+        dims = lambda s: (1, 1, x.B) if s == 1 else (x.B, s, s)
+
+        def per_image(v, s):
+            v.B, v.H, v.W = x.B, s, s
+            return v
+        ps = [self.new_act(*dims(s), C, '%s.pool%d' % (name, s)) for s in sizes]
+        self.fwd.add('psp_pool', dtype=self.dt, x=x.view(), nsizes=n, sizes=sizes, p=[per_image(p.view(), s) for p, s in zip(ps, sizes)])
+        if self.train:
+            def pool_backward():
+                acc = x.grad_state()
+                self.bwd.add('psp_pool_bwd', dtype=self.dt, nsizes=n, sizes=sizes, dp=[per_image(p.gview(), s) for p, s in zip(ps, sizes)], dx=x.gview(),
+                             accumulate=acc)
+            self.tape.append(pool_backward)
+        ts = [self.conv(p, st[1], name='%s.stage%d' % (name, s)) for p, st, s in zip(ps, module.stages, sizes)]
+        qs = [self._conv1x1_slice(t, bott, k * C, name='%s.q%d' % (name, s)) for k, (t, s) in enumerate(zip(ts, sizes))]
+        f = self._conv1x1_slice(x, bott, n * C, name=name + '.f')
+        out = self.new_act(x.B, x.H, x.W, Cout, name)
+        bias = bott.bias.data_ptr() if bott.bias is not None else None
+        self.fwd.add('psp_merge', dtype=self.dt, f=f.view(), bias=bias, nsizes=n, sizes=sizes, q=[per_image(q.view(), s) for q, s in zip(qs, sizes)],
+                     align_corners=ac, y=out.view())
+        if self.train:
+            def merge_backward():
+                for t in [f] + qs:
+                    assert t.grad_state() == 0, 'a slice convolution output has a single consumer'
+                self.bwd.add('psp_merge_bwd', dtype=self.dt, dy=out.gview(), y=out.view(), nsizes=n, sizes=sizes, align_corners=ac, df=f.gview(),
+                             dq=[per_image(q.gview(), s) for q, s in zip(qs, sizes)], partials=Scratch('psp_dbias', x.B * Cout * 4), nparts=x.B,
+                             dbias=self._gp(bott.bias) if bott.bias is not None else None, accumulate_dbias=0)
+            self.tape.append(merge_backward)
+        return out
+
+    def conv_bn_prelu(self, x, conv, bn, prelu, out=None, name=''):
+        """nn.Conv2d(3x3, padding 1, bias) -> BatchNorm2d -> nn.PReLU() with one slope (PSPUpsample.conv, architectures/pspnet.py:31-38).
+        eval: the convolution with the folded BatchNorm in its epilogue, then the plain PReLU in place (salt_bn_prelu without scale /
+        shift).  train: the raw output with per-tile statistics partials, salt_bn_finalize, and BatchNorm apply + PReLU in one pass
+        (the normalised value is never stored).  Backward: salt_bn_prelu_bwd turns dL/da into dL/du in place and reduces dL/dalpha,
+        then the usual BatchNorm backward (no ReLU), weight gradient and data gradient.  The convolution's bias is treated as Graph.conv
+        treats it in front of a train-mode BatchNorm."""
+        eng = self.engine
+        Cout, Cin, KH, KW = conv.weight.shape
+        if Cin != x.C or tuple(conv.stride) != (1, 1) or bn is None or bn.num_features != Cout or prelu.weight.numel() != 1 or Cout % 8:
+            raise SaltError('conv_bn_prelu %s: weight %s on %d channels, PReLU with %d slopes (a unit-step convolution to a multiple of 8 channels, '
+                            'a BatchNorm and ONE slope are expected)' % (name, tuple(conv.weight.shape), x.C, prelu.weight.numel()))
+        py, px = conv.padding
+        taps = conv_taps(KH, KW, py, px)
+        tk, td = [(t[0], t[1]) for t in taps], [(t[2], t[3]) for t in taps]
+        OH, OW = x.H + 2 * py - KH + 1, x.W + 2 * px - KW + 1
+        pk = eng.packed(conv, tk, transposed=False)
+        bias = conv.bias.data_ptr() if conv.bias is not None else None
+        alpha = prelu.weight.data_ptr()
+        if out is None:
+            out = self.new_act(x.B, OH, OW, Cout, name)
+        if (out.B, out.H, out.W, out.C) != (x.B, OH, OW, Cout):
+            raise SaltError('conv_bn_prelu %s: output %s does not fit %s' % (name, (out.B, out.H, out.W, out.C), (x.B, OH, OW, Cout)))
+        if x.on_side and self.fwd.default_stream == 0:
+            self.join()
+        if not self.train:
+            w = eng.bn_work(bn)
+            self._conv_launch(self.fwd, x.view(), pk.data_ptr(), td, 1, 0, out.view(), OH, OW, bias=bias, scale=w['scale'].data_ptr(),
+                              shift=w['shift'].data_ptr(), relu=0)
+            self.fwd.add('bn_prelu', dtype=self.dt, y=out.view(), scale=None, shift=None, alpha=alpha, a=out.view())
+            return out
+        y = self.new_act(x.B, OH, OW, Cout, name + '.y')
+        nparts = self._conv_parts(x.view(), td, 1, y.view(), OH, OW)
+        stats = Scratch('stats' + self._scratch_sfx, 4 * lib.salt_bn_stats_floats(nparts, Cout))
+        cnt = Scratch('stats_cnt' + self._scratch_sfx, nparts * 4)
+        self._conv_launch(self.fwd, x.view(), pk.data_ptr(), td, 1, 0, y.view(), OH, OW, bias=bias, stats=stats, stats_cnt=cnt)
+        w, fin = self._bn_fin_fields(bn)
+        self.fwd.add('bn_finalize', stats=stats, stats_cnt=cnt, nparts=nparts, **fin)
+        affine = dict(scale=w['scale'].data_ptr(), shift=w['shift'].data_ptr(), alpha=alpha)
+        self.fwd.add('bn_prelu', dtype=self.dt, y=y.view(), a=out.view(), **affine)
+
+        def backward():
+            if not out.grad_ready():
+                raise SaltError('conv_bn_prelu %s: dL/d(out) was never written' % name)
+            S = fill(STRUCTS['salt_bn_prelu_bwd_args'](), dtype=self.dt, y=y.view())
+            np_ = lib.salt_bn_prelu_bwd_parts(ctypes.byref(S))
+            if np_ < 1:
+                raise SaltError('conv_bn_prelu %s: %s' % (name, lib.salt_last_error().decode(errors='replace')))
+            self.bwd.add('bn_prelu_bwd', dtype=self.dt, da=out.gview(), y=y.view(), du=out.gview(), partials=Scratch('prelu', np_ * 4), nparts=np_,
+                         dalpha=self._gp(prelu.weight), accumulate_dalpha=0, **affine)
+            # this operator completed dL/du in place: it is the slice's last gradient writer and carries nobody's sums, so the
+            # BatchNorm backward below keeps its own reduction pass (a data-gradient launch in front of it summed dL/da, not dL/du)
+            out.buf.grad_writers.append(GradWriter(out.c0, out.C))
+            self._bn_train_bwd(y, bn, False, None, out, w)
+            self._wgrad(y.gview(), x.view(), td, tk, 1, 0, conv.weight, KH, KW)
+            self._dgrad(conv, x, y, taps, 1, False, KH, KW)
+        self.tape.append(backward)
+        return out
+
     # ------------------------------------------------------------------ logit head: 1x1 conv to <= 4 channels, fp32 NCHW out
     def head(self, x, conv, logits_nchw):
         Cout = conv.weight.shape[0]

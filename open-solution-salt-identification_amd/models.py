@@ -42,6 +42,10 @@ ARCHITECTURES = {
     'UNetDenseNet': {'model': A.UNetDenseNet,
                      'model_config': {'encoder_depth': 121, 'use_hypercolumn': True, 'dropout_2d': 0.0, 'pretrained': False, 'pool0': False},
                      'init_weights': False},
+    # models.py:41-45 with `pretrained` off: pyramid pooling on the /16 map (csrc/psp.hip); dropout_2d is the class default and an identity
+    'PSPNet': {'model': A.PSPNet,
+               'model_config': {'encoder_depth': 34, 'pretrained': False, 'use_hypercolumn': True, 'pool0': False},
+               'init_weights': False},
     # unet_models.py zoo (named by BASELINE.json's north_star; not wired into the reference's registry)
     'TernausUNetResNet': {'model': A.TernausUNetResNet,
                           'model_config': {'encoder_depth': 34, 'num_filters': 32, 'dropout_2d': 0.0, 'pretrained': False, 'is_deconv': True},
