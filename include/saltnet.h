@@ -1475,6 +1475,77 @@ typedef struct {
 } salt_dense_bn_prep_args;
 int salt_dense_bn_prep(const salt_dense_bn_prep_args*, void* stream);
 
+/* ------------------------------------------------------------------ paired line convolution (csrc/gcn.hip): the entry of the reference's
+ * GlobalConvolutionalNetwork (architectures/base.py:152-178).  conv1[0] (K x 1) and conv2[0] (1 x K) read the same encoder map x, the only
+ * wide tensor of the block; both pad one-sided by replication (Conv2dBnRelu: K - 1 rows on top, K - 1 columns on the right):
+ *     yv[b,i,j,n] = epi_v( sum_k sum_c wv[n][c][k] x[b, max(i - (K-1) + k, 0), j, c] )
+ *     yh[b,i,j,n] = epi_h( sum_k sum_c wh[n][c][k] x[b, i, min(j + k, W - 1), c] )
+ * ONE launch stages an L-shaped region of x per 8 x 16 pixel tile (rows i0 - (K-1) .. i0 + 7 of the tile's columns, then the K - 1
+ * columns to its right for the tile's rows) and contracts it for both branches.  The clamp is in the loader: no padded copy.
+ *
+ * Shapes: Cin a multiple of 8 up to 2048; Cout 1 .. 32, the same for both branches; K 2 .. 9 (even K is legal: the pad is one-sided);
+ * any B, H, W >= 1, H or W below K - 1 included.  x, yv, yh are 16-byte aligned NHWC views with cs >= C a multiple of 4 (f32) / 8 (bf16),
+ * channel slices of wider buffers included.  Anything else is SALT_E_UNSUPPORTED with a salt_last_error text, nothing is launched and
+ * salt_gcn_pair_stats_parts returns < 0 (it reads the struct on the host only).
+ * Weights: the fp32 MASTER weights, conv.weight of shape [Cout,Cin,K,1] / [Cout,Cin,1,K] = [Cout][Cin][K] in memory - no packed copy,
+ * nothing to refresh after an optimizer step.  SALT_BF16 rounds them to bf16 (nearest even) on the way into LDS and contracts with
+ * v_mfma_f32_32x32x16_bf16 (Cout padded to the 32-wide tile with zero rows), fp32 accumulation; SALT_F32 contracts with the exact-f32
+ * v_mfma_f32_32x32x2_f32, as salt_conv does.
+ *   eval  (no stats):  epi(v) = relu?((v + bias[n]) * scale[n] + shift[n]), each part optional per branch (scale / shift go together)
+ *   train (stats_v, stats_cnt_v, stats_h, stats_cnt_h all set; no scale / shift / relu):  y = v + bias and the BatchNorm statistics of
+ *       the STORED y as per-tile partials (sum, M2 about the tile's own mean, count), tile < salt_gcn_pair_stats_parts, in
+ *       salt_bn_finalize's layout [nparts][2][Cout] / [nparts] (sized by salt_bn_stats_floats), fixed order, no atomics: the same bits
+ *       on every run. */
+typedef struct {
+    int dtype;
+    salt_view x;              /* [B,H,W,Cin], may be a channel slice */
+    const float* wv;          /* fp32 master weight of the K x 1 convolution [Cout][Cin][K] */
+    const float* wh;          /* fp32 master weight of the 1 x K convolution [Cout][Cin][K] */
+    int K;
+    salt_view yv;             /* out [B,H,W,Cout] */
+    salt_view yh;             /* out [B,H,W,Cout] */
+    const float* bias_v;      /* [Cout] or NULL */
+    const float* scale_v;     /* eval: folded BatchNorm [Cout], or both NULL */
+    const float* shift_v;
+    int relu_v;
+    const float* bias_h;
+    const float* scale_h;
+    const float* shift_h;
+    int relu_h;
+    float* stats_v;           /* train: [nparts][2][Cout] */
+    float* stats_cnt_v;       /* [nparts] */
+    float* stats_h;
+    float* stats_cnt_h;
+} salt_gcn_pair_args;
+int salt_gcn_pair(const salt_gcn_pair_args*, void* stream);
+int salt_gcn_pair_stats_parts(const salt_gcn_pair_args*);   /* host only: the shapes, K and the alignment are read; < 0: unsupported */
+
+/* The gradient of x from BOTH branches in one launch that writes dx once (a plain store, or += with accumulate): no extended grid, no
+ * fold ring, no strip, no second pass.  The adjoint of the one-sided clamp, checked in float64 against autograd:
+ *     dx[b,r,j,c] = sum_k wv[:,c,k]^T dyv[b, r + (K-1) - k, j]            (rows outside [0, H) contribute nothing)
+ *                 + sum_k wh[:,c,k]^T dyh[b, r, j - k]                    (columns outside [0, W) contribute nothing)
+ *                 + [r == 0]     sum_{i <= min(K-2, H-1)} sum_{k <= K-2-i} wv[:,c,k]^T dyv[b, i, j]
+ *                 + [j == W - 1] sum_{j' >= max(W-K+1, 0)} sum_{k >= W-j'} wh[:,c,k]^T dyh[b, r, j']
+ * THE SUMMATION ORDER IS FIXED (fp32 accumulation; a rerun gives the same bits), per element of dx:
+ *     1. the K x 1 taps, k = 0 .. K-1;
+ *     2. row 0 only: its clamp taps, k = 0 .. K-2 and inside a k the source row i = K-2-k down to 0;
+ *     3. the 1 x K taps, k = 0 .. K-1;
+ *     4. column W - 1 only: its clamp taps, k = 1 .. K-1 and inside a k the source column j' = W-k .. W-1;
+ *     inside a tap the matrix core's order over the output channels; then the stored dx is added when accumulate is set.
+ * The clamp taps are ordinary taps on the ORIGINAL weights (one per (k, source) pair, which is the prefix- / suffix-summed weight of
+ * the formula applied term by term): no summed weight is rounded to bf16.  Shapes, views, dtypes and weights as above (dx in x's role). */
+typedef struct {
+    int dtype;
+    salt_view dyv;            /* [B,H,W,Cout] */
+    salt_view dyh;            /* [B,H,W,Cout] */
+    const float* wv;          /* fp32 master weights, as in the forward call */
+    const float* wh;
+    int K;
+    salt_view dx;             /* out [B,H,W,Cin] */
+    int accumulate;           /* dx += */
+} salt_gcn_pair_dgrad_args;
+int salt_gcn_pair_dgrad(const salt_gcn_pair_dgrad_args*, void* stream);
+
 /* ------------------------------------------------------------------ pyramid pooling at low resolution (csrc/psp.hip): the middle of
  * the reference's PSPNet (architectures/pspnet.py: PSPModule, PSPUpsample).  PSPModule pools its input x [B,h,w,C] to s x s bins for every
  * pyramid size s, runs a 1x1 convolution per size, resizes the results back to h x w, concatenates them with x and runs the 1x1

@@ -23,6 +23,7 @@ Reference classes mirrored (paths relative to the reference's common_blocks/):
   _DenseBlock / _DenseLayer / _Transition as densenet121 / 169 / 201 build them
   architectures/encoders.py:121-164 DenseNetEncoders;  architectures/unet.py:238-307 UNetDenseNet
   architectures/pspnet.py:9-28 PSPModule · :31-42 PSPUpsample · :45-105 PSPNet
+  architectures/base.py:152-178 GlobalConvolutionalNetwork · :181-197 BoundaryRefinement;  architectures/large_kernel_matters.py:8-98 LargeKernelMatters
 """
 import math
 
@@ -933,6 +934,103 @@ class PSPNet(HipNetwork):
         g.upsample(u3, 4, out=hyper.slice(d + u2.C, u3.C))
         g.upsample(u4, 8, out=hyper.slice(d + u2.C + u3.C, u4.C))
         g.head(self.final[0].emit(g, hyper), self.final[1], logits)
+
+
+class GlobalConvolutionalNetwork(EmitOnly):
+    """architectures/base.py:152-178: conv1 = (K x 1) -> (1 x K), conv2 = (1 x K) -> (K x 1), four Conv2dBnRelu with the one-sided replicate
+    pad; the sum of the two branches.  conv1[0] and conv2[0] read the same wide map: Graph.gcn_pair runs them as one launch."""
+
+    def __init__(self, in_channels, out_channels, kernel_size, use_relu=False):
+        super().__init__()
+        if not 2 <= kernel_size <= 9 or not 1 <= out_channels <= 32:
+            raise SaltError('GlobalConvolutionalNetwork: kernel_size %d / %d output channels (salt_gcn_pair: kernel sizes 2 .. 9, at most 32 '
+                            'output channels)' % (kernel_size, out_channels))
+        k = kernel_size
+        self.conv1 = nn.Sequential(Conv2dBnRelu(in_channels, out_channels, kernel_size=(k, 1), use_relu=use_relu, use_padding=True),
+                                   Conv2dBnRelu(out_channels, out_channels, kernel_size=(1, k), use_relu=use_relu, use_padding=True))
+        self.conv2 = nn.Sequential(Conv2dBnRelu(in_channels, out_channels, kernel_size=(1, k), use_relu=use_relu, use_padding=True),
+                                   Conv2dBnRelu(out_channels, out_channels, kernel_size=(k, 1), use_relu=use_relu, use_padding=True))
+
+    def emit(self, g, x, out=None, paired=None):
+        """``paired``: None - Graph.gcn_pair with its measured shape rule (the default); True - the paired launch whatever the rule says;
+        False - the composed route spelled out, conv1[0] and conv2[0] as two Graph.conv launches.  A keyword, not an environment switch."""
+        v, h = self.conv1[0], self.conv2[0]
+        if paired is False:
+            av, ah = v.emit(g, x), h.emit(g, x)
+        else:
+            av, ah = g.gcn_pair(x, v.conv, v.batch_norm, h.conv, h.batch_norm, relu=v.use_relu, name='gcn', force=bool(paired))
+        return g.add(self.conv1[1].emit(g, av), self.conv2[1].emit(g, ah), out=out, name='gcn.sum')
+
+
+class BoundaryRefinement(EmitOnly):
+    """architectures/base.py:181-197: x + Conv2dBnRelu(no ReLU)(Conv2dBnRelu(x)), both K x K with the replicate pad."""
+
+    def __init__(self, in_channels, out_channels, kernel_size):
+        super().__init__()
+        k = (kernel_size, kernel_size)
+        self.conv = nn.Sequential(Conv2dBnRelu(in_channels, out_channels, kernel_size=k, use_relu=True, use_padding=True),
+                                  Conv2dBnRelu(in_channels, out_channels, kernel_size=k, use_relu=False, use_padding=True))
+
+    def emit(self, g, x, out=None):
+        last = self.conv[1]
+        return g.conv(self.conv[0].emit(g, x), last.conv, last.batch_norm, relu=False, res=x, out=out, replicate=True, name='BoundaryRefinement')
+
+
+class LargeKernelMatters(HipNetwork):
+    """architectures.large_kernel_matters.LargeKernelMatters (large_kernel_matters.py:8-98): ResNet encoders without the stem pool, a
+    GlobalConvolutionalNetwork + BoundaryRefinement on each of the /2, /4, /8 and /16 maps, and a 21-channel decoder of transposed
+    convolutions, sums and BoundaryRefinements back to the tile's own size.  F.dropout2d is an identity as everywhere in this file:
+    ``dropout_2d`` is accepted and ignored."""
+
+    def __init__(self, encoder_depth, num_classes, kernel_size=9, internal_channels=21, use_relu=False, pretrained=False, dropout_2d=0.0,
+                 pool0=False):
+        super().__init__()
+        if pool0:
+            raise SaltError('LargeKernelMatters: pool0=True is not built (the reference then returns half-resolution logits)')
+        if not 2 <= kernel_size <= 9 or not 1 <= internal_channels <= 32:
+            raise SaltError('LargeKernelMatters: kernel_size %d / internal_channels %d (salt_gcn_pair: kernel sizes 2 .. 9, at most 32 output '
+                            'channels)' % (kernel_size, internal_channels))
+        self.num_classes, self.dropout_2d = num_classes, dropout_2d
+        self.encoders = ResNetEncoders(encoder_depth, pretrained=pretrained, pool0=pool0)
+        b, c = (512 if encoder_depth in (18, 34) else 2048), internal_channels
+        self.gcn2 = GlobalConvolutionalNetwork(b // 8, c, kernel_size, use_relu=use_relu)
+        self.gcn3 = GlobalConvolutionalNetwork(b // 4, c, kernel_size, use_relu=use_relu)
+        self.gcn4 = GlobalConvolutionalNetwork(b // 2, c, kernel_size, use_relu=use_relu)
+        self.gcn5 = GlobalConvolutionalNetwork(b, c, kernel_size, use_relu=use_relu)
+        for name in ('enc_br2', 'enc_br3', 'enc_br4', 'enc_br5', 'dec_br1', 'dec_br2', 'dec_br3', 'dec_br4'):
+            setattr(self, name, BoundaryRefinement(c, c, 3))
+        for name in ('deconv5', 'deconv4', 'deconv3', 'deconv2'):
+            setattr(self, name, DeconvConv2dBnRelu(c, c))
+        self.final = nn.Conv2d(c, num_classes, kernel_size=1, padding=0)
+        self.paired = None           # GlobalConvolutionalNetwork.emit's keyword for all four blocks (None: the shape rule decides); set before the first forward
+
+    def dead_parameter_names(self):
+        return ['encoders.encoder.fc.weight', 'encoders.encoder.fc.bias']
+
+    def output_shape(self, shape):
+        B, _, H, W = shape
+        if H % 16 or W % 16:
+            raise SaltError('LargeKernelMatters needs tiles whose sides are multiples of 16 (got %dx%d): encoder5 is the /16 map and every '
+                            'decoder level doubles it' % (H, W))
+        return (B, self.num_classes, H, W)
+
+    def emit(self, g, x_nchw, logits):
+        self.output_shape(tuple(x_nchw.shape))
+        enc = self.encoders.encoder
+        x = g.conv_first(x_nchw, enc.conv1, enc.bn1, relu=True, name='stem')
+        e2 = emit_blocks(g, enc.layer1, x)
+        e3 = emit_blocks(g, enc.layer2, e2)
+        e4 = emit_blocks(g, enc.layer3, e3)
+        e5 = emit_blocks(g, enc.layer4, e4)
+        gcn2 = self.enc_br2.emit(g, self.gcn2.emit(g, e2, paired=self.paired))
+        gcn3 = self.enc_br3.emit(g, self.gcn3.emit(g, e3, paired=self.paired))
+        gcn4 = self.enc_br4.emit(g, self.gcn4.emit(g, e4, paired=self.paired))
+        gcn5 = self.enc_br5.emit(g, self.gcn5.emit(g, e5, paired=self.paired))
+        d5 = self.deconv5.emit(g, gcn5)
+        d4 = self.deconv4.emit(g, self.dec_br4.emit(g, g.add(d5, gcn4, name='dec4.sum')))
+        d3 = self.deconv3.emit(g, self.dec_br3.emit(g, g.add(d4, gcn3, name='dec3.sum')))
+        d2 = self.dec_br1.emit(g, self.deconv2.emit(g, self.dec_br2.emit(g, g.add(d3, gcn2, name='dec2.sum'))))
+        g.head(d2, self.final, logits)
 
 
 class DepthChannelExcitation(EmitOnly):

@@ -20,7 +20,7 @@ void salt_set_error(const char* fmt, ...) {
 
 extern "C" const char* salt_last_error(void) { return g_err; }
 
-extern "C" int salt_abi_version(void) { return 31; }
+extern "C" int salt_abi_version(void) { return 32; }
 
 extern "C" int salt_device_info(int* cu_count, int* lds_bytes, char* arch_name, int arch_name_len) {
     int dev = 0;
@@ -339,6 +339,8 @@ extern "C" int salt_abi_struct_sizes(int* out, int n) {
     (int)sizeof(salt_dense_conv_wgrad_args),
     (int)sizeof(salt_dense_moments_args),
     (int)sizeof(salt_dense_bn_prep_args),
+    (int)sizeof(salt_gcn_pair_args),
+    (int)sizeof(salt_gcn_pair_dgrad_args),
     (int)sizeof(salt_psp_pool_args),
     (int)sizeof(salt_psp_pool_bwd_args),
     (int)sizeof(salt_psp_merge_args),

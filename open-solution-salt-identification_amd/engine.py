@@ -1104,7 +1104,15 @@ class Graph:
             Hp, Wp = x.H + top, x.W + right
             td = [(-(t[2]) - top, -(t[3])) for t in taps]
             acc = x.grad_state()
-            if x.C % self.ve == 0:
+            fused = x.C % self.ve == 0
+            if fused and (top >= 8 or right >= 8):
+                # a long line kernel ((9, 1) / (1, 9): the composed route of Graph.gcn_pair): the fused fold needs tiles larger than the pad,
+                # which the plan of a small map does not give - ask it, and take the strip fold where it refuses
+                S = self._conv_probe(dy._view(dy.buf.grad()), 1, td, 1, 0, x._view(x.buf.grad()), Hp, Wp, fold_top=top, fold_right=right)
+                fused = lib.salt_conv_stats_parts(ctypes.byref(S)) >= 0
+                if not fused and 'fused fold needs tiles larger than the pad' not in lib.salt_last_error().decode(errors='replace'):
+                    raise SaltError('conv plan failed: ' + lib.salt_last_error().decode(errors='replace'))       # any other refusal is not the strip's to hide
+            if fused:
                 # fused fold: the launch tiles the extended grid so that every pad-ring pixel shares a tile with the edge pixel it folds
                 # onto; the epilogue sums them from the staged tile - no strip, no second pass, and (a plain store of the complete
                 # gradient) the launch can carry the BatchNorm-backward sums of x's producer
@@ -1674,6 +1682,78 @@ class Graph:
             self._dgrad(conv, x, y, taps, 1, False, KH, KW)
         self.tape.append(backward)
         return out
+
+    # ------------------------------------------------------------------ GlobalConvolutionalNetwork entry: the paired line convolution (csrc/gcn.hip)
+    @staticmethod
+    def gcn_pair_composed(x, K):
+        """The ONE shape rule of Graph.gcn_pair: True where the pair measured slower than two Graph.conv launches by more than the
+        run-to-run spread of the same table (profiles/lkm_bench.json); those shapes take the composed route.  As measured
+        that is EVERY shape of the table: a GCN block with the pair ran 5 .. 51 % slower forward + backward than the composed one at all
+        nine shapes ([32,64,64,64] .. [32,2048,8,8] and [2,64,32,32] .. [2,512,4,4], 16 K to 8 M elements of x, spread under 2 %), and
+        nothing in between or beyond was measured faster.  So the rule is True for every shape today: the pair runs only where a caller
+        asks for it (``force``), until one of the causes listed in DESIGN 21 is removed and the table says otherwise.  tests/test_lkm_cpu.py
+        holds this function to the table in both directions."""
+        return True
+
+    def gcn_pair(self, x, conv_v, bn_v, conv_h, bn_h, relu, name='gcn', force=False):
+        """conv1[0] (K x 1) and conv2[0] (1 x K) of a GlobalConvolutionalNetwork (architectures/base.py:152-178), each a Conv2dBnRelu with
+        the reference's one-sided replicate pad, on the SAME input x -> (a_v, a_h) (saltnet.h: salt_gcn_pair / salt_gcn_pair_dgrad).
+        eval: ONE launch with both folded epilogues.  train: ONE launch with the raw outputs and their per-tile statistics partials, then
+        per branch bn_finalize + affine_act (the per-tile protocol in every SALT_BN_FIN mode).  Backward: the two BatchNorm backwards, the
+        two weight gradients on the existing path (P = dL/dy, Q = x, K taps each) and ONE data-gradient launch that stores dL/dx once.
+        The convolution biases are treated as Graph.conv treats them in front of a train-mode BatchNorm.
+        Where gcn_pair_composed says so the two convolutions run as two Graph.conv launches instead; ``force`` takes the pair regardless (tests,
+        tools/lkm_bench.py)."""
+        eng = self.engine
+        Cout, Cin, K, one = conv_v.weight.shape
+        if (one != 1 or tuple(conv_h.weight.shape) != (Cout, Cin, 1, K) or Cin != x.C or bn_v is None or bn_h is None
+                or bn_v.num_features != Cout or bn_h.num_features != Cout or tuple(conv_v.stride) != (1, 1) or tuple(conv_h.stride) != (1, 1)):
+            raise SaltError('gcn_pair %s: weights %s / %s on %d channels (a K x 1 and a 1 x K unit-step convolution of the same widths, each with a '
+                            'BatchNorm, are expected)' % (name, tuple(conv_v.weight.shape), tuple(conv_h.weight.shape), x.C))
+        if not force and self.gcn_pair_composed(x, K):
+            return (self.conv(x, conv_v, bn_v, relu=relu, replicate=True, name=name + '.v'),
+                    self.conv(x, conv_h, bn_h, relu=relu, replicate=True, name=name + '.h'))
+        av, ah = self.new_act(x.B, x.H, x.W, Cout, name + '.v'), self.new_act(x.B, x.H, x.W, Cout, name + '.h')
+        probe = fill(STRUCTS['salt_gcn_pair_args'](), dtype=self.dt, x=x._view(x.buf.t), K=K, yv=av._view(av.buf.t), yh=ah._view(ah.buf.t))
+        nparts = lib.salt_gcn_pair_stats_parts(ctypes.byref(probe))
+        if nparts < 1:
+            raise SaltError('gcn_pair %s: %s' % (name, lib.salt_last_error().decode(errors='replace')))
+        if x.on_side and self.fwd.default_stream == 0:
+            self.join()
+        bias = lambda c: c.bias.data_ptr() if c.bias is not None else None
+        common = dict(dtype=self.dt, wv=conv_v.weight.data_ptr(), wh=conv_h.weight.data_ptr(), K=K)
+        if not self.train:
+            wv, wh = eng.bn_work(bn_v), eng.bn_work(bn_h)
+            self.fwd.add('gcn_pair', x=x.view(), yv=av.view(), yh=ah.view(), bias_v=bias(conv_v), scale_v=wv['scale'].data_ptr(),
+                         shift_v=wv['shift'].data_ptr(), relu_v=int(relu), bias_h=bias(conv_h), scale_h=wh['scale'].data_ptr(),
+                         shift_h=wh['shift'].data_ptr(), relu_h=int(relu), **common)
+            av.on_side = ah.on_side = self.fwd.default_stream == 1
+            return av, ah
+        yv, yh = self.new_act(x.B, x.H, x.W, Cout, name + '.v.y'), self.new_act(x.B, x.H, x.W, Cout, name + '.h.y')
+        prod = []
+
+        def launch_v(stats, stats_cnt):
+            prod.append(self.fwd.add('gcn_pair', x=x.view(), yv=yv.view(), yh=yh.view(), bias_v=bias(conv_v), bias_h=bias(conv_h), stats_v=stats,
+                                     stats_cnt_v=stats_cnt, **common))
+            return prod[0]
+
+        def launch_h(stats, stats_cnt):                  # the same launch: it fills the second branch's workspaces too
+            self.fwd.set_fields(prod[0], stats_h=stats, stats_cnt_h=stats_cnt)
+            return prod[0]
+        w_v, _ = self._bn_behind(launch_v, False, nparts, yv, bn_v, relu, None, av, self._scratch_sfx + '.gcn_v')
+        w_h, _ = self._bn_behind(launch_h, False, nparts, yh, bn_h, relu, None, ah, self._scratch_sfx + '.gcn_h')
+        av.on_side = ah.on_side = self.fwd.default_stream == 1
+
+        def backward():
+            self._bn_train_bwd(yv, bn_v, relu, None, av, w_v)
+            self._bn_train_bwd(yh, bn_h, relu, None, ah, w_h)
+            self._wgrad(yv.gview(), x.view(), [(k - (K - 1), 0) for k in range(K)], [(k, 0) for k in range(K)], 1, 1, conv_v.weight, K, 1)
+            self._wgrad(yh.gview(), x.view(), [(0, k) for k in range(K)], [(0, k) for k in range(K)], 1, 1, conv_h.weight, 1, K)
+            if x.buf.name != '__input__':
+                acc = x.grad_state()
+                self.bwd.add('gcn_pair_dgrad', dyv=yv.gview(), dyh=yh.gview(), dx=x.gview(), accumulate=acc, **common)
+        self.tape.append(backward)
+        return av, ah
 
     # ------------------------------------------------------------------ logit head: 1x1 conv to <= 4 channels, fp32 NCHW out
     def head(self, x, conv, logits_nchw):

@@ -46,6 +46,11 @@ ARCHITECTURES = {
     'PSPNet': {'model': A.PSPNet,
                'model_config': {'encoder_depth': 34, 'pretrained': False, 'use_hypercolumn': True, 'pool0': False},
                'init_weights': False},
+    # models.py:35-40 with `pretrained` off: global convolutional networks on the /2 .. /16 maps (csrc/gcn.hip)
+    'LargeKernelMatters': {'model': A.LargeKernelMatters,
+                           'model_config': {'encoder_depth': 34, 'pretrained': False, 'kernel_size': 9, 'internal_channels': 21,
+                                            'dropout_2d': 0.0, 'use_relu': True, 'pool0': False},
+                           'init_weights': False},
     # unet_models.py zoo (named by BASELINE.json's north_star; not wired into the reference's registry)
     'TernausUNetResNet': {'model': A.TernausUNetResNet,
                           'model_config': {'encoder_depth': 34, 'num_filters': 32, 'dropout_2d': 0.0, 'pretrained': False, 'is_deconv': True},
