@@ -99,10 +99,13 @@ class Act:
     """[B,H,W,C] activation in ``dtype`` storage on the device: contiguous, or (``sliced``) channels [32, 32 + C) of rows C + 96 wide whose
     other channels hold a sentinel.  ``check`` asserts that nothing outside the window changed."""
 
-    def __init__(self, data, dtype, sliced):
+    def __init__(self, data, dtype, sliced, layout=None):
+        """layout: (c0, cs) of a window the two standard placements do not give (rows that are no multiple of 16 bytes)"""
         from salt_amd.engine import shaped_view
         B, H, W, C = data.shape
         self.C, self.c0, self.cs = C, (32 if sliced else 0), (C + 96 if sliced else C)
+        if layout is not None:
+            self.c0, self.cs = layout
         self.sentinel = float(torch.tensor(SENTINEL, dtype=TDT[dtype]).float())          # as the storage dtype holds it
         self.buf = torch.full((B * H * W * self.cs + 128,), SENTINEL, dtype=TDT[dtype], device=DEV)
         self.rows = self.buf[64:64 + B * H * W * self.cs].view(B, H, W, self.cs)
@@ -117,6 +120,50 @@ class Act:
         ok = bool((b[:64] == self.sentinel).all()) and bool((b[-64:] == self.sentinel).all())
         ok = ok and bool((r[..., :self.c0] == self.sentinel).all()) and bool((r[..., self.c0 + self.C:] == self.sentinel).all())
         assert ok, '%s: write outside the view' % what
+
+
+def vec_of(t, dtype=torch.float32):
+    """a Vec holding t"""
+    v = Vec(t.numel(), dtype=dtype)
+    v.win.copy_(t.reshape(-1).to(dtype))
+    return v
+
+
+def bits(t):
+    return t.view({1: torch.int8, 2: torch.int16, 4: torch.int32, 8: torch.int64}[t.element_size()])
+
+
+class Frozen:
+    """device buffers that a launch must leave bit-unchanged"""
+
+    def __init__(self, **bufs):
+        self.bufs = bufs
+        self.was = {k: v.clone() for k, v in bufs.items()}
+
+    def check(self, what):
+        for k, v in self.bufs.items():
+            assert torch.equal(bits(v), bits(self.was[k])), '%s: %s changed' % (what, k)
+
+
+def within(got, ref64, ev32, what, ratios, case, key, allowance=None, keep=None):
+    """The bound of the fp64 operator suites of scSE and the channel gate: a float32 evaluation ``ev32`` of the same case sits e32 (largest
+    absolute error over the tensor) from the float64 reference, ``got`` may sit 4 e32 + 1e-6 max|ref| from it, plus a per-element
+    ``allowance`` (the rounding of 16-bit storage).  ``keep``: the elements compared.  The worst error / bound goes to ratios[case][key]."""
+    assert got.shape == ref64.shape, (what, got.shape, ref64.shape)
+    assert bool(torch.isfinite(got).all()), '%s: non-finite output' % what
+    ev32 = ev32.double()
+    if keep is not None:
+        got, ref64, ev32 = got[keep], ref64[keep], ev32[keep]
+        allowance = allowance[keep] if allowance is not None else None
+    mx = float(ref64.abs().max())
+    e32 = float((ev32 - ref64).abs().max())
+    bound = 4 * e32 + 1e-6 * mx + (allowance if allowance is not None else 0.0)
+    err = (got - ref64).abs()
+    ratio = float((err / bound).max()) if mx > 0 else (0.0 if float(err.max()) == 0 else float('inf'))
+    per = ratios.setdefault(case, {})
+    per[key] = max(per.get(key, 0.0), ratio)
+    print('%s | %s: err %.3e  yardstick %.3e  max|ref| %.3e  ratio %.3f' % (what, key, float(err.max()), e32, mx, ratio))
+    assert ratio <= 1.0, '%s | %s: error at %.3f of the bound (err %.3e, yardstick %.3e, max|ref| %.3e)' % (what, key, ratio, float(err.max()), e32, mx)
 
 
 def merge_partials(stats, cnt):

@@ -416,7 +416,8 @@ def test_backward_program_is_idempotent_without_a_fresh_forward(dtype):
 def test_scse_backward_batch_tiles_c256(B):
     """se_fc_bwd_kernel is ONE workgroup whose per-image vectors had to fit 160 KB of LDS - C = 256 (the ResNet101 / 152
     decoders, architectures/base.py:82-117) failed with SALT_E_LDS above 51 images per GPU, i.e. at BASELINE C3's batch 64.  Round 6
-    walks the batch in tiles; 51 still runs as ONE tile (the old path), 64 as 45 + 19, 130 as three tiles - all against the oracle's
+    walks the batch in tiles of (160 KiB - 2 R C 4) / ((3 C + 2 R + 1) 4) = 40 images at C = 256, R = 16 (launch_se_fc); 51 still runs as
+    ONE tile (the old path), 64 as 40 + 24, 130 as four tiles (40 + 40 + 40 + 10) - all against the oracle's
     composition of ChannelSELayer and SpatialSELayer (pinned by fixtures F4_channel_se / F4_spatial_se in tests/test_oracle_golden.py)."""
     from torch import nn
     from gpu_harness import BlockRun
