@@ -933,6 +933,10 @@ typedef struct {
                                * (cvRound(c * 2048), each on its own), integer horizontal / vertical sums, saturate((v + 2^21) >> 22);
                                * differs from 1 by one LSB on a few percent of the pixels.  0: bilinear, half-pixel centres, nearest for
                                * the mask (rounds 1 - 2 default) */
+    int pad_mode;             /* 0: edge (replicate: padded index clamped to the tile), 1: reflect-101 (cv2.BORDER_REFLECT_101 of PadFixed,
+                               * augmentation.py:99-101 = np.pad(mode='reflect') of imgaug 0.2.5's Pad at inference): index i of an axis of n
+                               * -> -i for i < 0, 2 n - 2 - i for i >= n; needs pad <= n - 1 on every side (else SALT_E_BADARG).  Applied
+                               * where the clamp is: on the resized grid, image and mask alike; everything after the pad is unchanged */
 } salt_preprocess_args;
 int salt_preprocess(const salt_preprocess_args*, void* stream);
 
@@ -1040,6 +1044,7 @@ typedef struct {
     uint8_t* geo_img;         /* debug out [B,h,w]: the tile after the geometric stages, or NULL */
     uint8_t* geo_mask;        /* debug out [B,h,w]: the binarised mask after the geometric stages, or NULL */
     uint8_t* gray;            /* debug out [B,H,W]: the padded tile after the intensity stage, or NULL */
+    int pad_mode;             /* 0 edge | 1 reflect-101, as salt_preprocess_args.pad_mode */
 } salt_augment_preprocess_args;
 int salt_augment_preprocess(const salt_augment_preprocess_args*, void* stream);
 
@@ -1083,6 +1088,123 @@ typedef struct {
     int* gt_count;            /* out [B] */
 } salt_iou_sweep_args;
 int salt_iou_sweep(const salt_iou_sweep_args*, void* stream);
+
+/* ------------------------------------------------------------------ loader modes 'resize' / 'stacking' (csrc/resize.hip)
+ * The reference's second-level data path (loaders.py:564-579, 786-795; postprocessing.py:8-21) and its `loader_mode: resize`.
+ * skimage / imgaug / cv2 are not executable where this library is built, so every formula below is RESTATED from their sources
+ * (skimage 0.14, PIL) and pinned against scipy.ndimage / PIL by the CPU tests; DESIGN.md 23 has the provenance.
+ *
+ * Source coordinates, all in float64, every operation rounded on its own (no fused multiply-add):
+ *     s_r = h_in / h_out,  r(i) = s_r * (i + 0.5) - 0.5;   s_c = w_in / w_out,  c(j) = s_c * (j + 0.5) - 0.5
+ * BILINEAR64(P, r, c), P a [h_in, w_in] map that reads 0 outside [0, h_in) x [0, w_in):
+ *     r0 = floor(r), dr = r - r0, c0 = floor(c), dc = c - c0
+ *     top = (1 - dc) * P(r0, c0)     + dc * P(r0, c0 + 1)
+ *     bot = (1 - dc) * P(r0 + 1, c0) + dc * P(r0 + 1, c0 + 1)
+ *     v   = (1 - dr) * top + dr * bot                                  (float64; fp32 taps are widened exactly)
+ *
+ * salt_stack_resize: ResizeArray + to_tensor_stacking in one launch (skimage.transform.resize(order 1, mode 'constant', cval 0, no
+ * anti-aliasing) of every map: the border output pixels of an up-scale are blended with the zero outside, as the reference's are).
+ *     y[b, m, i, j] = (float)BILINEAR64(x[b, :, :, m], r(i), c(j))     one rounding, to fp32
+ * The input is addressed by element strides, so both layouts a caller holds are one entry point:
+ *     [B,h,w,M] (np.stack(maps, axis=-1) per tile, utils.py:580): sb = h w M, sr = w M, sc = M, sm = 1
+ *     [B,M,h,w] (per-model planes):                                 sb = M h w, sr = w, sc = 1, sm = h w
+ * 1 <= M <= SALT_STACK_RESIZE_MAX_MAPS; h, w, H, W <= SALT_RESIZE_MAX_SIDE; B <= 65535 (one grid plane per image). */
+#define SALT_STACK_RESIZE_MAX_MAPS 64
+#define SALT_RESIZE_MAX_SIDE 256
+typedef struct {
+    const float* x;           /* fp32 maps, element (b, r, c, m) at x[b sb + r sr + c sc + m sm] */
+    int B;
+    int h;
+    int w;
+    int M;
+    int64_t sb;               /* element strides, all > 0; sm == 1 or sc == 1 */
+    int64_t sr;
+    int64_t sc;
+    int64_t sm;
+    int H;
+    int W;
+    float* y;                 /* out fp32 NCHW [B,M,H,W], contiguous */
+} salt_stack_resize_args;
+int salt_stack_resize(const salt_stack_resize_args*, void* stream);
+
+/* salt_mask_resize: the stacking target (loaders.py:355-360, 572-575).  For class k in (0, 1): Image.fromarray((mask == k) as uint8)
+ * -> transforms.Resize((H, W)) = PIL BILINEAR -> convert('L') -> float32; the two classes are resized independently.
+ * PIL's 8-bit resample is TWO passes, horizontal then vertical, the intermediate rounded onto the uint8 grid:
+ *     per axis (n_in -> n_out): scale = n_in / n_out, support = max(scale, 1), centre(x) = (x + 0.5) scale
+ *     window [start, start + len) = [max(int(centre - support + 0.5), 0), min(int(centre + support + 0.5), n_in))
+ *     weight of tap t: triangle((t - centre + 0.5) * (1 / support)), triangle(u) = max(1 - |u|, 0), times 1 / (their sum) (float64)
+ *     t[r, j]      = floor(sum_t wc[j][t] * (mask[b, r, cstart[j] + t] == k) + 0.5)          horizontal, all float64
+ *     target[b, k, i, j] = floor(sum_t wr[i][t] * t[rstart[i] + t, j] + 0.5)                 vertical
+ * The tables are built by the caller in float64 and passed in (DEVICE arrays); the kernel rounds nothing but the two floor(x + 0.5).
+ * The horizontal intermediate lives in registers and is never stored. */
+typedef struct {
+    const uint8_t* mask;      /* [B,h,w] */
+    int B;
+    int h;
+    int w;
+    int H;
+    int W;
+    const int* row_start;     /* DEVICE [H]: first source row of output row i */
+    const int* row_len;       /* DEVICE [H]: 1 <= len <= row_taps, row_start + row_len <= h */
+    const double* row_w;      /* DEVICE [H][row_taps] */
+    int row_taps;
+    const int* col_start;     /* DEVICE [W] */
+    const int* col_len;       /* DEVICE [W] */
+    const double* col_w;      /* DEVICE [W][col_taps] */
+    int col_taps;
+    float* target;            /* out fp32 NCHW [B,2,H,W] */
+} salt_mask_resize_args;
+int salt_mask_resize(const salt_mask_resize_args*, void* stream);
+
+/* postprocessing.resize_image on a (C,H,W) probability array with a (C,h,w) target (skimage 0.14's n-D branch:
+ * scipy.ndimage.map_coordinates(order 1, mode 'constant') at (channel, r(i), c(j)), no anti-aliasing): BILINEAR64 per channel.
+ * h <= H and w <= W only (every coordinate then lies inside the source; an up-scale through this path is refused).
+ * salt_resize_prob stores (float)v.  salt_resize_threshold and salt_resize_iou_sweep decide on the float64 interpolant v itself
+ * (the reference thresholds the float64 array, postprocessing.py:41-43), which is never stored. */
+typedef struct {
+    const float* prob;        /* fp32 NCHW [B,C,H,W] */
+    int B;
+    int C;
+    int H;
+    int W;
+    int h;
+    int w;
+    float* out;               /* out fp32 NCHW [B,C,h,w] */
+} salt_resize_prob_args;
+int salt_resize_prob(const salt_resize_prob_args*, void* stream);
+
+typedef struct {
+    const float* prob;        /* fp32 NCHW [B,C,H,W] */
+    int B;
+    int C;
+    int H;
+    int W;
+    int cls;
+    int h;
+    int w;
+    double threshold;
+    uint8_t* mask;            /* out [B,h,w] in {0,1}: v > threshold */
+} salt_resize_threshold_args;
+int salt_resize_threshold(const salt_resize_threshold_args*, void* stream);
+
+/* the counts of salt_iou_sweep with pred_t = v > t on the resized interpolant, against original-size masks */
+typedef struct {
+    const float* prob;        /* fp32 NCHW [B,C,H,W] */
+    int B;
+    int C;
+    int H;
+    int W;
+    int cls;
+    int h;
+    int w;
+    const uint8_t* gt;        /* [B,h,w] in {0,1} */
+    int T;
+    const double* thresholds; /* HOST array [T], T <= SALT_MAX_THRESHOLDS */
+    int* inter;               /* out [B][T] */
+    int* pred;                /* out [B][T] */
+    int* gt_count;            /* out [B] */
+} salt_resize_iou_sweep_args;
+int salt_resize_iou_sweep(const salt_resize_iou_sweep_args*, void* stream);
 
 /* ------------------------------------------------------------------ program executor
  * A training/inference step is a static list of the operators above.  The host builds it once per

@@ -200,9 +200,14 @@ class ExperimentTiming(Callback):
 
 
 class ValidationMonitor(Callback):
-    """callbacks.py:462-568.  ``data_dir`` / ``loader_mode`` are accepted for signature compatibility; the ground-truth masks come
-    from the validation batches themselves (target channel 1), not from files on disk.  ``use_depth``: the validation batches are
-    ``(X, D, *targets)`` and the network is called as ``model(X, D)`` (callbacks.py:568-586)."""
+    """callbacks.py:462-568.  ``data_dir`` is accepted for signature compatibility; the ground-truth masks come from the validation
+    batches themselves (target channel 1), not from files on disk.  ``use_depth``: the validation batches are ``(X, D, *targets)`` and
+    the network is called as ``model(X, D)`` (callbacks.py:568-586).
+
+    ``loader_mode`` 'resize' / 'stacking' with ORIGINAL-SIZE masks in ``meta_valid`` (a uint8 array / tensor [N,h,w] in validation
+    order - the reference reads them from meta_valid's files): the probabilities are brought back to h x w by resize_image and scored
+    against those masks, as the reference does (callbacks.py:503-527, postprocessing.py:8-21).  Any other ``meta_valid`` (None, a
+    DataFrame, a string) or loader mode scores the batches' own targets on a centre crop, as before."""
 
     def __init__(self, data_dir=None, loader_mode=None, epoch_every=None, batch_every=None, use_depth=False):
         super().__init__()
@@ -213,6 +218,9 @@ class ValidationMonitor(Callback):
     def set_params(self, transformer, validation_datagen=None, meta_valid=None, *args, **kwargs):
         super().set_params(transformer, validation_datagen)
         self.meta_valid = meta_valid
+        # the resized scoring path (score_validation): every callback's shared validation pass must take it, so the transformer holds it
+        y_true = original_size_masks(meta_valid) if self.loader_mode in RESIZED_MODES else None
+        transformer.validation_masks = (self.loader_mode, y_true) if y_true is not None else None
         net_depth = bool(getattr(getattr(transformer, 'model', None), 'uses_depth', False))
         if bool(self.use_depth) != net_depth:
             raise SaltError('ValidationMonitor(use_depth=%s) on a network that %s a depth input' % (bool(self.use_depth), 'takes' if net_depth else 'does not take'))
@@ -304,9 +312,31 @@ class EarlyStopping(Callback):
         self.epoch_id += 1
 
 
-def score_validation(transformer, validation_datagen, target_size=(101, 101), use_depth=None):
+RESIZED_MODES = ('resize', 'stacking')
+
+
+def original_size_masks(meta_valid):
+    """``meta_valid`` as original-size ground truth: a uint8 array / tensor [N,h,w] -> uint8 tensor, anything else -> None"""
+    if isinstance(meta_valid, np.ndarray) and meta_valid.ndim == 3 and meta_valid.dtype == np.uint8:
+        return torch.from_numpy(np.ascontiguousarray(meta_valid))
+    if torch.is_tensor(meta_valid) and meta_valid.dim() == 3 and meta_valid.dtype == torch.uint8:
+        return meta_valid
+    return None
+
+
+def score_validation(transformer, validation_datagen, target_size=(101, 101), use_depth=None, loader_mode=None, y_true=None):
     """One pass over the validation generator (callbacks.py:529-568 + 503-527): mean loss, and IoU / IOUT at the threshold the
-    reference's sweep selects.  Everything but a few integers per image stays on the GPU."""
+    reference's sweep selects.  Everything but a few integers per image stays on the GPU.
+
+    ``loader_mode`` 'resize' / 'stacking' together with ``y_true`` (original-size masks, uint8 [N,h,w] in validation order): the
+    probabilities are resized back to h x w (resize_image) and swept against those masks; the loss is the batches' own.  Without
+    ``y_true``, or in any other mode, the batches' targets are scored on the centre crop."""
+    resized = loader_mode in RESIZED_MODES and y_true is not None
+    if resized:
+        y_true = original_size_masks(y_true.detach() if torch.is_tensor(y_true) else np.asarray(y_true))
+        if y_true is None:
+            raise SaltError('score_validation: y_true must be a uint8 array / tensor [N,h,w]')
+    seen = 0
     model = transformer.model
     if use_depth is None:
         use_depth = bool(getattr(model, 'uses_depth', False))
@@ -328,11 +358,18 @@ def score_validation(transformer, validation_datagen, target_size=(101, 101), us
                 logits = model(X)
             losses.append((loss_function(logits, target) * weight).detach().reshape(1))
             prob = torch.sigmoid(logits.float())
-            H, W = prob.shape[2:]
-            hw = (min(target_size[0], H), min(target_size[1], W))
-            top, left = inference.crop_window(H, W, hw)
-            gt = (target[:, 1, top:top + hw[0], left:left + hw[1]] > 0.5).to(torch.uint8)
-            counts.append(inference.iou_counts(prob, gt, thresholds, cls=1))
+            if resized:
+                n = prob.shape[0]
+                if seen + n > y_true.shape[0]:
+                    raise SaltError('score_validation: %d original-size masks for more validation tiles' % y_true.shape[0])
+                counts.append(inference.iou_counts_resized(prob, y_true[seen:seen + n].to(dev), thresholds, cls=1))
+                seen += n
+            else:
+                H, W = prob.shape[2:]
+                hw = (min(target_size[0], H), min(target_size[1], W))
+                top, left = inference.crop_window(H, W, hw)
+                gt = (target[:, 1, top:top + hw[0], left:left + hw[1]] > 0.5).to(torch.uint8)
+                counts.append(inference.iou_counts(prob, gt, thresholds, cls=1))
             if batch_id == steps:
                 break
     if was_training:

@@ -30,7 +30,7 @@ enum : uint64_t {
 
 struct AugKP {
     const unsigned char* img; const unsigned char* mask; float* x; float* target;
-    int B, h, w, rh, rw, top, left, H, W, channels;
+    int B, h, w, rh, rw, top, left, H, W, channels, pad_mode;
     float mean[3], inv_std[3];
     salt_augment_config cfg;
     uint64_t seed, counter;
@@ -86,11 +86,7 @@ __device__ __forceinline__ float u8_to_unit(int v) {
     return (float)v * (1.f / 255.f);
 }
 
-__device__ __forceinline__ int reflect101(int i, int n) {
-    if (n == 1) return 0;
-    i = i < 0 ? -i : i;
-    return i >= n ? 2 * n - 2 - i : i;
-}
+using salt_pre::reflect101;
 
 // cv2.filter2D (correlation) with a reflect-101 border, the 9 products summed row by row, each operation rounded on its own
 __device__ void conv3x3(const unsigned char* src, unsigned char* dst, int h, int w, const float (&k)[9], bool binarize) {
@@ -338,7 +334,7 @@ __global__ __launch_bounds__(NT) void augment_kernel(AugKP p) {
         }
     }
 
-    // ---- resize + edge pad (salt_preprocess interpolation 2), intensity, normalisation, one-hot target
+    // ---- resize + pad (edge | reflect-101) (salt_preprocess interpolation 2), intensity, normalisation, one-hot target
     const bool invert = s_prm[P_INVERT] != 0.f, contrast = s_prm[P_CONTRAST_ON] != 0.f;
     const float alpha = s_prm[P_CONTRAST], value = s_prm[P_VALUE];
     const int op = (int)s_prm[P_OP];
@@ -347,7 +343,7 @@ __global__ __launch_bounds__(NT) void augment_kernel(AugKP p) {
     const int HW = p.H * p.W;
     for (int i = tid; i < HW; i += NT) {
         const int Y = i / p.W, X = i - (i / p.W) * p.W;
-        const int ry = min(max(Y - p.top, 0), p.rh - 1), rx = min(max(X - p.left, 0), p.rw - 1);
+        const int ry = salt_pre::pad_index(Y, p.top, p.rh, p.pad_mode), rx = salt_pre::pad_index(X, p.left, p.rw, p.pad_mode);
         int v, m;
         if (resize) {
             int y0, x0, cy[4], cx[4];
@@ -394,6 +390,8 @@ extern "C" int salt_augment_preprocess(const salt_augment_preprocess_args* a, vo
     p.top = a->top; p.left = a->left; p.H = a->H; p.W = a->W; p.channels = a->channels;
     if (p.top + p.rh > p.H || p.left + p.rw > p.W) SALT_FAIL(SALT_E_BADARG, "augment_preprocess: resized tile + pad offset exceeds the output");
     if ((int64_t)p.H * p.W >= (1ll << 30)) SALT_FAIL(SALT_E_BADARG, "augment_preprocess: output too large");
+    p.pad_mode = a->pad_mode;
+    if (const char* why = salt_pre::pad_mode_error(a->pad_mode, p.top, p.left, p.rh, p.rw, p.H, p.W)) SALT_FAIL(SALT_E_BADARG, "augment_preprocess: %s", why);
     for (int i = 0; i < 3; ++i) {
         if (a->std[i] <= 0.f) SALT_FAIL(SALT_E_BADARG, "augment_preprocess: std must be positive");
         p.mean[i] = a->mean[i]; p.inv_std[i] = 1.f / a->std[i];

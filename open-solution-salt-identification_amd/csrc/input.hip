@@ -6,7 +6,7 @@
 //     -> optional resize to [rh, rw]: cubic (cv2.INTER_CUBIC, imgaug's iaa.Scale default) or bilinear     train: 101 -> 102
 //        uint8 tiles: cv2's own 11-bit FIXED-POINT evaluation of the separable cubic (interpolation 2, cubic_fixed_u8 below);
 //        float tiles / interpolation 1: the float form of the same filter
-//     -> edge (replicate) pad: `top` rows / `left` columns, rest to [H, W]                                train: 13; inference 13/14
+//     -> edge (replicate) or reflect-101 pad: `top` rows / `left` columns, rest to [H, W]                 train: 13; inference 13/14
 //     -> Grayscale(3) + ToTensor + Normalize(mean, std) per channel
 //     -> AddDepthChannels: ch1 := linspace(0, 1, H)[row], ch2 := ch0 * ch1                                (3-channel mode)
 //   mask tile [h, w] -> nearest resize -> same pad -> one-hot {1 - m, m} target [2, H, W]
@@ -16,7 +16,7 @@ namespace {
 
 struct PreKP {
     const void* img; const unsigned char* mask; float* x; float* target;
-    int img_is_u8, B, h, w, rh, rw, top, left, H, W, channels, cubic;
+    int img_is_u8, B, h, w, rh, rw, top, left, H, W, channels, cubic, pad_mode;
     float mean[3], inv_std[3];
 };
 
@@ -33,7 +33,7 @@ __global__ void preprocess_kernel(PreKP p) {
     const float sy = (float)p.h / (float)p.rh, sx = (float)p.w / (float)p.rw;
     for (int64_t i = blockIdx.x * 256LL + threadIdx.x; i < n; i += gridDim.x * 256LL) {
         const int X = (int)(i % p.W); int64_t r = i / p.W; const int Y = (int)(r % p.H); const int b = (int)(r / p.H);
-        const int ry = min(max(Y - p.top, 0), p.rh - 1), rx = min(max(X - p.left, 0), p.rw - 1);      // edge pad = clamp
+        const int ry = salt_pre::pad_index(Y, p.top, p.rh, p.pad_mode), rx = salt_pre::pad_index(X, p.left, p.rw, p.pad_mode);   // edge pad = clamp
         auto px = [&](int yy, int xx) -> float {
             const int64_t o = ((int64_t)b * p.h + yy) * p.w + xx;
             return p.img_is_u8 ? (float)reinterpret_cast<const unsigned char*>(p.img)[o] * (1.f / 255.f) : reinterpret_cast<const float*>(p.img)[o];
@@ -108,6 +108,8 @@ extern "C" int salt_preprocess(const salt_preprocess_args* a, void* stream) {
     if (a->interpolation == 2 && !a->img_is_u8) SALT_FAIL(SALT_E_BADARG, "preprocess: the fixed-point cubic resize is cv2's uint8 path: uint8 tiles only");
     if (a->interpolation == 2 && (int64_t)a->h * a->w >= (1ll << 31)) SALT_FAIL(SALT_E_BADARG, "preprocess: tile too large");
     if (p.top + p.rh > p.H || p.left + p.rw > p.W) SALT_FAIL(SALT_E_BADARG, "preprocess: resized tile + pad offset exceeds the output");
+    p.pad_mode = a->pad_mode;
+    if (const char* why = salt_pre::pad_mode_error(a->pad_mode, p.top, p.left, p.rh, p.rw, p.H, p.W)) SALT_FAIL(SALT_E_BADARG, "preprocess: %s", why);
     for (int c = 0; c < 3; ++c) {
         if (a->std[c] <= 0.f) SALT_FAIL(SALT_E_BADARG, "preprocess: std must be positive");
         p.mean[c] = a->mean[c]; p.inv_std[c] = 1.f / a->std[c];

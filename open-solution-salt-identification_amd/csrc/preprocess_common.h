@@ -4,6 +4,27 @@
 
 namespace salt_pre {
 
+// cv2.BORDER_REFLECT_101 = np.pad(mode='reflect'): the border pixel is not repeated; one reflection (|overhang| <= n - 1)
+__device__ __forceinline__ int reflect101(int i, int n) {
+    if (n == 1) return 0;
+    i = i < 0 ? -i : i;
+    return i >= n ? 2 * n - 2 - i : i;
+}
+
+// padded output index -> index on the (resized) tile axis of n pixels that starts `before` pixels in: pad_mode 0 edge, 1 reflect-101
+__device__ __forceinline__ int pad_index(int out, int before, int n, int pad_mode) {
+    const int i = out - before;
+    return pad_mode ? reflect101(i, n) : min(max(i, 0), n - 1);
+}
+
+// host side of pad_mode: a value that exists, and for reflect-101 a pad of at most n - 1 pixels on every side
+static inline const char* pad_mode_error(int pad_mode, int top, int left, int rh, int rw, int H, int W) {
+    if (pad_mode != 0 && pad_mode != 1) return "pad_mode must be 0 (edge) or 1 (reflect-101)";
+    if (pad_mode == 1 && (top > rh - 1 || H - top - rh > rh - 1 || left > rw - 1 || W - left - rw > rw - 1))
+        return "reflect-101 needs a pad of at most n - 1 pixels on every side";
+    return nullptr;
+}
+
 // cv2.INTER_CUBIC / imgaug 0.2.5 iaa.Scale default: Keys cubic convolution, a = -0.75, taps at floor(s) - 1 .. floor(s) + 2 of the
 // half-pixel-centred source coordinate s = (dst + 0.5) * in / out - 0.5, indices clamped to the image (BORDER_REPLICATE)
 __device__ __forceinline__ void cubic_w(float t, float (&w)[4]) {

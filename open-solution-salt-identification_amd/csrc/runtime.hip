@@ -20,7 +20,7 @@ void salt_set_error(const char* fmt, ...) {
 
 extern "C" const char* salt_last_error(void) { return g_err; }
 
-extern "C" int salt_abi_version(void) { return 32; }
+extern "C" int salt_abi_version(void) { return 33; }
 
 extern "C" int salt_device_info(int* cu_count, int* lds_bytes, char* arch_name, int arch_name_len) {
     int dev = 0;
@@ -324,6 +324,11 @@ extern "C" int salt_abi_struct_sizes(int* out, int n) {
     (int)sizeof(salt_augment_preprocess_args),
     (int)sizeof(salt_crop_threshold_args),
     (int)sizeof(salt_iou_sweep_args),
+    (int)sizeof(salt_stack_resize_args),
+    (int)sizeof(salt_mask_resize_args),
+    (int)sizeof(salt_resize_prob_args),
+    (int)sizeof(salt_resize_threshold_args),
+    (int)sizeof(salt_resize_iou_sweep_args),
     (int)sizeof(salt_program_entry),
     (int)sizeof(salt_pool_head_args),
     (int)sizeof(salt_pool_head_bwd_args),

@@ -11,6 +11,10 @@ models.py:167) happens here on the device:
                            metrics.py:21-66 (IoU / IOUT with the empty-mask conventions)
                                                                              -> salt_iou_sweep (+ a few host floats)
 
+  loader modes 'resize' /  postprocessing.py:8-21 (resize_image brings the 128x128 probabilities back to 101x101 before the
+  'stacking'               threshold and the metric)                        -> salt_resize_prob, salt_resize_threshold,
+                                                                             salt_resize_iou_sweep
+
 Everything here needs the HIP library; there is no CPU path.
 """
 import ctypes
@@ -166,10 +170,26 @@ def predict_tta(net, X, flip_ud=False, flip_lr=True, variants_per_pass=None, dep
     return tta_mean(logits, variants, B, method)
 
 
-def predict_tta_tiles(net, preprocessor, images, flip_ud=False, flip_lr=True, rotation=False, method='mean'):
+def predict_tta_tiles(net, preprocessor, images, flip_ud=False, flip_lr=True, rotation=False, method='mean', loader_mode='resize_and_pad',
+                      pad_method='edge', target_size=None):
     """TTA exactly in the reference's order of operations: transform the RAW [B,h,w] tiles (augmentation.py:143-153: flipud, fliplr,
     rot90), preprocess every variant (inference pad + Normalize + AddDepthChannels), forward, inverse-transform the probability
-    maps (augmentation.py:156-163) and aggregate (loaders.py:722-760).  ``rotation`` needs square tiles."""
+    maps (augmentation.py:156-163) and aggregate (loaders.py:722-760).  ``rotation`` needs square tiles.
+
+    ``loader_mode`` / ``pad_method`` must be the preprocessor's (a mismatch raises: the caller states the config once and this checks
+    it).  In 'resize' mode every variant is scaled in by the preprocessor and the aggregate is brought back to ``target_size``
+    (default: the tiles' own size) by resize_image; in 'resize_and_pad' mode ``target_size`` must stay None (the crop is
+    crop_threshold's)."""
+    from .input_pipeline import LOADER_MODES, PAD_METHODS
+    if loader_mode not in LOADER_MODES:
+        raise SaltError('predict_tta_tiles: loader_mode %r (%s)' % (loader_mode, ' | '.join(LOADER_MODES)))
+    if pad_method not in PAD_METHODS:
+        raise SaltError('predict_tta_tiles: pad_method %r (%s)' % (pad_method, ' | '.join(PAD_METHODS)))
+    have = (getattr(preprocessor, 'loader_mode', 'resize_and_pad'), getattr(preprocessor, 'pad_method', 'edge'))
+    if have != (loader_mode, pad_method):
+        raise SaltError('predict_tta_tiles(loader_mode=%r, pad_method=%r) with a preprocessor built for %r / %r' % ((loader_mode, pad_method) + have))
+    if target_size is not None and loader_mode != 'resize':
+        raise SaltError("predict_tta_tiles: target_size belongs to loader_mode='resize'")
     if net.training:
         raise SaltError('predict_tta_tiles: call net.eval() first')
     if not images.is_cuda:
@@ -198,7 +218,10 @@ def predict_tta_tiles(net, preprocessor, images, flip_ud=False, flip_lr=True, ro
                 logits = torch.empty((len(specs) * B,) + tuple(lg.shape[1:]), dtype=torch.float32, device=lg.device)
             logits[v * B:(v + 1) * B].copy_(lg)
     # sigmoid, inverse transform (rot90(-k), fliplr, flipud: augmentation.py:156-163) and aggregation of all variants: one kernel
-    return tta_mean(logits, specs, B, method)
+    prob = tta_mean(logits, specs, B, method)
+    if loader_mode == 'resize':
+        return resize_image(prob, tuple(images.shape[1:]) if target_size is None else target_size)
+    return prob
 
 
 # ----------------------------------------------------------------------------- post-processing
@@ -218,6 +241,37 @@ def crop_threshold(prob, target_size=(101, 101), threshold=0.5, cls=1):
     mask = torch.empty((B, h, w), dtype=torch.uint8, device=prob.device)
     _run('crop_threshold', prob=prob.data_ptr(), B=B, C=C, H=H, W=W, cls=cls, top=top, left=left, h=h, w=w,
          threshold=float(threshold), mask=mask.data_ptr())
+    return mask
+
+
+def _down(prob, target_size, what):
+    prob = _f32c(prob)
+    if prob.dim() != 4:
+        raise SaltError('%s: prob must be [B,C,H,W]' % what)
+    h, w = int(target_size[0]), int(target_size[1])
+    if h > prob.shape[2] or w > prob.shape[3]:
+        raise SaltError('%s: %dx%d -> %dx%d is an up-scale; resize_image is pinned for the way back (h <= H, w <= W) only'
+                        % (what, prob.shape[2], prob.shape[3], h, w))
+    return prob, h, w
+
+
+def resize_image(prob, target_size=(101, 101)):
+    """postprocessing.resize_image on the device: [B,C,H,W] -> fp32 [B,C,h,w], the order-1 interpolant evaluated in float64 and
+    rounded once.  Decisions belong to resize_threshold / iou_counts_resized, which take them on the float64 value."""
+    prob, h, w = _down(prob, target_size, 'resize_image')
+    B, C, H, W = prob.shape
+    out = torch.empty((B, C, h, w), dtype=torch.float32, device=prob.device)
+    _run('resize_prob', prob=prob.data_ptr(), B=B, C=C, H=H, W=W, h=h, w=w, out=out.data_ptr())
+    return out
+
+
+def resize_threshold(prob, target_size=(101, 101), threshold=0.5, cls=1):
+    """resize_image + binarize (postprocessing.py:8-21, 41-43): uint8 masks [B,h,w] of ``resized(prob[:, cls]) > threshold``, the
+    comparison made on the float64 interpolant as the reference's is."""
+    prob, h, w = _down(prob, target_size, 'resize_threshold')
+    B, C, H, W = prob.shape
+    mask = torch.empty((B, h, w), dtype=torch.uint8, device=prob.device)
+    _run('resize_threshold', prob=prob.data_ptr(), B=B, C=C, H=H, W=W, cls=cls, h=h, w=w, threshold=float(threshold), mask=mask.data_ptr())
     return mask
 
 
@@ -259,6 +313,26 @@ def iou_counts(prob, gt, thresholds, cls=1):
     pred = torch.empty((B, T), dtype=torch.int32, device=prob.device)
     gtc = torch.empty((B,), dtype=torch.int32, device=prob.device)
     _run('iou_sweep', prob=prob.data_ptr(), B=B, C=C, H=H, W=W, cls=cls, top=top, left=left, h=h, w=w, gt=gt.data_ptr(), T=T,
+         thresholds=ctypes.cast(th, ctypes.c_void_p).value, inter=inter.data_ptr(), pred=pred.data_ptr(), gt_count=gtc.data_ptr())
+    return inter.cpu().numpy().astype(np.int64), pred.cpu().numpy().astype(np.int64), gtc.cpu().numpy().astype(np.int64)
+
+
+def iou_counts_resized(prob, gt, thresholds, cls=1):
+    """iou_counts for loader modes 'resize' / 'stacking': ``prob`` [B,C,H,W] is brought back to the size of the ORIGINAL-size masks
+    ``gt`` (uint8 [B,h,w]) by resize_image and compared there; the interpolant is never stored.  Same return value as iou_counts."""
+    if not torch.is_tensor(gt) or not gt.is_cuda:
+        raise SaltError('iou_counts_resized: gt must live on the GPU')
+    prob, h, w = _down(prob, gt.shape[1:], 'iou_counts_resized')
+    gt = gt.contiguous().to(torch.uint8)
+    B, C, H, W = prob.shape
+    if gt.shape[0] != B:
+        raise SaltError('iou_counts_resized: %d masks for %d probability maps' % (gt.shape[0], B))
+    T = len(thresholds)
+    th = (ctypes.c_double * T)(*[float(t) for t in thresholds])
+    inter = torch.empty((B, T), dtype=torch.int32, device=prob.device)
+    pred = torch.empty((B, T), dtype=torch.int32, device=prob.device)
+    gtc = torch.empty((B,), dtype=torch.int32, device=prob.device)
+    _run('resize_iou_sweep', prob=prob.data_ptr(), B=B, C=C, H=H, W=W, cls=cls, h=h, w=w, gt=gt.data_ptr(), T=T,
          thresholds=ctypes.cast(th, ctypes.c_void_p).value, inter=inter.data_ptr(), pred=pred.data_ptr(), gt_count=gtc.data_ptr())
     return inter.cpu().numpy().astype(np.int64), pred.cpu().numpy().astype(np.int64), gtc.cpu().numpy().astype(np.int64)
 

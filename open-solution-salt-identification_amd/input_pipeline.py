@@ -8,6 +8,12 @@ The reference prepares every tile on the CPU with PIL / imgaug / torchvision and
     inference  edge-pad to the next multiple of 64 with the reference's split: top 13 / bottom 14, left 14 / right 13
     both       Grayscale(3) + ToTensor + Normalize(ImageNet) + AddDepthChannels; mask -> {background, salt} one-hot
 
+The reference's other loader modes (pipelines.py:12-14) and its other pad (neptune.yaml:24) are here too:
+
+    DevicePreprocessor(..., loader_mode='resize')     scale to `resize` (128) without a pad, in both branches (augmentation.py:71-90)
+    DevicePreprocessor(..., pad_method='reflect')     reflect-101 instead of the edge pad, in both branches and with augment=
+    StackingPreprocessor(size=(128, 128))             loader_mode 'stacking' (loaders.py:564-579): first-level maps -> X, masks -> target
+
 Training augmentation (the reference's affine_seq / intensity_seq, main.py:130-133, augmentation.py:34-65) runs on the device too,
 fused into the same pass (csrc/augment.hip, `salt_augment_preprocess`).  It is off by default; a main.py-style caller turns it on for
 the training batches only:
@@ -29,6 +35,10 @@ from ._abi import OP_FUNCS, SaltError, check, fill
 
 MEAN = (0.485, 0.456, 0.406)          # ImageNet statistics (neptune.yaml / loaders.py dataset_params)
 STD = (0.229, 0.224, 0.225)
+
+
+LOADER_MODES = ('resize_and_pad', 'resize')        # pipelines.py:12-14; 'stacking' is StackingPreprocessor's
+PAD_METHODS = ('edge', 'reflect')                  # salt_preprocess_args.pad_mode 0 / 1
 
 
 def pad_split(size, divisor=64):
@@ -106,8 +116,15 @@ class DevicePreprocessor:
     """Callable: (images [B,h,w] uint8|float, masks [B,h,w] or None) on the GPU -> (X [B,C,H,W], target [B,2,H,W] | None)."""
 
     def __init__(self, train, channels=3, resize=102, pad=13, divisor=64, mean=MEAN, std=STD, interpolation='cubic', augment=False, seed=1234,
-                 record_params=False):
-        """``interpolation`` of the train-branch resize: 'cubic' (default) is what the reference executes - augmentation.py:79-85 calls
+                 record_params=False, loader_mode='resize_and_pad', pad_method='edge'):
+        """``loader_mode``: 'resize_and_pad' (default: the geometry above) or 'resize' (pipelines.py:12-14, augmentation.py:71-90
+        resize_seq / resize_to_fit_net): the tile is scaled to ``resize`` x ``resize`` (128 in the reference's config) and NOT padded, in the
+        train and the inference branch, image and mask alike - the same resize kernel with top = left = 0.
+        ``pad_method``: 'edge' (default) or 'reflect' (neptune.yaml:24; PadFixed's cv2.BORDER_REFLECT_101 in training, imgaug's
+        np.pad(mode='reflect') at inference - one index map), applied where the edge pad is, in both branches and with ``augment``; it
+        needs a pad of at most n - 1 pixels on every side.
+
+        ``interpolation`` of the train-branch resize: 'cubic' (default) is what the reference executes - augmentation.py:79-85 calls
         ``iaa.Scale({...})`` without an interpolation argument and imgaug 0.2.5 (environment.yml:15) defaults to 'cubic' =
         cv2.INTER_CUBIC, applied to the uint8 tile AND the uint8 {0,1} mask.  uint8 tiles take cv2's own evaluation of that filter
         (11-bit fixed-point coefficients, integer sums, saturating shift: opencv_python 3.4.0.12, environment.yml:16); float tiles -
@@ -120,6 +137,11 @@ class DevicePreprocessor:
         last call for ``last_params()``."""
         if interpolation not in ('cubic', 'cubic_float', 'bilinear'):
             raise SaltError('DevicePreprocessor: interpolation %r (cubic | cubic_float | bilinear)' % (interpolation,))
+        if loader_mode not in LOADER_MODES:
+            raise SaltError('DevicePreprocessor: loader_mode %r (%s; the stacking loader is StackingPreprocessor)' % (loader_mode, ' | '.join(LOADER_MODES)))
+        if pad_method not in PAD_METHODS:
+            raise SaltError('DevicePreprocessor: pad_method %r (%s)' % (pad_method, ' | '.join(PAD_METHODS)))
+        self.loader_mode, self.pad_method = loader_mode, pad_method
         self.interpolation = interpolation
         self.train, self.channels, self.resize, self.pad, self.divisor = bool(train), int(channels), resize, pad, divisor
         self.mean, self.std = tuple(mean), tuple(std)
@@ -141,6 +163,10 @@ class DevicePreprocessor:
 
     def geometry(self, h, w):
         """(resize_h, resize_w, top, left, H, W)"""
+        if self.loader_mode == 'resize':
+            r = self.resize
+            rh, rw = (0, 0) if (h, w) == (r, r) else (r, r)
+            return rh, rw, 0, 0, r, r
         if self.train:
             r = self.resize
             return r, r, self.pad, self.pad, r + 2 * self.pad, r + 2 * self.pad
@@ -162,6 +188,7 @@ class DevicePreprocessor:
         images = images.contiguous()
         B, h, w = images.shape
         rh, rw, top, left, H, W = self.geometry(h, w)
+        self._check_pad(h, w, rh, rw, top, left, H, W)
         x = torch.empty((B, self.channels, H, W), dtype=torch.float32, device=images.device)
         target, mptr = None, None
         if masks is not None:
@@ -173,9 +200,19 @@ class DevicePreprocessor:
         fill(s, img=images.data_ptr(), img_is_u8=int(images.dtype == torch.uint8), mask=mptr, B=B, h=h, w=w, resize_h=rh, resize_w=rw,
              top=top, left=left, H=H, W=W, channels=self.channels, mean=list(self.mean), std=list(self.std), x=x.data_ptr(),
              target=target.data_ptr() if target is not None else None,
-             interpolation=0 if self.interpolation == 'bilinear' else (2 if self.interpolation == 'cubic' and images.dtype == torch.uint8 else 1))
+             interpolation=0 if self.interpolation == 'bilinear' else (2 if self.interpolation == 'cubic' and images.dtype == torch.uint8 else 1),
+             pad_mode=PAD_METHODS.index(self.pad_method))
         check(fn(ctypes.byref(s), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), 'preprocess')
         return x, target
+
+    def _check_pad(self, h, w, rh, rw, top, left, H, W):
+        """reflect-101 reflects once: every side's pad is at most n - 1 pixels of the (resized) tile"""
+        if self.pad_method != 'reflect':
+            return
+        nh, nw = rh or h, rw or w
+        if max(top, H - top - nh) > nh - 1 or max(left, W - left - nw) > nw - 1:
+            raise SaltError("DevicePreprocessor: pad_method='reflect' needs a pad of at most n - 1 pixels on every side "
+                            '(tile %dx%d, pads %d/%d and %d/%d)' % (nh, nw, top, H - top - nh, left, W - left - nw))
 
     def _augment(self, images, masks, params, debug):
         if images.dtype != torch.uint8:
@@ -185,6 +222,7 @@ class DevicePreprocessor:
         if h > 128 or w > 128:
             raise SaltError('DevicePreprocessor: augmentation takes tiles up to 128x128 (got %dx%d)' % (h, w))
         rh, rw, top, left, H, W = self.geometry(h, w)
+        self._check_pad(h, w, rh, rw, top, left, H, W)
         dev = images.device
         x = torch.empty((B, self.channels, H, W), dtype=torch.float32, device=dev)
         target, mptr = None, None
@@ -213,7 +251,7 @@ class DevicePreprocessor:
              target=target.data_ptr() if target is not None else None, seed=self.seed & (2 ** 64 - 1), counter=self.counter,
              params=rec.data_ptr() if rec is not None else None, params_given=int(params is not None),
              geo_img=dbg['geo_img'].data_ptr() if debug else None, geo_mask=dbg['geo_mask'].data_ptr() if debug else None,
-             gray=dbg['gray'].data_ptr() if debug else None)
+             gray=dbg['gray'].data_ptr() if debug else None, pad_mode=PAD_METHODS.index(self.pad_method))
         check(fn(ctypes.byref(s), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), 'augment_preprocess')
         self.counter += 1
         self._params = rec
@@ -225,6 +263,101 @@ class DevicePreprocessor:
         if self._params is None:
             raise SaltError('DevicePreprocessor: no params recorded (construct with augment and record_params=True)')
         return self._params if raw else decode_params(self._params)
+
+
+def pil_resize_table(n_in, n_out):
+    """PIL's BILINEAR resample coefficients of one axis (Resample.c precompute_coeffs) in float64, as salt_mask_resize takes them:
+    (start [n_out] int32, length [n_out] int32, weights [n_out, taps] float64).  scale = n_in / n_out, support = max(scale, 1),
+    centre = (x + 0.5) scale, window [max(int(centre - support + 0.5), 0), min(int(centre + support + 0.5), n_in)), triangle weights
+    of (tap - centre + 0.5) * (1 / support), normalised to sum 1."""
+    scale = n_in / n_out
+    fs = max(scale, 1.0)
+    support, ss = 1.0 * fs, 1.0 / fs
+    taps = int(np.ceil(support)) * 2 + 1
+    start, length = np.zeros(n_out, np.int32), np.zeros(n_out, np.int32)
+    weights = np.zeros((n_out, taps), np.float64)
+    for x in range(n_out):
+        centre = (x + 0.5) * scale
+        lo, hi = max(int(centre - support + 0.5), 0), min(int(centre + support + 0.5), n_in)
+        ww = 0.0
+        for t in range(hi - lo):
+            weights[x, t] = max(1.0 - abs((t + lo - centre + 0.5) * ss), 0.0)
+            ww += weights[x, t]
+        if ww != 0.0:
+            weights[x, :hi - lo] *= 1.0 / ww
+        start[x], length[x] = lo, hi - lo
+    return start, length, weights
+
+
+class StackingPreprocessor:
+    """The second-level loader (loaders.py:564-579, ImageSegmentationLoaderStacking) on the device.  Callable:
+    (stacks [B,h,w,M] or [B,M,h,w] fp32, masks [B,h,w] uint8 | None) on the GPU -> (X [B,M,H,W], target [B,2,H,W] | None).
+
+    X is ResizeArray + to_tensor_stacking (skimage's order-1 'constant' resize of every first-level map, float64, one rounding to
+    fp32: ``salt_stack_resize``); the target is the PIL BILINEAR resize of (mask == k), k in (0, 1), the two classes resized
+    independently (``salt_mask_resize``).  ``layout``: 'hwm' ([B,h,w,M], what np.stack(maps, axis=-1) per tile gives, utils.py:580),
+    'mhw' ([B,M,h,w] planes) or None = by shape (the last axis is M when it is the only one that differs from a square tile; ambiguous
+    shapes must say).  A depth-conditioned network takes D / 1000 beside X as before."""
+
+    def __init__(self, size=(128, 128), layout=None):
+        if layout not in (None, 'hwm', 'mhw'):
+            raise SaltError("StackingPreprocessor: layout %r ('hwm' | 'mhw' | None)" % (layout,))
+        self.size, self.layout = (int(size[0]), int(size[1])), layout
+        self._tables = {}
+
+    def _layout(self, shape):
+        if self.layout is not None:
+            return self.layout
+        _, a, b, c = shape
+        if a == b and b != c:
+            return 'hwm'
+        if b == c and a != b:
+            return 'mhw'
+        raise SaltError('StackingPreprocessor: cannot tell [B,h,w,M] from [B,M,h,w] for shape %s: pass layout=' % (tuple(shape),))
+
+    def tables(self, h, w, device):
+        """the per-axis PIL tables of (h, w) -> size on ``device``, built once"""
+        key = (h, w, str(device))
+        if key not in self._tables:
+            dev = []
+            for start, length, weights in (pil_resize_table(h, self.size[0]), pil_resize_table(w, self.size[1])):
+                dev.append((torch.from_numpy(start).to(device), torch.from_numpy(length).to(device), torch.from_numpy(weights).to(device)))
+            self._tables[key] = dev
+        return self._tables[key]
+
+    def __call__(self, stacks, masks=None):
+        if not torch.is_tensor(stacks) or not stacks.is_cuda or (masks is not None and (not torch.is_tensor(masks) or not masks.is_cuda)):
+            raise SaltError('StackingPreprocessor: tensors must live on the GPU (there is no CPU path)')
+        if stacks.dim() != 4 or stacks.dtype != torch.float32:
+            raise SaltError('StackingPreprocessor: stacks must be fp32 [B,h,w,M] or [B,M,h,w]')
+        stacks = stacks.contiguous()
+        B = stacks.shape[0]
+        if self._layout(stacks.shape) == 'hwm':
+            h, w, M = stacks.shape[1:]
+            strides = dict(sb=h * w * M, sr=w * M, sc=M, sm=1)
+        else:
+            M, h, w = stacks.shape[1:]
+            strides = dict(sb=M * h * w, sr=w, sc=1, sm=h * w)
+        if not 1 <= M <= 64:
+            raise SaltError('StackingPreprocessor: 1 <= M <= 64 first-level maps (got %d)' % M)
+        H, W = self.size
+        dev = stacks.device
+        stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+        x = torch.empty((B, M, H, W), dtype=torch.float32, device=dev)
+        fn, S = OP_FUNCS['salt_stack_resize']
+        check(fn(ctypes.byref(fill(S(), x=stacks.data_ptr(), B=B, h=h, w=w, M=M, H=H, W=W, y=x.data_ptr(), **strides)), stream), 'stack_resize')
+        if masks is None:
+            return x, None
+        if tuple(masks.shape) != (B, h, w):
+            raise SaltError('StackingPreprocessor: masks must be [B,h,w] like the maps')
+        masks = masks.contiguous().to(torch.uint8)
+        (rs, rl, rw), (cs, cl, cw) = self.tables(h, w, dev)
+        target = torch.empty((B, 2, H, W), dtype=torch.float32, device=dev)
+        fn, S = OP_FUNCS['salt_mask_resize']
+        check(fn(ctypes.byref(fill(S(), mask=masks.data_ptr(), B=B, h=h, w=w, H=H, W=W, row_start=rs.data_ptr(), row_len=rl.data_ptr(),
+                                   row_w=rw.data_ptr(), row_taps=rw.shape[1], col_start=cs.data_ptr(), col_len=cl.data_ptr(),
+                                   col_w=cw.data_ptr(), col_taps=cw.shape[1], target=target.data_ptr())), stream), 'mask_resize')
+        return x, target
 
 
 def emptiness_target(is_not_empty):

@@ -105,6 +105,7 @@ class Model:
         self.loss_function = None
         self.callbacks = None
         self.validation_loss = {}
+        self.validation_masks = None          # (loader_mode, original-size masks) set by ValidationMonitor.set_params, or None
 
     @property
     def output_names(self):
@@ -118,6 +119,8 @@ class Model:
         classifier network (``is_classifier``) is scored as {'sum', 'auc'} (callbacks.py:662-674)."""
         if getattr(self.model, 'is_classifier', False):
             return score_validation_emptiness(self, validation_datagen)
+        if self.validation_masks is not None:                 # loader modes 'resize' / 'stacking' with meta_valid masks
+            return score_validation(self, validation_datagen, loader_mode=self.validation_masks[0], y_true=self.validation_masks[1])
         return score_validation(self, validation_datagen)
 
     def persist(self, filepath):
