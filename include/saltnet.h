@@ -1206,6 +1206,72 @@ typedef struct {
 } salt_resize_iou_sweep_args;
 int salt_resize_iou_sweep(const salt_resize_iou_sweep_args*, void* stream);
 
+/* ------------------------------------------------------------------ ensembling between models (csrc/ensemble.hip)
+ * What the reference does with the predictions of several trained networks: main.py:892-912 (save_predictions: the mean over the
+ * cross-validation folds, binarized and run-length encoded), notebooks/prediction_average.ipynb (the same across experiments, in a
+ * float64 accumulator), utils.py:560-581 (channel 1 of every first-level model stacked with np.stack(axis=-1) for the second level).
+ *
+ * salt_ensemble: ONE pass over K member maps p_k, fp32 NCHW [B,C,H,W] each, up to three outputs.
+ *   the member's value at output pixel (y, x) of channel c:
+ *     mode 0 (postprocessing.crop_image):  v_k = p_k[b, c, top + y, left + x]                                   (the fp32 itself)
+ *     mode 1 (postprocessing.resize_image): v_k = BILINEAR64(p_k[b, c], r(y), c(x)), H x W -> h x w             (float64, never stored;
+ *                                           the same source text as salt_resize_prob: resize-each-then-mean, h <= H and w <= W)
+ *   the mean, members added in ASCENDING k, the accumulator starting at member 0 (np.mean(np.array(maps), axis=0)):
+ *     acc 0: s = v_0; s = fl32(s + v_k) for k = 1 .. K-1; mean = fl32(s / (float)K), one correctly rounded division;
+ *            mask = mean[cls] > (float)threshold
+ *     acc 1: the same in float64: s = (double)v_0; s = s + v_k; v = s / (double)K; mean = (float)v; mask = v[cls] > threshold,
+ *            decided on the float64 value as salt_resize_threshold decides
+ *   mode 1 with acc 0 is SALT_E_UNSUPPORTED (the reference's resized maps are float64).
+ *   the stack, no averaging: stack[b sb + y sr + x sc + (m0 + k) sm] = (float)v_k of channel cls
+ *     [B,h,w,M] (np.stack(maps, axis=-1), utils.py:580):              sb = h w M, sr = w M, sc = M, sm = 1
+ *     [B,M,h,w] (StackingPreprocessor(layout='mhw')):                 sb = M h w, sr = w,   sc = 1, sm = h w
+ *   with M >= m0 + K: a caller fills a slice of a wider stack, the other slots are not touched.
+ * Refused without a launch (SALT_E_BADARG): NULL args, K outside 1 .. SALT_MAX_MEMBERS, a NULL member, a window outside the map,
+ * an up-scale, cls outside [0, C), no output requested, a stack without positive strides. */
+#define SALT_MAX_MEMBERS 64
+typedef struct {
+    const float* const* members;  /* HOST array [K] of device pointers, each fp32 NCHW [B,C,H,W]; 1 <= K <= SALT_MAX_MEMBERS */
+    int K;
+    int B;
+    int C;
+    int H;
+    int W;
+    int mode;                 /* 0: crop window [top,top+h) x [left,left+w); 1: resize H x W -> h x w */
+    int top;
+    int left;
+    int h;
+    int w;
+    int acc;                  /* 0: fp32 accumulator, 1: float64 accumulator */
+    float* mean;              /* out fp32 [B,C,h,w] or NULL */
+    int cls;
+    double threshold;
+    uint8_t* mask;            /* out [B,h,w] in {0,1} or NULL */
+    float* stack;             /* out or NULL: member k's class-`cls` map at stack[b*sb + y*sr + x*sc + (m0+k)*sm] */
+    int64_t sb;
+    int64_t sr;
+    int64_t sc;
+    int64_t sm;
+    int m0;
+} salt_ensemble_args;
+int salt_ensemble(const salt_ensemble_args*, void* stream);
+
+/* salt_rle_encode: utils.run_length_encoding (utils.py:99-111) of a batch of masks.  Pixel p = x h + y (COLUMN-major, x.T.flatten());
+ * a run is a maximal range [s, e] of set positions (it continues from the bottom of a column into the top of the next); image b's
+ * runs, in ascending s, are the pairs (s + 1, e - s + 1).  counts[b] is their number; the pairs of all images are packed: image b's
+ * begin at pair index sum(counts[0 .. b)).  Two launches (count, then place at the exclusive prefix of counts), one 256-thread
+ * workgroup per image, no atomics: the output is deterministic. */
+typedef struct {
+    const uint8_t* mask;      /* [B,h,w], nonzero = set; 1 <= h*w <= 65536 */
+    int B;
+    int h;
+    int w;
+    int* counts;              /* out [B]: runs of image b */
+    int* runs;                /* out, packed pairs (start, length), start 1-based */
+    int64_t cap_pairs;        /* pairs `runs` holds; a pair whose packed index is >= cap_pairs is NOT written */
+    int64_t* total;           /* out [1]: sum(counts), also when it exceeds cap_pairs */
+} salt_rle_encode_args;
+int salt_rle_encode(const salt_rle_encode_args*, void* stream);
+
 /* ------------------------------------------------------------------ program executor
  * A training/inference step is a static list of the operators above.  The host builds it once per
  * (model, batch shape); running it is one call.  capture/replay wraps it in a hipGraph. */

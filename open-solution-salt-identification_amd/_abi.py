@@ -45,7 +45,7 @@ def _parse(src):
             line = ' '.join(line.split())
             if not line:
                 continue
-            fm = re.match(r'^(const\s+)?(\w+)\s*(\*+)?\s*(\w+)\s*(\[(\w+)\])?$', line)
+            fm = re.match(r'^(const\s+)?(\w+)\s*((?:\*\s*(?:const\b\s*)?)+)?\s*(\w+)\s*(\[(\w+)\])?$', line)      # `T* const* p` is a pointer too
             if not fm:
                 raise SaltError('saltnet.h: cannot parse field %r of %s' % (line, name))
             _, typ, ptr, fname, _, arr = fm.groups()

@@ -329,6 +329,8 @@ extern "C" int salt_abi_struct_sizes(int* out, int n) {
     (int)sizeof(salt_resize_prob_args),
     (int)sizeof(salt_resize_threshold_args),
     (int)sizeof(salt_resize_iou_sweep_args),
+    (int)sizeof(salt_ensemble_args),
+    (int)sizeof(salt_rle_encode_args),
     (int)sizeof(salt_program_entry),
     (int)sizeof(salt_pool_head_args),
     (int)sizeof(salt_pool_head_bwd_args),

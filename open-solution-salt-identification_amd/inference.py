@@ -171,7 +171,7 @@ def predict_tta(net, X, flip_ud=False, flip_lr=True, variants_per_pass=None, dep
 
 
 def predict_tta_tiles(net, preprocessor, images, flip_ud=False, flip_lr=True, rotation=False, method='mean', loader_mode='resize_and_pad',
-                      pad_method='edge', target_size=None):
+                      pad_method='edge', target_size=None, resize_back=True):
     """TTA exactly in the reference's order of operations: transform the RAW [B,h,w] tiles (augmentation.py:143-153: flipud, fliplr,
     rot90), preprocess every variant (inference pad + Normalize + AddDepthChannels), forward, inverse-transform the probability
     maps (augmentation.py:156-163) and aggregate (loaders.py:722-760).  ``rotation`` needs square tiles.
@@ -179,7 +179,8 @@ def predict_tta_tiles(net, preprocessor, images, flip_ud=False, flip_lr=True, ro
     ``loader_mode`` / ``pad_method`` must be the preprocessor's (a mismatch raises: the caller states the config once and this checks
     it).  In 'resize' mode every variant is scaled in by the preprocessor and the aggregate is brought back to ``target_size``
     (default: the tiles' own size) by resize_image; in 'resize_and_pad' mode ``target_size`` must stay None (the crop is
-    crop_threshold's)."""
+    crop_threshold's).  ``resize_back=False`` returns the aggregate at the network's size in 'resize' mode too: ensemble.FoldEnsemble
+    brings K of them back and averages them in one launch."""
     from .input_pipeline import LOADER_MODES, PAD_METHODS
     if loader_mode not in LOADER_MODES:
         raise SaltError('predict_tta_tiles: loader_mode %r (%s)' % (loader_mode, ' | '.join(LOADER_MODES)))
@@ -219,7 +220,7 @@ def predict_tta_tiles(net, preprocessor, images, flip_ud=False, flip_lr=True, ro
             logits[v * B:(v + 1) * B].copy_(lg)
     # sigmoid, inverse transform (rot90(-k), fliplr, flipud: augmentation.py:156-163) and aggregation of all variants: one kernel
     prob = tta_mean(logits, specs, B, method)
-    if loader_mode == 'resize':
+    if loader_mode == 'resize' and resize_back:
         return resize_image(prob, tuple(images.shape[1:]) if target_size is None else target_size)
     return prob
 
