@@ -822,6 +822,80 @@ typedef struct {
 int salt_bce_dice(const salt_bce_dice_args*, void* stream);
 int salt_bce_dice_parts(const salt_bce_dice_args*);
 
+/* ------------------------------------------------------------------ softmax head (model_params['activation'] = 'softmax')
+ * p = softmax over the C channels of every pixel of fp32 NCHW logits, the pixel's maximum subtracted first (logits of +-80 give
+ * finite results).  One thread per pixel, coalesced along HW; y may alias x.  2 <= C <= 4; anything else, a NULL pointer or
+ * B, HW < 1 is SALT_E_BADARG from host code, nothing is launched. */
+typedef struct {
+    const float* x;           /* logits [B,C,HW] */
+    float* y;                 /* probabilities [B,C,HW] */
+    int B;
+    int C;
+    int HW;
+} salt_softmax_args;
+int salt_softmax(const salt_softmax_args*, void* stream);
+
+/* Softmax Jacobian: dz_j = p_j (dp_j - sum_c p_c dp_c) per pixel.  dz may alias dp.  Same refusals as salt_softmax. */
+typedef struct {
+    const float* p;           /* probabilities [B,C,HW] (salt_softmax's output) */
+    const float* dp;          /* d loss / d p */
+    float* dz;                /* d loss / d logits */
+    int B;
+    int C;
+    int HW;
+} salt_softmax_bwd_args;
+int salt_softmax_bwd(const salt_softmax_bwd_args*, void* stream);
+
+/* Lovasz-softmax, lovasz_softmax(probas, labels, only_present=False, per_image=True, ignore=None) of lovasz_losses.py:173-210: for
+ * every image b and class c, e_i = |fg_i - p[b,c,i]| with fg_i = (target[b,c,i] > 0.5), sorted descending (stable: ties keep
+ * ascending pixel index), g = lovasz_grad(fg_sorted), L[b,c] = sum_k e_k g_k (no elu);  loss = loss_scale * mean of the B*C rows;
+ * dprobas[b,c,i] = (fg_i ? -1 : +1) g_rank(i) loss_scale / (B C), exactly 0 where e_i == 0.  A row (b,c) is a contiguous run of HW
+ * floats: the sort, the scan and the fp32 sequence of g are salt_lovasz_hinge's kernels with the absolute-error policy over
+ * B*C rows of HW elements (split form for HW >= 4096 when ws_split is given; gradients bit-identical to the unsplit form).
+ * `probas` may be any values in [0,1]; they need not sum to 1.  2 <= C <= 4, B, HW >= 1, else SALT_E_BADARG without a launch. */
+typedef struct {
+    const float* probas;      /* fp32 [B,C,HW] */
+    const float* target;      /* fp32 one-hot [B,C,HW] in {0,1} */
+    int B;
+    int C;
+    int HW;
+    uint32_t* ws_keys;        /* [2][B*C][HW] workspace */
+    uint32_t* ws_vals;        /* [2][B*C][HW] workspace */
+    float* loss_per_row;      /* [B*C] */
+    float* loss;              /* [1] */
+    float* dprobas;           /* fp32 [B,C,HW] or NULL (forward only) */
+    float loss_scale;
+    uint32_t* ws_split;       /* NULL, or [B*C * salt_lovasz_split_words(HW)] words */
+} salt_lovasz_softmax_args;
+int salt_lovasz_softmax(const salt_lovasz_softmax_args*, void* stream);
+
+/* Dice + cross entropy on softmax probabilities (the intent of mixed_dice_cross_entropy_loss, models.py:343-388), target one-hot
+ * WITH the background channel 0, y = argmax_c target (first maximum), N = B*HW, sums over the whole batch:
+ *   CE = -(1/N) sum log p[b,y,i] (as logsumexp - z_y);  for c = 1 .. C-1: I_c = sum p_c t_c, D_c = sum p_c + sum t_c + smooth + 1e-7,
+ *   dice_c = 1 - (2 I_c + smooth) / D_c;  loss = loss_scale (dice_weight mean_c dice_c + cross_entropy_weight CE).
+ * The reference function's channel arithmetic (target[:, class_nr] against output channel class_nr + 1) assumes a target without a
+ * background channel and is not reproduced.  A partial-sums pass (salt_bce_dice's parts-per-plane rule, one part = one image x one
+ * run of pixels), a fixed-order finalize in double, and a gradient pass through the softmax Jacobian (skipped when dlogits is
+ * NULL).  No floating-point atomics: reruns are bit-identical.  2 <= C <= 4, B, HW >= 1, else SALT_E_BADARG without a launch. */
+typedef struct {
+    const float* logits;      /* fp32 [B,C,HW] */
+    const float* target;      /* fp32 one-hot [B,C,HW] */
+    int B;
+    int C;
+    int HW;
+    float dice_weight;        /* reference default 0.5 */
+    float cross_entropy_weight; /* reference default 0.5 */
+    float smooth;             /* reference default 0 */
+    float* partials;          /* [nparts][3C+1] workspace: per class I, sum p, sum t; then the CE sum */
+    int nparts;               /* as returned by salt_dice_ce_parts */
+    float* sums;              /* [3C+1] workspace (kept for backward) */
+    float* loss;              /* [1] */
+    float* dlogits;           /* or NULL */
+    float loss_scale;
+} salt_dice_ce_args;
+int salt_dice_ce(const salt_dice_ce_args*, void* stream);
+int salt_dice_ce_parts(const salt_dice_ce_args*);
+
 /* ------------------------------------------------------------------ optimizer (models.py:74-75,289-297)
  * torch.optim.Adam with L2-in-gradient weight decay over one flat fp32 parameter buffer. */
 typedef struct {
@@ -888,6 +962,8 @@ typedef struct {
     const int* rot;           /* host array [V] or NULL: quarter turns k of the variant's forward np.rot90 (augmentation.py:143-153; H == W);
                                * the inverse applied here is rot90(-k), then fliplr, then flipud (augmentation.py:156-163) */
     int method;               /* aggregation over the variants (loaders.py:727-735): 0 mean, 1 max, 2 min, 3 gmean = exp(mean(log p)) */
+    int activation;           /* 0 (a zeroed struct): sigmoid of `logits`; 1: none, `logits` holds probabilities already (the softmax
+                               * head: salt_softmax over the [V*B,C,HW] logits first) */
 } salt_tta_mean_args;
 int salt_tta_mean(const salt_tta_mean_args*, void* stream);
 

@@ -34,13 +34,16 @@ class _NativeLoss(torch.autograd.Function):
     """Hand-written HIP loss kernels as differentiable torch functions of fp32 NCHW logits."""
 
     @staticmethod
-    def forward(ctx, logits, target, kind):
+    def forward(ctx, logits, target, kind, *weights):
+        """``weights``: nothing, or the (dice_weight, cross_entropy_weight, smooth) tuple of 'dice_ce'"""
         from . import losses
-        loss, dl = losses.native_loss(logits.detach(), target, kind, want_grad=True)
+        params = dict(zip(losses.DICE_CE_DEFAULTS, weights[0])) if weights else None
+        loss, dl = losses.native_loss(logits.detach(), target, kind, want_grad=True, params=params)
         ctx.save_for_backward(dl)
+        ctx.n_inputs = 3 + len(weights)
         return loss
 
     @staticmethod
     def backward(ctx, g):
         (dl,) = ctx.saved_tensors
-        return dl * g, None, None
+        return (dl * g,) + (None,) * (ctx.n_inputs - 1)

@@ -357,7 +357,7 @@ def score_validation(transformer, validation_datagen, target_size=(101, 101), us
                 target = data[1].to(dev)
                 logits = model(X)
             losses.append((loss_function(logits, target) * weight).detach().reshape(1))
-            prob = torch.sigmoid(logits.float())
+            prob = inference.class_probabilities(logits, getattr(transformer, 'activation_func', 'sigmoid'))
             if resized:
                 n = prob.shape[0]
                 if seen + n > y_true.shape[0]:

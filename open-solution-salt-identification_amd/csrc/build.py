@@ -16,7 +16,7 @@ ROOT = os.path.dirname(PKG)
 INC = os.path.join(ROOT, 'include')
 OBJ = os.path.join(HERE, '_obj')
 LIB = os.path.join(PKG, 'libsaltnet_hip.so')
-SOURCES = ['runtime.hip', 'conv_mfma.hip', 'conv_wgrad.hip', 'conv_ws.hip', 'conv_thin.hip', 'conv_wgrad_ls.hip', 'conv_small.hip', 'head_fused.hip', 'elementwise.hip', 'hyper.hip', 'se.hip', 'se_res.hip', 'conv_group.hip', 'dense.hip', 'psp.hip', 'gcn.hip', 'depth.hip', 'classifier.hip', 'stacking.hip', 'loss.hip', 'input.hip', 'augment.hip', 'resize.hip', 'ensemble.hip']
+SOURCES = ['runtime.hip', 'conv_mfma.hip', 'conv_wgrad.hip', 'conv_ws.hip', 'conv_thin.hip', 'conv_wgrad_ls.hip', 'conv_small.hip', 'head_fused.hip', 'elementwise.hip', 'hyper.hip', 'se.hip', 'se_res.hip', 'conv_group.hip', 'dense.hip', 'psp.hip', 'gcn.hip', 'depth.hip', 'classifier.hip', 'stacking.hip', 'loss.hip', 'loss_softmax.hip', 'input.hip', 'augment.hip', 'resize.hip', 'ensemble.hip']
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-I' + INC, '-I' + HERE, '-Wno-unused-value']
 
 
@@ -29,7 +29,7 @@ def _hipcc():
 
 def _digest(path):
     h = hashlib.sha1()
-    for p in [path, os.path.join(HERE, 'common.h'), os.path.join(HERE, 'preprocess_common.h'), os.path.join(HERE, 'resample64.h'), os.path.join(INC, 'saltnet.h')]:
+    for p in [path, os.path.join(HERE, 'common.h'), os.path.join(HERE, 'preprocess_common.h'), os.path.join(HERE, 'resample64.h'), os.path.join(HERE, 'loss_common.h'), os.path.join(INC, 'saltnet.h')]:
         with open(p, 'rb') as f:
             h.update(f.read())
     h.update(' '.join(FLAGS).encode())

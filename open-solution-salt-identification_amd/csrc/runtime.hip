@@ -20,7 +20,7 @@ void salt_set_error(const char* fmt, ...) {
 
 extern "C" const char* salt_last_error(void) { return g_err; }
 
-extern "C" int salt_abi_version(void) { return 33; }
+extern "C" int salt_abi_version(void) { return 34; }
 
 extern "C" int salt_device_info(int* cu_count, int* lds_bytes, char* arch_name, int arch_name_len) {
     int dev = 0;
@@ -313,6 +313,10 @@ extern "C" int salt_abi_struct_sizes(int* out, int n) {
     (int)sizeof(salt_channel_gate_args),
     (int)sizeof(salt_lovasz_args),
     (int)sizeof(salt_bce_dice_args),
+    (int)sizeof(salt_softmax_args),
+    (int)sizeof(salt_softmax_bwd_args),
+    (int)sizeof(salt_lovasz_softmax_args),
+    (int)sizeof(salt_dice_ce_args),
     (int)sizeof(salt_adam_args),
     (int)sizeof(salt_adam_pack_args),
     (int)sizeof(salt_adam_tick_args),

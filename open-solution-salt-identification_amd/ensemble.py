@@ -206,7 +206,8 @@ class FoldEnsemble:
     the reference's resize-each-then-mean."""
 
     def __init__(self, nets, preprocessor, flip_ud=False, flip_lr=True, rotation=False, method='mean', loader_mode='resize_and_pad',
-                 pad_method='edge', target_size=(101, 101)):
+                 pad_method='edge', target_size=(101, 101), activation='sigmoid'):
+        """``activation``: the members' model_params['activation'], 'sigmoid' (default) or 'softmax'; passed to predict_tta_tiles"""
         nets = list(nets)
         if not 1 <= len(nets) <= MAX_MEMBERS:
             raise SaltError('FoldEnsemble: 1 <= K <= %d networks (got %d)' % (MAX_MEMBERS, len(nets)))
@@ -218,7 +219,8 @@ class FoldEnsemble:
         if loader_mode not in ('resize_and_pad', 'resize'):
             raise SaltError("FoldEnsemble: loader_mode %r ('resize_and_pad' | 'resize')" % (loader_mode,))
         self.nets, self.preprocessor = nets, preprocessor
-        self.tta = dict(flip_ud=flip_ud, flip_lr=flip_lr, rotation=rotation, method=method, loader_mode=loader_mode, pad_method=pad_method)
+        self.tta = dict(flip_ud=flip_ud, flip_lr=flip_lr, rotation=rotation, method=method, loader_mode=loader_mode, pad_method=pad_method,
+                        activation=activation)
         self.loader_mode, self.target_size = loader_mode, (int(target_size[0]), int(target_size[1]))
 
     def members(self, images):

@@ -68,12 +68,32 @@ def flip(x, ud, lr, out=None):
 
 
 TTA_METHODS = {'mean': 0, 'max': 1, 'min': 2, 'gmean': 3}
+ACTIVATIONS = ('sigmoid', 'softmax')
 
 
-def tta_mean(logits, variants, batch, method='mean'):
-    """sigmoid -> inverse transform -> aggregation over the variants in ONE kernel; ``logits`` is variant-major [V*B, C, H, W];
+def _activation(activation):
+    if activation not in ACTIVATIONS:
+        raise SaltError('activation %r (%s)' % (activation, ' | '.join(ACTIVATIONS)))
+    return activation
+
+
+def class_probabilities(logits, activation='sigmoid'):
+    """Class probabilities [B,C,H,W] (fp32) of a network's logits, as the model's ``activation`` defines them (models.py:143-150):
+    'sigmoid' per channel, 'softmax' over the channels of every pixel (salt_softmax; 2 .. 4 channels)."""
+    if _activation(activation) == 'sigmoid':
+        return torch.sigmoid(logits.float())
+    logits = _f32c(logits)
+    B, C, H, W = logits.shape
+    prob = torch.empty_like(logits)
+    _run('softmax', x=logits.data_ptr(), y=prob.data_ptr(), B=B, C=C, HW=H * W)
+    return prob
+
+
+def tta_mean(logits, variants, batch, method='mean', activation='sigmoid'):
+    """activation -> inverse transform -> aggregation over the variants; ``logits`` is variant-major [V*B, C, H, W];
     ``variants``: (ud, lr) or (ud, lr, k) with k the quarter turns of the variant's np.rot90 (square maps); ``method``: mean (default,
-    neptune.yaml:80) | max | min | gmean (loaders.py:727-735)."""
+    neptune.yaml:80) | max | min | gmean (loaders.py:727-735).  ``activation`` 'sigmoid' (default) is evaluated inside the ONE
+    aggregation kernel; 'softmax' is a salt_softmax pass over all variants in front of the same kernel in its no-activation mode."""
     logits = _f32c(logits)
     VB, C, H, W = logits.shape
     V = len(variants)
@@ -81,13 +101,15 @@ def tta_mean(logits, variants, batch, method='mean'):
         raise SaltError('tta_mean: %d logits for %d variants x batch %d' % (VB, V, batch))
     if method not in TTA_METHODS:
         raise SaltError('TTA aggregation %r (mean | max | min | gmean, loaders.py:727-735)' % (method,))
+    if _activation(activation) == 'softmax':
+        logits = class_probabilities(logits, 'softmax')
     ud = (ctypes.c_int * V)(*[int(v[0]) for v in variants])
     lr = (ctypes.c_int * V)(*[int(v[1]) for v in variants])
     rot = (ctypes.c_int * V)(*[int(v[2]) if len(v) > 2 else 0 for v in variants])
     prob = torch.empty((batch, C, H, W), dtype=torch.float32, device=logits.device)
     _run('tta_mean', logits=logits.data_ptr(), V=V, B=batch, C=C, H=H, W=W, flip_ud=ctypes.cast(ud, ctypes.c_void_p).value,
          flip_lr=ctypes.cast(lr, ctypes.c_void_p).value, prob=prob.data_ptr(), rot=ctypes.cast(rot, ctypes.c_void_p).value,
-         method=TTA_METHODS[method])
+         method=TTA_METHODS[method], activation=1 if activation == 'softmax' else 0)
     return prob
 
 
@@ -124,7 +146,8 @@ def _looks_like_depth_channels(X):
     return bool(ok.item())
 
 
-def predict_tta(net, X, flip_ud=False, flip_lr=True, variants_per_pass=None, depth_channels=None, method='mean', depth=None):
+def predict_tta(net, X, flip_ud=False, flip_lr=True, variants_per_pass=None, depth_channels=None, method='mean', depth=None,
+                activation='sigmoid'):
     """Probabilities [B, C, H, W] of an eval-mode HipNetwork aggregated over the flip variants (reference default main.py:282-285:
     left-right only; BASELINE C4's "4-flip" is flip_ud=True, flip_lr=True).  ``depth_channels``: the input is the reference's
     3-channel [gray, depth ramp, gray*ramp] batch, whose channels 1 / 2 an up-down flip must rebuild rather than flip (see
@@ -133,7 +156,7 @@ def predict_tta(net, X, flip_ud=False, flip_lr=True, variants_per_pass=None, dep
     ``method``: 'mean' (default, neptune.yaml:80; one fused kernel) or 'max' / 'min' / 'gmean' (loaders.py:727-735).
 
     ``depth``: the tiles' depths [B,1] of a depth-conditioned network (UNetResNetWithDepth); a flip does not change a tile's depth, so
-    every variant runs with the same values.
+    every variant runs with the same values.  ``activation``: the model's, 'sigmoid' (default) or 'softmax' (see tta_mean).
 
     The variants are forwarded ``variants_per_pass`` at a time as one larger batch (default: all of them).  For bit-faithful
     handling of the asymmetric 13/14 edge pad use :func:`predict_tta_tiles`, which flips the raw tiles like the reference."""
@@ -167,11 +190,11 @@ def predict_tta(net, X, flip_ud=False, flip_lr=True, variants_per_pass=None, dep
                 if logits is None:
                     logits = torch.empty((V * B,) + tuple(lg.shape[1:]), dtype=torch.float32, device=X.device)
                 logits[i * B:(i + len(group)) * B].copy_(lg)
-    return tta_mean(logits, variants, B, method)
+    return tta_mean(logits, variants, B, method, activation)
 
 
 def predict_tta_tiles(net, preprocessor, images, flip_ud=False, flip_lr=True, rotation=False, method='mean', loader_mode='resize_and_pad',
-                      pad_method='edge', target_size=None, resize_back=True):
+                      pad_method='edge', target_size=None, resize_back=True, activation='sigmoid'):
     """TTA exactly in the reference's order of operations: transform the RAW [B,h,w] tiles (augmentation.py:143-153: flipud, fliplr,
     rot90), preprocess every variant (inference pad + Normalize + AddDepthChannels), forward, inverse-transform the probability
     maps (augmentation.py:156-163) and aggregate (loaders.py:722-760).  ``rotation`` needs square tiles.
@@ -180,8 +203,9 @@ def predict_tta_tiles(net, preprocessor, images, flip_ud=False, flip_lr=True, ro
     it).  In 'resize' mode every variant is scaled in by the preprocessor and the aggregate is brought back to ``target_size``
     (default: the tiles' own size) by resize_image; in 'resize_and_pad' mode ``target_size`` must stay None (the crop is
     crop_threshold's).  ``resize_back=False`` returns the aggregate at the network's size in 'resize' mode too: ensemble.FoldEnsemble
-    brings K of them back and averages them in one launch."""
+    brings K of them back and averages them in one launch.  ``activation``: the model's, 'sigmoid' (default) or 'softmax'."""
     from .input_pipeline import LOADER_MODES, PAD_METHODS
+    _activation(activation)
     if loader_mode not in LOADER_MODES:
         raise SaltError('predict_tta_tiles: loader_mode %r (%s)' % (loader_mode, ' | '.join(LOADER_MODES)))
     if pad_method not in PAD_METHODS:
@@ -218,8 +242,8 @@ def predict_tta_tiles(net, preprocessor, images, flip_ud=False, flip_lr=True, ro
             if logits is None:
                 logits = torch.empty((len(specs) * B,) + tuple(lg.shape[1:]), dtype=torch.float32, device=lg.device)
             logits[v * B:(v + 1) * B].copy_(lg)
-    # sigmoid, inverse transform (rot90(-k), fliplr, flipud: augmentation.py:156-163) and aggregation of all variants: one kernel
-    prob = tta_mean(logits, specs, B, method)
+    # activation, inverse transform (rot90(-k), fliplr, flipud: augmentation.py:156-163) and aggregation of all variants
+    prob = tta_mean(logits, specs, B, method, activation)
     if loader_mode == 'resize' and resize_back:
         return resize_image(prob, tuple(images.shape[1:]) if target_size is None else target_size)
     return prob

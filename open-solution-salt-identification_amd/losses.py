@@ -2,8 +2,10 @@
 
   lovasz_loss          <- models.py:326-328  (lovasz_losses.py:81-115, per-image, F.elu variant)
   mixed_dice_bce_loss  <- models.py:331-340  (defaults dice 0.2 / bce 0.9, sigmoid dice, batch-wide sums)
+  lovasz_softmax_loss  <- lovasz_losses.py:173-210 (per image, all classes) on softmax(logits); 2 .. 4 channels
+  mixed_dice_cross_entropy_loss <- models.py:343-388 (defaults dice 0.5 / cross entropy 0.5; target WITH its background channel)
 
-Both accept what the reference passes (fp32 logits [B,C,H,W], float one-hot target [B,C,H,W]) and return
+All accept what the reference passes (fp32 logits [B,C,H,W], float one-hot target [B,C,H,W]) and return
 a differentiable 0-dim tensor.  They run only on GPU tensors; there is no CPU fallback."""
 import ctypes
 
@@ -22,7 +24,20 @@ def _workspace(key, n, dtype, device):
     return t
 
 
-def native_loss(logits, target, kind, want_grad=True, loss_scale=1.0):
+DICE_CE_DEFAULTS = {'dice_weight': 0.5, 'cross_entropy_weight': 0.5, 'smooth': 0.0}       # models.py:343
+
+
+def dice_ce_params(params):
+    """(dice_weight, cross_entropy_weight, smooth) of a 'dice_ce' loss from a dict that may name any of them (None: the defaults)"""
+    params = dict(params or {})
+    unknown = set(params) - set(DICE_CE_DEFAULTS)
+    if unknown:
+        raise SaltError('dice_ce: unknown loss parameter(s) %s (%s)' % (sorted(unknown), ' | '.join(DICE_CE_DEFAULTS)))
+    return tuple(float(params.get(k, v)) for k, v in DICE_CE_DEFAULTS.items())
+
+
+def native_loss(logits, target, kind, want_grad=True, loss_scale=1.0, params=None):
+    """``params``: the weights of 'dice_ce' (see dice_ce_params); the other kinds take none."""
     if logits.device.type != 'cuda':
         raise SaltError('native losses run on the GPU only (got %s)' % logits.device)
     logits = logits.contiguous().float()
@@ -58,6 +73,41 @@ def native_loss(logits, target, kind, want_grad=True, loss_scale=1.0):
         fill(a, logits=logits.data_ptr(), target=target.data_ptr(), dice_weight=0.2, bce_weight=0.9, partials=parts.data_ptr(), nparts=nparts,
              sums=sums.data_ptr(), loss=loss.data_ptr(), dlogits=dl.data_ptr() if want_grad else None, loss_scale=loss_scale)
         check(lib.salt_bce_dice(ctypes.byref(a), st), 'bce_dice')
+    elif kind == 'lovasz_softmax':
+        # softmax -> row loss (gradient with respect to the probabilities into a workspace) -> softmax Jacobian into dlogits
+        HW = H * W
+        sid = torch.cuda.current_stream().cuda_stream
+        wk = _workspace(('k', dev, sid), 2 * B * C * HW, torch.int32, dev)
+        wv = _workspace(('v', dev, sid), 2 * B * C * HW, torch.int32, dev)
+        probas = _workspace(('p', dev, sid), B * C * HW, torch.float32, dev)
+        lpr = torch.empty(B * C, dtype=torch.float32, device=dev)
+        sw = int(lib.salt_lovasz_split_words(HW))
+        ws = _workspace(('s', dev, sid), B * C * sw, torch.int32, dev) if sw else None
+        a = STRUCTS['salt_softmax_args']()
+        fill(a, x=logits.data_ptr(), y=probas.data_ptr(), B=B, C=C, HW=HW)
+        check(lib.salt_softmax(ctypes.byref(a), st), 'softmax')
+        a = STRUCTS['salt_lovasz_softmax_args']()
+        fill(a, probas=probas.data_ptr(), target=target.data_ptr(), B=B, C=C, HW=HW, ws_keys=wk.data_ptr(), ws_vals=wv.data_ptr(),
+             loss_per_row=lpr.data_ptr(), loss=loss.data_ptr(), dprobas=dl.data_ptr() if want_grad else None, loss_scale=loss_scale,
+             ws_split=ws.data_ptr() if ws is not None else None)
+        check(lib.salt_lovasz_softmax(ctypes.byref(a), st), 'lovasz_softmax')
+        if want_grad:
+            a = STRUCTS['salt_softmax_bwd_args']()
+            fill(a, p=probas.data_ptr(), dp=dl.data_ptr(), dz=dl.data_ptr(), B=B, C=C, HW=HW)        # in place: dprobas -> dlogits
+            check(lib.salt_softmax_bwd(ctypes.byref(a), st), 'softmax_bwd')
+    elif kind == 'dice_ce':
+        dw, cw, smooth = dice_ce_params(params)
+        a = STRUCTS['salt_dice_ce_args']()
+        fill(a, B=B, C=C, HW=H * W)
+        nparts = lib.salt_dice_ce_parts(ctypes.byref(a))
+        if nparts < 1:
+            raise SaltError('dice_ce: %d output channels (the softmax losses take 2 .. 4)' % C)
+        parts = torch.empty(nparts * (3 * C + 1), dtype=torch.float32, device=dev)
+        sums = torch.empty(3 * C + 1, dtype=torch.float32, device=dev)
+        fill(a, logits=logits.data_ptr(), target=target.data_ptr(), dice_weight=dw, cross_entropy_weight=cw, smooth=smooth,
+             partials=parts.data_ptr(), nparts=nparts, sums=sums.data_ptr(), loss=loss.data_ptr(),
+             dlogits=dl.data_ptr() if want_grad else None, loss_scale=loss_scale)
+        check(lib.salt_dice_ce(ctypes.byref(a), st), 'dice_ce')
     else:
         raise SaltError('unknown loss %r' % kind)
     return loss[0], dl
@@ -75,5 +125,28 @@ def mixed_dice_bce_loss(output, target, dice_weight=0.2, dice_loss=None, bce_wei
     return _NativeLoss.apply(output, target, 'bce_dice')
 
 
+def lovasz_softmax_loss(output, target):
+    """lovasz_softmax(softmax(output), labels, only_present=False, per_image=True, ignore=None) of lovasz_losses.py:173-210 on logits
+    [B,C,H,W] and the one-hot target [B,C,H,W] (channel 0 the background), 2 <= C <= 4: mean over the B*C (image, class) rows."""
+    from .autograd import _NativeLoss
+    return _NativeLoss.apply(output, target, 'lovasz_softmax')
+
+
+def mixed_dice_cross_entropy_loss(output, target, dice_weight=0.5, dice_loss=None, cross_entropy_weight=0.5, cross_entropy_loss=None, smooth=0,
+                                  dice_activation='softmax'):
+    """dice_weight * mean over the foreground classes of the soft Dice loss of softmax(output) + cross_entropy_weight * cross entropy
+    (models.py:343-388), batch-wide sums, on logits [B,C,H,W] and the one-hot target [B,C,H,W] WITH its background channel 0.
+
+    The reference function pairs ``target[:, class_nr]`` with output channel ``class_nr + 1`` (models.py:346-351), which assumes a target
+    without a background channel; with this project's [background, foreground] targets that would swap the classes, so it is not
+    reproduced: class c of the output is compared with channel c of the target, and the label is the target's argmax."""
+    if dice_activation != 'softmax' or dice_loss is not None or cross_entropy_loss is not None:
+        raise NotImplementedError('only the softmax Dice + cross entropy pair has a HIP kernel')
+    from .autograd import _NativeLoss
+    return _NativeLoss.apply(output, target, 'dice_ce', (float(dice_weight), float(cross_entropy_weight), float(smooth)))
+
+
 lovasz_loss.native_kind = 'lovasz'
 mixed_dice_bce_loss.native_kind = 'bce_dice'
+lovasz_softmax_loss.native_kind = 'lovasz_softmax'
+mixed_dice_cross_entropy_loss.native_kind = 'dice_ce'

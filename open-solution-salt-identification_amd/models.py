@@ -12,6 +12,8 @@ parameter buffers), the optimizer is one fused Adam kernel, ``_fit_loop`` runs f
 ``nn.DataParallel`` (models.py:81-85) is replaced by one process per GPU (parallel.py).
 """
 
+import functools
+
 import numpy as np
 import torch
 
@@ -19,7 +21,7 @@ from . import architectures as A
 from . import parallel
 from . import switches
 from ._abi import SaltError
-from .losses import lovasz_loss, mixed_dice_bce_loss
+from .losses import dice_ce_params, lovasz_loss, lovasz_softmax_loss, mixed_dice_bce_loss, mixed_dice_cross_entropy_loss
 from .optim import FusedAdam, weight_regularization
 
 ARCHITECTURES = {
@@ -103,6 +105,7 @@ class Model:
         self.model = None
         self.optimizer = None
         self.loss_function = None
+        self.loss_params = None               # weights of the 'dice_ce' loss (model_params['loss_params']): set_loss writes, _fused_step reads
         self.callbacks = None
         self.validation_loss = {}
         self.validation_masks = None          # (loader_mode, original-size masks) set by ValidationMonitor.set_params, or None
@@ -172,8 +175,28 @@ class SegmentationModel(Model):
         self._initialize_model_weights = lambda: None
 
     def set_loss(self):
+        mp = self.architecture_config['model_params']
+        self.loss_params = None
         if self.activation_func == 'softmax':
-            raise NotImplementedError('No softmax loss defined')
+            if getattr(self.model, 'is_classifier', False):
+                raise SaltError('%s is a classifier: its emptiness path (pooled head, ROC-AUC validation) is sigmoid-only' % mp['architecture'])
+            choices = {'lovasz_softmax': lovasz_softmax_loss, 'dice_ce': mixed_dice_cross_entropy_loss}
+            if 'loss' not in mp:
+                # the reference defines no softmax loss either (models.py:174-176); nothing is chosen on the user's behalf
+                raise NotImplementedError("No softmax loss defined: name one in model_params['loss'] (%s)" % ' | '.join(choices))
+            name = mp['loss']
+            if name not in choices:
+                raise SaltError("activation 'softmax' trains with loss %s, got %r" % (' | '.join(choices), name))
+            if not 2 <= mp['out_channels'] <= 4:
+                raise SaltError('the softmax losses take 2 .. 4 output channels, got %d' % mp['out_channels'])
+            loss_function = choices[name]
+            if name == 'dice_ce' and mp.get('loss_params'):
+                # optional weights of Dice + cross entropy: dice_weight / cross_entropy_weight / smooth.  The fused step reads them
+                # from here (they are part of the loss program's cache key); the same values reach the autograd-bridge path
+                dice_ce_params(mp['loss_params'])
+                self.loss_params = dict(mp['loss_params'])
+                loss_function = functools.partial(mixed_dice_cross_entropy_loss, **self.loss_params)
+                loss_function.native_kind = 'dice_ce'
         elif self.activation_func == 'sigmoid':
             name = self.architecture_config['model_params'].get('loss', 'lovasz')
             loss_function = {'lovasz': lovasz_loss, 'bce_dice': mixed_dice_bce_loss}[name]
@@ -236,6 +259,7 @@ class SegmentationModel(Model):
     def _fused_step(self, X, target, kind, weight, D=None):
         """``D``: the depth input [B,1] of a depth-conditioned network (SegmentationModelWithDepth), fp32 on X's device."""
         eng = self.model.engine(X.device)
+        eng.loss_params = self.loss_params
         # 'first step of a shape ran eagerly' is remembered ON the engine (a rebuilt engine starts empty - no recycled id() can skip it)
         if self.step_graph and not self.dp._active() and (tuple(X.shape), kind) in eng.eager_done:
             # the whole step (pack, forward, loss, backward, Adam; both streams) replayed as ONE hipGraph launch (the first step of

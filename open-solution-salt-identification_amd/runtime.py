@@ -18,6 +18,7 @@ import torch
 from . import _abi
 from ._abi import SaltError, lib
 from .engine import Graph, Program, DT_CODE, TORCH_DT
+from .losses import dice_ce_params
 
 
 def _require_gpu(device):
@@ -119,8 +120,13 @@ class CompiledNet:
         return (t.dtype == buf.dtype and tuple(t.shape) == tuple(buf.shape) and t.is_contiguous() and t.device == buf.device
                 and t.data_ptr() % 16 == 0)
 
+    def loss_key(self, kind, loss_scale):
+        """Cache key of a loss program (and of a captured step that contains it): the kind, the scale, and for 'dice_ce' the weights
+        the engine holds (Engine.loss_params, from model_params['loss_params'])."""
+        return (kind, float(loss_scale)) + (dice_ce_params(self.engine.loss_params) if kind == 'dice_ce' else ())
+
     def loss_program(self, kind, loss_scale):
-        key = (kind, float(loss_scale))
+        key = self.loss_key(kind, loss_scale)
         if key in self._loss_progs:
             return self._loss_progs[key]
         g = self.g
@@ -144,6 +150,33 @@ class CompiledNet:
             p.add('bce_dice', logits=self.logits.data_ptr(), target=self.target.data_ptr(), B=B, C=K, HW=H * W, dice_weight=0.2, bce_weight=0.9,
                   partials=parts.data_ptr(), nparts=nparts, sums=sums.data_ptr(), loss=self.loss.data_ptr(), dlogits=self.dlogits.data_ptr(),
                   loss_scale=loss_scale)
+        elif kind == 'lovasz_softmax':
+            # softmax -> rows (b, c) of H*W probabilities through the hinge's sort with the absolute-error policy, d loss / d probas
+            # into dlogits -> softmax Jacobian in place
+            HW = H * W
+            probas = g.alloc((B, K, HW), torch.float32, zero=False)
+            wk = g.alloc((2, B * K, HW), torch.int32, zero=False)
+            wv = g.alloc((2, B * K, HW), torch.int32, zero=False)
+            rows = g.alloc((B * K,), torch.float32)
+            sw = int(lib.salt_lovasz_split_words(HW))
+            ws = g.alloc((B * K * sw,), torch.int32, zero=False) if sw else None
+            p.add('softmax', x=self.logits.data_ptr(), y=probas.data_ptr(), B=B, C=K, HW=HW)
+            p.add('lovasz_softmax', probas=probas.data_ptr(), target=self.target.data_ptr(), B=B, C=K, HW=HW, ws_keys=wk.data_ptr(),
+                  ws_vals=wv.data_ptr(), loss_per_row=rows.data_ptr(), loss=self.loss.data_ptr(), dprobas=self.dlogits.data_ptr(),
+                  loss_scale=loss_scale, ws_split=ws.data_ptr() if ws is not None else None)
+            p.add('softmax_bwd', p=probas.data_ptr(), dp=self.dlogits.data_ptr(), dz=self.dlogits.data_ptr(), B=B, C=K, HW=HW)
+        elif kind == 'dice_ce':
+            dw, cw, smooth = key[2:]
+            S = _abi.STRUCTS['salt_dice_ce_args']()
+            _abi.fill(S, B=B, C=K, HW=H * W)
+            nparts = lib.salt_dice_ce_parts(ctypes.byref(S))
+            if nparts < 1:
+                raise SaltError('dice_ce: %d output channels (the softmax losses take 2 .. 4)' % K)
+            parts = g.alloc((nparts * (3 * K + 1),), torch.float32)
+            sums = g.alloc((3 * K + 1,), torch.float32)
+            p.add('dice_ce', logits=self.logits.data_ptr(), target=self.target.data_ptr(), B=B, C=K, HW=H * W, dice_weight=dw,
+                  cross_entropy_weight=cw, smooth=smooth, partials=parts.data_ptr(), nparts=nparts, sums=sums.data_ptr(),
+                  loss=self.loss.data_ptr(), dlogits=self.dlogits.data_ptr(), loss_scale=loss_scale)
         else:
             raise SaltError('unknown native loss %r' % kind)
         p.finalize()
@@ -177,6 +210,7 @@ class Engine:
         self._graph_stream = None       # capture / replay stream of the step graphs: step_graph creates it, run_step_graph reads
         self._pack_fork = None          # (pack program, one-entry side-stream program) cached by _pack_fork_entries
         self.eager_done = set()          # (shape, loss kind) whose first training step already ran eagerly (models.SegmentationModel._fused_step)
+        self.loss_params = None          # weights of the 'dice_ce' loss programs (model_params['loss_params']): SegmentationModel._fused_step writes, CompiledNet.loss_key reads
 
     # ------------------------------------------------------------------ flat parameter storage
     def _flatten(self):
@@ -417,7 +451,7 @@ class Engine:
         # the cache lives ON the compiled instance (which this engine owns) and holds the optimizer object itself: a rebuilt engine /
         # net / optimizer can never alias a stale executable through a recycled id()
         cache = net.__dict__.setdefault('_step_graphs', {})
-        key = (kind, float(loss_scale))
+        key = net.loss_key(kind, loss_scale)
         if self._pack_batched_n != len(self._pack_ops):
             self._build_pack_batch()
         hit = cache.get(key)
