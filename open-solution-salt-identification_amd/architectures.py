@@ -1055,10 +1055,10 @@ class UNetResNetWithDepth(UNetResNet):
         self.depth_channel_excitation = DepthChannelExcitation((5 if use_hypercolumn else 1) * self.bottom // 8)
 
     def emit(self, g, x_nchw, logits):
-        if getattr(g, 'd', None) is None:
+        if 'd' not in g.step_inputs:
             raise SaltError('UNetResNetWithDepth needs the graph\'s depth input (CompiledNet allocates it)')
         # first operator of the main stream: the side-stream level gates and the in-place gate of dec1 are all ordered behind it
-        self._gate = g.depth_gate(g.d, self.depth_channel_excitation.fc[0])
+        self._gate = g.depth_gate(g.step_inputs['d'], self.depth_channel_excitation.fc[0])
         try:
             super().emit(g, x_nchw, logits)
         finally:
@@ -1162,9 +1162,9 @@ class StackingFCNWithDepth(StackingFCN):
         self.depth_channel_excitation = DepthChannelExcitation(filter_nr)
 
     def _gate(self, g):
-        if getattr(g, 'd', None) is None:
+        if 'd' not in g.step_inputs:
             raise SaltError('StackingFCNWithDepth needs the graph\'s depth input (CompiledNet allocates it)')
-        return g.depth_gate(g.d, self.depth_channel_excitation.fc[0])
+        return g.depth_gate(g.step_inputs['d'], self.depth_channel_excitation.fc[0])
 
 
 class TernausUNetResNet(HipNetwork):

@@ -94,6 +94,18 @@ class Scratch:
         self.name, self.nbytes = name, int(nbytes)
 
 
+# The address of a step input (``key`` = 'x' | 'd' | 'target' | 'loss') plus a byte offset.  A field given one is filled with the static
+# buffer's address ``ptr`` (+ offset) and recorded in Program.slots, which CompiledNet.bind re-points at the caller's tensor.
+StepInput = namedtuple('StepInput', 'key ptr offset', defaults=(0,))
+
+
+def set_path(struct, path, value):
+    """struct.<path[0]>. ... .<path[-1]> = value (``path`` names the nested argument structs on the way, e.g. (field, 'p') of a view)"""
+    for a in path[:-1]:
+        struct = getattr(struct, a)
+    setattr(struct, path[-1], value)
+
+
 class Program:
     """A flat list of (operator, argument struct) pairs executed by salt_program_run."""
 
@@ -104,6 +116,7 @@ class Program:
         self.join_next = False
         self.streams = []      # 0 main / 1 side, per op
         self.patches = []      # (struct, path, Scratch)
+        self.slots = {}        # step-input key -> [(struct, path, byte offset)]: set_fields writes, CompiledNet.bind re-points them
         self._entries = None
         self.marks = {}
         self._pre_run = None           # callable(stream, begin) run before the entries are issued (Graph.finalize: shard hygiene)
@@ -118,28 +131,25 @@ class Program:
             if stream == 0 and self.join_next:
                 stream, self.join_next = 2, False
         self.streams.append(stream)
-        plain = {}
-        for k, v in fields.items():
-            if isinstance(v, Scratch):
-                self.patches.append((s, (k,), v))
-            elif isinstance(v, tuple) and len(v) == 2 and isinstance(v[1], Scratch):   # (view, scratch) -> view.p patched
-                plain[k] = v[0]
-                self.patches.append((s, (k, 'p'), v[1]))
-            else:
-                plain[k] = v
-        fill(s, **plain)
+        self.set_fields(s, **fields)
         self.ops.append((opname, fn, s))
         return s
 
-    def set_fields(self, s, **fields):
-        """Set more fields of an argument struct that ``add`` returned (same conventions: Scratch values are patched at finalize)."""
-        plain = {}
+    def set_fields(self, s, /, **fields):
+        """Set fields of an argument struct of this program.  A Scratch value is patched in at finalize, a StepInput value is the static
+        address now and a recorded slot; either may come as (view, value) for the view's pointer ``p``."""
         for k, v in fields.items():
+            path = (k,)
+            if isinstance(v, tuple) and len(v) == 2 and isinstance(v[1], (Scratch, StepInput)):
+                fill(s, **{k: v[0]})
+                v, path = v[1], (k, 'p')
             if isinstance(v, Scratch):
-                self.patches.append((s, (k,), v))
+                self.patches.append((s, path, v))
+            elif isinstance(v, StepInput):
+                self.slots.setdefault(v.key, []).append((s, path, v.offset))
+                set_path(s, path, v.ptr + v.offset)
             else:
-                plain[k] = v
-        fill(s, **plain)
+                fill(s, **{k: v})
 
     def mark(self, label):
         self.marks[label] = len(self.ops)
@@ -148,6 +158,8 @@ class Program:
         self.ops.extend(other.ops)
         self.streams.extend(other.streams)
         self.patches.extend(other.patches)
+        for key, slots in other.slots.items():
+            self.slots.setdefault(key, []).extend(slots)
         self._entries = None
 
     def finalize(self):
@@ -413,6 +425,7 @@ class Graph:
         self.dlogits = None            # fp32 NCHW dL/d(logits): head / _head_bn / pool_head / to_nchw write, CompiledNet and the backward emitters read
         self.n_folded = 0              # affine_acts dropped by _resolve_lazies (tests, tools/fwd_fold_probe.py)
         self._shard_state = None       # {'dirty', 'rezeroed'} of the backward statistics shards: finalize writes, its run hooks and the tests read
+        self.step_inputs = {}          # 'x' | 'd' -> static input tensor of the instance: CompiledNet writes, _in and the depth networks' emit read
         # fp64 statistics shards of the train-mode BatchNorm layers (SALT_BN_FIN=2): slices of one arena per program, cleared by ONE
         # salt_zero at the head of the program
         self._fin_bytes = {'fwd': 0, 'bwd': 0}
@@ -450,6 +463,14 @@ class Graph:
     def f32(self, n):
         return self.alloc((max(int(n), 1),), torch.float32)
 
+    def _in(self, t):
+        """Address of a network input: a step input of the instance as a recorded slot (CompiledNet.bind re-points it at the caller's
+        batch), any other tensor - the tests' harness and the tools emit on tensors of their own - as its plain address."""
+        for key, buf in self.step_inputs.items():
+            if buf is t:
+                return StepInput(key, t.data_ptr())
+        return t.data_ptr()
+
     def finalize(self):
         for buf, reads in self._virtual_acts:
             if buf.reads != reads:
@@ -462,10 +483,7 @@ class Graph:
             self.scratch[name] = self.alloc((_round_up(max(nb, 16), 16),), torch.uint8, zero=False)
         for prog in (self.fwd, self.bwd):
             for s, path, sc in prog.patches:
-                obj = s
-                for a in path[:-1]:
-                    obj = getattr(obj, a)
-                setattr(obj, path[-1], self.scratch[sc.name].data_ptr())
+                set_path(s, path, self.scratch[sc.name].data_ptr())
             prog.finalize()
         # ONE arena for the fp64 statistics shards of both programs, cleared by ONE salt_zero at the head of the FORWARD program (a
         # training step runs forward -> loss -> backward exactly once each; the backward program's own clear - a 6 us launch at the
@@ -836,7 +854,7 @@ class Graph:
             pad_mode, OH, OW = 0, (x.H + 2 * py - KH) // stride + 1, (x.W + 2 * px - KW) // stride + 1
         tk = [(t[0], t[1]) for t in taps]
         td = [(t[2], t[3]) for t in taps]
-        pk = eng.packed(conv, tk, transposed=False)
+        pk = eng.packs.dense(conv, tk, transposed=False)
         bias = conv.bias.data_ptr() if conv.bias is not None else None
         if out is None:
             out = self.new_act(x.B, OH, OW, Cout, name)
@@ -972,7 +990,7 @@ class Graph:
         eng = self.engine
         Cout, _, KH, KW = conv.weight.shape
         taps = [(kh, kw) for kh in range(KH) for kw in range(KW)]
-        pk = eng.packed_tapgemm(conv, c0, x.C, transposed=False)
+        pk = eng.packs.tapgemm(conv, c0, x.C, transposed=False)
         z = self.new_act(x.B, x.H, x.W, len(taps) * Cout, name)
         # cfg 11 | 1 << 16: ask for conv1x1_ls_kernel with 32-channel items wherever it applies - the heuristic sends these few-pixel
         # launches to conv_mfma_kernel's 128 x 32 tiles (a serial chain of K / 32 staged chunks per workgroup: 30 us for 0.15 GFLOP)
@@ -988,7 +1006,7 @@ class Graph:
                 if not z.grad_ready():
                     raise SaltError('hyper_level: dL/dz was never written (conv_hyper must consume %s)' % name)
                 self._wgrad(z.gview(), x.view(), [(0, 0)], None, 1, 0, conv.weight, KH, KW, b_slice=(c0, D1), tapgemm=(Cout, taps))
-                pkt = eng.packed_tapgemm(conv, c0, x.C, transposed=True, bwd=True)
+                pkt = eng.packs.tapgemm(conv, c0, x.C, transposed=True, bwd=True)
                 acc = x.grad_state()
                 self._conv_launch(self.bwd, z.gview(), pkt.data_ptr(), [(0, 0)], 1, 0, x.gview(), x.H, x.W, accumulate=acc, stream=self._bwd_pack_tag(), cfg=ask)
             self.tape.append(backward)
@@ -1008,7 +1026,7 @@ class Graph:
         tk = [(t[0], t[1]) for t in taps]
         td = [(t[2], t[3]) for t in taps]
         d1 = (0, x.C)
-        pk = eng.packed(conv, tk, transposed=False, d1=d1)
+        pk = eng.packs.dense(conv, tk, transposed=False, d1=d1)
         bias = conv.bias.data_ptr() if conv.bias is not None else None
         if head is not None and not (self.head_bn_ok(Cout, head[0]) if self.train else self.hyper_head_ok(Cout, head[0])):
             raise SaltError('conv_hyper: this head cannot be fused (ask hyper_head_ok / head_bn_ok first)')
@@ -1097,7 +1115,7 @@ class Graph:
     def _dgrad(self, conv, x, dy, taps, stride, replicate, KH, KW, d1=None):
         eng = self.engine
         tk = [(t[0], t[1]) for t in taps]
-        pk = eng.packed(conv, tk, transposed=True, bwd=True, d1=d1)       # n = cin, c = cout
+        pk = eng.packs.dense(conv, tk, transposed=True, bwd=True, d1=d1)       # n = cin, c = cout
         if replicate:
             # gradient w.r.t. the replicate-padded input on the extended domain, then fold the pad back
             top, right = KH - 1, KW - 1
@@ -1144,7 +1162,7 @@ class Graph:
         if fused is not None:
             # ONE launch for all four phases (each its own packed weight block; taps a phase lacks are zero weights)
             td_u, phase_taps = fused
-            pk_t, elems = eng.packed_phases(conv, phase_taps, transposed=True, bwd=True)
+            pk_t, elems = eng.packs.phases(conv, phase_taps, transposed=True, bwd=True)
             s = self._conv_launch(self.bwd, dy.gview(), pk_t.data_ptr(), td_u, 1, 0, x.gview(), x.H // 2, x.W // 2, out_step=2, accumulate=acc,
                                   nphase=4, w_phase_elems=elems, stream=self._bwd_pack_tag())
             x.offer_carrier(SUMS_CONV, s)              # all four parities of an even grid: every pixel once - can carry the BatchNorm-backward sums (round 6)
@@ -1156,7 +1174,7 @@ class Graph:
             oh, ow = (x.H - ay + 1) // 2, (x.W - ax + 1) // 2
             if not sel or oh <= 0 or ow <= 0:
                 continue
-            pk_s = eng.packed(conv, [tk[i] for i in sel], transposed=True, bwd=True)
+            pk_s = eng.packs.dense(conv, [tk[i] for i in sel], transposed=True, bwd=True)
             td = [((ay - taps[i][2]) // 2, (ax - taps[i][3]) // 2) for i in sel]
             self._conv_launch(self.bwd, dy.gview(), pk_s.data_ptr(), td, 1, 0, x.gview(), oh, ow, out_step=2, out_oy=ay, out_ox=ax, accumulate=acc,
                               stream=self._bwd_pack_tag())
@@ -1223,12 +1241,12 @@ class Graph:
         if fused is not None:
             # ONE launch for the four output-parity phases of the transposed convolution
             td_u, phase_taps = fused
-            pk_t, elems = eng.packed_phases(deconv, phase_taps, transposed=True)
+            pk_t, elems = eng.packs.phases(deconv, phase_taps, transposed=True)
             plan = dict(out_step=2, nphase=4, w_phase_elems=elems)
             launches = [(pk_t.data_ptr(), td_u, 1, 0, x.H, x.W, dict(bias=bias, **plan))]
         else:
             plan = None
-            launches = [(eng.packed(deconv, [(s[0], s[1]) for s in sel], transposed=True).data_ptr(), [(s[2], s[3]) for s in sel], 1, 0, x.H, x.W,
+            launches = [(eng.packs.dense(deconv, [(s[0], s[1]) for s in sel], transposed=True).data_ptr(), [(s[2], s[3]) for s in sel], 1, 0, x.H, x.W,
                          dict(out_step=2, out_oy=fy, out_ox=fx, bias=bias)) for fy, fx, sel in phases]       # n = cout (D1), c = cin (D0)
         if train_bn:
             # The workspace names carry NO _scratch_sfx here, unlike conv / _stem_s2d: a transposed convolution emitted inside Graph.side()
@@ -1248,7 +1266,7 @@ class Graph:
                 self._wgrad(x.view(), tgt.gview(), [(t[2], t[3]) for t in taps_all], [(t[0], t[1]) for t in taps_all], 2, 0,
                             deconv.weight, KH, KW)
                 # data gradient: stride-2 convolution of dY with W[cin][cout] (n = cin, c = cout)
-                pk = eng.packed(deconv, [(t[0], t[1]) for t in taps_all], transposed=False, bwd=True)
+                pk = eng.packs.dense(deconv, [(t[0], t[1]) for t in taps_all], transposed=False, bwd=True)
                 acc = x.grad_state()
                 self._conv_launch(self.bwd, tgt.gview(), pk.data_ptr(), [(t[2], t[3]) for t in taps_all], 2, 0, x.gview(), x.H, x.W, accumulate=acc,
                                   stream=self._bwd_pack_tag())
@@ -1267,7 +1285,7 @@ class Graph:
         OW = (W + 2 * pad - K) // stride + 1
         out = self.new_act(B, OH, OW, Cout, name)
         bias = conv.bias.data_ptr() if conv.bias is not None else None
-        common = dict(dtype=self.dt, x=x_nchw.data_ptr(), B=B, Cin=Cin, H=H, W=W, w=conv.weight.data_ptr(), K=K, stride=stride, pad=pad, bias=bias)
+        common = dict(dtype=self.dt, x=self._in(x_nchw), B=B, Cin=Cin, H=H, W=W, w=conv.weight.data_ptr(), K=K, stride=stride, pad=pad, bias=bias)
         if self.train:
             y = self.new_act(B, OH, OW, Cout, name + '.y')
             S = fill(STRUCTS['salt_conv_first_args'](), B=B, Cin=Cin, H=H, W=W, K=K, stride=stride, pad=pad)
@@ -1280,7 +1298,7 @@ class Graph:
                 self._bn_train_bwd(y, bn, relu, None, out, w)
                 S2 = fill(STRUCTS['salt_conv_first_wgrad_args'](), B=B, Cin=Cin, H=H, W=W, K=K, stride=stride, pad=pad)
                 np_ = lib.salt_conv_first_wgrad_parts(ctypes.byref(S2))
-                self.bwd.add('conv_first_wgrad', stream=1, dtype=self.dt, x=x_nchw.data_ptr(), B=B, Cin=Cin, H=H, W=W, K=K, stride=stride, pad=pad,
+                self.bwd.add('conv_first_wgrad', stream=1, dtype=self.dt, x=self._in(x_nchw), B=B, Cin=Cin, H=H, W=W, K=K, stride=stride, pad=pad,
                              dy=y.gview(), partials=Scratch('wgrad', np_ * Cout * Cin * K * K * 4), nparts=np_,
                              grad=self._gp(conv.weight), accumulate=0)
             self.tape.append(backward)
@@ -1298,8 +1316,8 @@ class Graph:
         Cout, _, K, _ = conv.weight.shape
         TT, half = (K + 1) // 2, (K + 1) // 4
         z = self.new_act(B, H // 2, W // 2, 16, name + '.s2d')
-        self.fwd.add('s2d', dtype=self.dt, x=x_nchw.data_ptr(), B=B, Cin=Cin, H=H, W=W, z=z.view())
-        wp = eng.packed_stem(conv)
+        self.fwd.add('s2d', dtype=self.dt, x=self._in(x_nchw), B=B, Cin=Cin, H=H, W=W, z=z.view())
+        wp = eng.packs.stem(conv)
         taps = [(dh - half, dw - half) for dh in range(TT) for dw in range(TT)]
         OH, OW = H // 2, W // 2
         out = self.new_act(B, OH, OW, Cout, name)
@@ -1347,7 +1365,7 @@ class Graph:
             raise SaltError('stack_conv: weight %s does not fit the %d-map stack (a 3x3 Conv2dBnRelu is expected)' % (tuple(conv.weight.shape), M))
         nparts = stack_conv_parts(B, M, H, W, F)
         bias = conv.bias.data_ptr() if conv.bias is not None else None
-        common = dict(dtype=self.dt, x=x_nchw.data_ptr(), B=B, M=M, H=H, W=W, w=conv.weight.data_ptr(), bias=bias, F=F)
+        common = dict(dtype=self.dt, x=self._in(x_nchw), B=B, M=M, H=H, W=W, w=conv.weight.data_ptr(), bias=bias, F=F)
         if not self.train:
             if head is None or logits is None:
                 raise SaltError('stack_conv: the eval form is the whole network - it needs the head and the logits buffer')
@@ -1562,7 +1580,7 @@ class Graph:
         Cout, D1, KH, KW = conv.weight.shape
         d1, one = (c0, x.C), [(0, 0)]
         y = self.new_act(x.B, x.H, x.W, Cout, name)
-        self._conv_launch(self.fwd, x.view(), self.engine.packed(conv, one, transposed=False, d1=d1).data_ptr(), one, 1, 0, y.view(), x.H, x.W)
+        self._conv_launch(self.fwd, x.view(), self.engine.packs.dense(conv, one, transposed=False, d1=d1).data_ptr(), one, 1, 0, y.view(), x.H, x.W)
         if self.train:
             def backward():
                 if not y.grad_ready():
@@ -1640,7 +1658,7 @@ class Graph:
         taps = conv_taps(KH, KW, py, px)
         tk, td = [(t[0], t[1]) for t in taps], [(t[2], t[3]) for t in taps]
         OH, OW = x.H + 2 * py - KH + 1, x.W + 2 * px - KW + 1
-        pk = eng.packed(conv, tk, transposed=False)
+        pk = eng.packs.dense(conv, tk, transposed=False)
         bias = conv.bias.data_ptr() if conv.bias is not None else None
         alpha = prelu.weight.data_ptr()
         if out is None:
@@ -1809,7 +1827,7 @@ class Graph:
     def from_nchw(self, x_nchw, name='input'):
         B, C, H, W = x_nchw.shape
         a = self.new_act(B, H, W, C, name)
-        self.fwd.add('layout', dtype=self.dt, nchw=x_nchw.data_ptr(), nhwc=a.view(), to_nhwc=1)
+        self.fwd.add('layout', dtype=self.dt, nchw=self._in(x_nchw), nhwc=a.view(), to_nhwc=1)
         if self.train:
             dx = self.alloc((B, C, H, W), torch.float32)
             self.input_grads.append(dx)
@@ -2048,13 +2066,13 @@ class Graph:
         its columns of dL/ds) writes fc.weight.grad and fc.bias.grad.  ``d`` gets no gradient."""
         B, C = int(d.shape[0]), fc.weight.shape[0]
         s = self.f32(B * C)
-        self.fwd.add('depth_gate', d=d.data_ptr(), w=fc.weight.data_ptr(), bias=fc.bias.data_ptr(), B=B, C=C, s=s.data_ptr(), backward=0)
+        self.fwd.add('depth_gate', d=self._in(d), w=fc.weight.data_ptr(), bias=fc.bias.data_ptr(), B=B, C=C, s=s.data_ptr(), backward=0)
         gate = DepthGate(s, B, C, self.f32(B * C) if (self.train and not self._gate_shards()) else None, [], np.zeros(C, dtype=bool))
         if self.train:
             def backward():
                 if not gate.covered.all():
                     raise SaltError('depth_gate: %d of %d gate channels never met a channel_gate' % (int((~gate.covered).sum()), C))
-                sb = self.bwd.add('depth_gate', d=d.data_ptr(), B=B, C=C, s=s.data_ptr(), backward=1,
+                sb = self.bwd.add('depth_gate', d=self._in(d), B=B, C=C, s=s.data_ptr(), backward=1,
                                   ds=gate.ds.data_ptr() if gate.ds is not None else None, gw=self._gp(fc.weight), gb=self._gp(fc.bias),
                                   accumulate=0)
                 if gate.ds is None:

@@ -8,7 +8,7 @@ callbacks.py:262-275), ``state_dict()``, ``zero_grad()``, ``step()``."""
 
 import torch
 
-from ._abi import SaltError
+from ._abi import SaltError, lib
 from .engine import Program
 
 
@@ -75,17 +75,14 @@ class FusedAdam(torch.optim.Optimizer):
         eng = self._eng
         if eng.dtype != 'bf16':
             return None
-        if eng._pack_batched_n != len(eng._pack_ops):
-            eng._build_pack_batch()
-            eng._packed_version = eng._packed_bwd_version = -1
-        if self._pack_gen == eng._pack_generation:
+        eng.packs.ensure_built()
+        gen, jobs = eng.packs.adam_jobs()
+        if self._pack_gen == gen:
             return self._pack_prog
-        self._pack_gen, self._pack_prog = eng._pack_generation, None
-        jobs = eng._adam_jobs
+        self._pack_gen, self._pack_prog = gen, None
         if not jobs:
             return None
         import ctypes
-        from ._abi import lib
         base = eng.flat.data_ptr()
         blocks = [lib.salt_pack_job_blocks(ctypes.byref(j)) for j in jobs]
         pref = np.concatenate([[0], np.cumsum(blocks)]).astype(np.int32)
@@ -135,7 +132,7 @@ class FusedAdam(torch.optim.Optimizer):
         self.steps += 1
         self._eng.touch(weights=True, stats=False)
         if fused is not None:
-            self._eng._adam_packed_version = self._eng.wver      # Engine.refresh: only the remaining forward packs are stale
+            self._eng.packs.note_adam_packed(self._eng.wver)     # WeightPacks.refresh: only the remaining forward packs are stale
 
     def state_dict(self):
         g = {k: v for k, v in self.param_groups[0].items() if k != 'params'}

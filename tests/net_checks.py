@@ -6,6 +6,7 @@ Fixed here is only what defines the compared step itself (Adam lr 1e-4 with L2 1
 below which a tensor is not compared relatively, and the 16 elements below which a tensor counts as small.
 
 Importable without a GPU and without the built library: salt_amd is imported inside the functions."""
+import ctypes
 from collections import OrderedDict
 
 import numpy as np
@@ -213,6 +214,40 @@ def check_after_adam(opt, net, own, idx, fx, norm_tol, sum_tol, bn_tol, skip_bn)
             continue
         assert abs(float(sd[k].double().sum()) - s) <= bn_tol * max(1.0, abs(s)), k
     return sd
+
+
+# ------------------------------------------------------------------------------------------------ step inputs
+def _ptr_fields(struct, ptr, out):
+    """(struct, field) of every pointer field of an argument struct (nested views / arrays included) that holds ``ptr``: the by-value
+    search CompiledNet.bind used before the emitters recorded their step-input slots, kept as the oracle of those records"""
+    for name, ct in struct._fields_:
+        v = getattr(struct, name)
+        if isinstance(v, ctypes.Structure):
+            _ptr_fields(v, ptr, out)
+        elif isinstance(v, ctypes.Array):
+            for e in v:
+                if isinstance(e, ctypes.Structure):
+                    _ptr_fields(e, ptr, out)
+        elif ct is ctypes.c_void_p and v == ptr:
+            out.append((struct, name))
+    return out
+
+
+def recorded_and_searched_slots(net, which):
+    """-> (recorded, searched, addresses of bwd's structs): the slots the programs of a CompiledNet recorded for step input ``which``
+    and the fields that hold its static buffer's address by value, each as a set of (address of the holding struct, field).  A ctypes
+    struct is identified by its address: a nested one gets a fresh Python object on every access."""
+    progs = [net.fwd, net.bwd] + list(net._loss_progs.values())
+    recorded, searched = set(), set()
+    for prog in progs:
+        for st, path, off in prog.slots.get(which, ()):
+            assert off == 0
+            for a in path[:-1]:
+                st = getattr(st, a)
+            recorded.add((ctypes.addressof(st), path[-1]))
+        for _, _, st in prog.ops:
+            searched |= {(ctypes.addressof(h), f) for h, f in _ptr_fields(st, getattr(net, which).data_ptr(), [])}
+    return recorded, searched, {ctypes.addressof(st) for _, _, st in net.bwd.ops}
 
 
 # ------------------------------------------------------------------------------------------------ trainer

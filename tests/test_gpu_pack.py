@@ -109,11 +109,12 @@ def test_fused_step_leaves_every_forward_pack_current():
     for _ in range(2):
         m._fit_loop([X, T])
     eng = m.model.engine()
-    assert m.optimizer._adam_pack_program() is not None and len(eng._adam_jobs) > 30
+    assert m.optimizer._adam_pack_program() is not None and len(eng.packs.adam_jobs()[1]) > 30
     eng.refresh(True)                                    # what the next step would do: the rest of the forward packs + the backward packs
     torch.cuda.synchronize()
-    have = {k: t.clone() for k, t in eng._packed.items()}
-    eng._pack_batched.run(); eng._pack_batched_bwd.run()   # every job from the fp32 masters
+    have = {k: t.clone() for k, t in eng.packs.tensors.items()}
+    pack_fwd, pack_bwd, _ = eng.packs.programs()
+    pack_fwd.run(); pack_bwd.run()                       # every job from the fp32 masters
     torch.cuda.synchronize()
-    for k, t in eng._packed.items():
+    for k, t in eng.packs.tensors.items():
         assert torch.equal(have[k].view(torch.int16), t.view(torch.int16)), k[1:]

@@ -453,7 +453,7 @@ def test_fused_step_reads_a_resident_batch_in_place(deterministic_sums):
             Xd = X.double().to(DEV)[sl] if mode == 'views' else X[sl].clone().to(DEV)
             ls.append(float(m._fit_loop([Xd, Tt[sl].clone().to(DEV)])['sum']))
         net = m.model.engine().net((4, 5, 32, 32), True)
-        assert len(net._slot_list('x')) >= 1
+        assert len(net.slots('x')) >= 1
         res.append((ls, m.model.engine().flat.clone()))
     assert res[0][0] == res[1][0] and len(set(res[0][0])) == 2 and torch.equal(res[0][1], res[1][1])
 

@@ -488,9 +488,10 @@ def test_builder_state_is_declared_not_probed_with_getattr_defaults():
         'Buffer': ['act_op', 'bn_train_out', 'grad_bias', 'head_fused', 'lazy'],
         'Act': ['on_side'],
         'Graph': ['_virtual_acts', '_bias_bufs', '_lazies', '_n_bnb', '_uses_bwd_packs', 'input_grads', 'dlogits', 'n_folded', '_shard_state'],
-        'Program': ['_graph'],
-        'CompiledNet': ['target', 'loss'],
-        'Engine': ['_pack_generation', '_pack_batched_n', '_adam_packed_version', '_graph_stream', '_pack_fork'],
+        'Program': ['_graph', 'slots'],
+        'CompiledNet': ['target', 'loss', '_step_graphs'],
+        'WeightPacks': ['generation', '_built', '_adam_version', '_fork'],
+        'Engine': ['_graph_stream'],
     }
     names = {n for ns in declared.values() for n in ns}
     for fn in ('engine.py', 'runtime.py'):
@@ -510,6 +511,30 @@ def test_builder_state_is_declared_not_probed_with_getattr_defaults():
             assigned[cls.name] = {t.attr for t in targets if isinstance(t, ast.Attribute) and isinstance(t.value, ast.Name) and t.value.id == 'self'}
     for cls, ns in declared.items():
         assert not set(ns) - assigned[cls], '%s.__init__ does not declare %s' % (cls, sorted(set(ns) - assigned[cls]))
+
+
+def test_pack_state_has_one_owner_and_step_inputs_are_recorded_not_searched():
+    """optim.py reaches the weight packs through WeightPacks' public members only (no underscore attribute of the engine or of the pack
+    object), runtime.py no longer searches argument structs for a pointer value, and what a newly registered pack job makes stale - the
+    packed versions go back to -1 - is written in exactly one function of WeightPacks."""
+    with open(os.path.join(PKG, 'optim.py')) as f:
+        optim = f.read()
+    assert 'eng.packs.' in optim
+    assert not re.search(r'\b(eng|self\._eng|packs)\._\w', optim), re.findall(r'\b(?:eng|self\._eng|packs)\._\w+', optim)
+    with open(os.path.join(PKG, 'runtime.py')) as f:
+        runtime = f.read()
+    assert '_ptr_fields' not in runtime and '_slot_list' not in runtime
+    packs = [n for n in ast.parse(runtime).body if isinstance(n, ast.ClassDef) and n.name == 'WeightPacks']
+    assert len(packs) == 1
+    invalidating = set()
+    for fn in (n for n in packs[0].body if isinstance(n, ast.FunctionDef) and n.name != '__init__'):
+        for node in (n for n in ast.walk(fn) if isinstance(n, ast.Assign)):
+            names = {t.attr for t in node.targets if isinstance(t, ast.Attribute)}
+            if names & {'_version', '_bwd_version'} and ast.unparse(node.value) == '-1':
+                invalidating.add(fn.name)
+    assert invalidating == {'_register'}, invalidating
+    engine = [n for n in ast.parse(runtime).body if isinstance(n, ast.ClassDef) and n.name == 'Engine'][0]
+    assert not {'packed', 'packed_tapgemm', 'packed_phases', 'packed_stem'} & {n.name for n in engine.body if isinstance(n, ast.FunctionDef)}
 
 
 def test_no_test_module_is_imported_and_the_abi_handle_is_defined_once():
