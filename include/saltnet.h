@@ -796,12 +796,41 @@ typedef struct {
     float* loss;              /* [1]: mean over images * loss_scale */
     float* dlogits;           /* fp32 NCHW or NULL (forward only) */
     float loss_scale;         /* loss weight (models.py:194) and 1/world for data parallel */
-    uint32_t* ws_split;       /* NULL, or [B * salt_lovasz_split_words(P)] words: images of >= 4096 elements are then sorted by several
+    uint32_t* ws_split;       /* NULL, or [rows * salt_lovasz_split_words(N)] words: rows of >= 4096 elements are then sorted by several
                                  workgroups each (segments of 2048 positions, 1 + 4 + 1 launches); same positions, ties and gradients */
+    int flags;                /* SALT_LOVASZ_* below; 0 (a zeroed field): per image, no void label - the behaviour before the field existed */
+    float ignore;             /* SALT_LOVASZ_HAS_IGNORE: the void value of `target` */
+    uint32_t* ws_flat;        /* NULL, or [rows * salt_lovasz_flat_words(N)] words: rows above 131072 elements are then sorted by the
+                                 long-row form (histograms in global memory); without it such a row runs in one workgroup */
 } salt_lovasz_args;
 int salt_lovasz_hinge(const salt_lovasz_args*, void* stream);
-/* words per image of salt_lovasz_args.ws_split (0: the split form does not apply to this size) */
+/* words per row of salt_lovasz_args.ws_split (0: the split form does not apply to this size) */
 int64_t salt_lovasz_split_words(int P);
+/* The options of lovasz_hinge(logits, labels, per_image, ignore) and lovasz_softmax(probas, labels, only_present, per_image, ignore)
+ * (lovasz_losses.py:81-115,173-210), as bits of `flags`.  Rows x N below: the hinge sorts B rows of N = P elements, batch-flat 1 row
+ * of N = B P; the softmax form B C rows of N = HW, batch-flat C rows of N = B HW.
+ *   BATCH_FLAT    per_image=False: one row over the whole batch in the order of view(-1) - the hinge's B P floats as they lie in
+ *                 memory; for class c of the softmax form pixel (b, i) has flat index b HW + i and lives at probas[(b C + c) HW + i].
+ *                 The loss is that row's (the mean of the C rows'); only loss_per_image[0] (loss_per_row[0 .. C)) is written.
+ *   HAS_IGNORE    an element whose target EQUALS `ignore` is void (tested before target > 0.5 makes a label): it is sorted behind
+ *                 every valid element, counts neither in k, c_k nor G, adds 0 to the loss and gets a gradient of exactly 0; the valid
+ *                 elements have the positions and g_k of the reference's compacted list.  A row without a valid element has loss 0
+ *                 and still counts in the mean.  Softmax form: row (b, c) reads its own target plane, so the caller writes `ignore`
+ *                 into EVERY plane of a void pixel.
+ *   ONLY_PRESENT  softmax form only: a class row with no positive among its valid elements is skipped (gradient exactly 0).  Per
+ *                 image the loss is the mean over the image's present classes (0 if none) and the result the mean over the B images,
+ *                 dprobas of row (b, c) scale by loss_scale / (B present_b); batch-flat it is the mean over the classes present
+ *                 anywhere in the batch.  Needs ws_present.
+ * Each form uses the shortest sort that fits N: one workgroup below 4096, the split form (ws_split) up to 131072, the long-row form
+ * (ws_flat) above; a missing workspace falls back to one workgroup.  All forms give bit-identical gradients.
+ * SALT_E_BADARG from host code, nothing launched: an unknown flag bit, ONLY_PRESENT on the hinge or without ws_present, a NaN `ignore`
+ * with HAS_IGNORE, a row longer than the payload encodes (N > 2^31 - 4096; N > 2^30 with HAS_IGNORE, ONLY_PRESENT or the softmax
+ * form's BATCH_FLAT, whose payload carries the void bit). */
+#define SALT_LOVASZ_BATCH_FLAT 1
+#define SALT_LOVASZ_ONLY_PRESENT 2
+#define SALT_LOVASZ_HAS_IGNORE 4
+/* words per row of ws_flat for a row of N elements (0: the long-row form does not apply to this size) */
+int64_t salt_lovasz_flat_words(int64_t N);
 
 /* 0.2*mean_c dice(sigmoid) + 0.9*BCEWithLogits (models.py:315-340,361-388), sums over the whole batch */
 typedef struct {
@@ -865,7 +894,11 @@ typedef struct {
     float* loss;              /* [1] */
     float* dprobas;           /* fp32 [B,C,HW] or NULL (forward only) */
     float loss_scale;
-    uint32_t* ws_split;       /* NULL, or [B*C * salt_lovasz_split_words(HW)] words */
+    uint32_t* ws_split;       /* NULL, or [rows * salt_lovasz_split_words(N)] words */
+    int flags;                /* SALT_LOVASZ_* (see salt_lovasz_args); 0: per image, all classes, no void label */
+    float ignore;             /* SALT_LOVASZ_HAS_IGNORE: the void value, written by the caller into every target plane of a void pixel */
+    uint32_t* ws_flat;        /* NULL, or [rows * salt_lovasz_flat_words(N)] words */
+    uint32_t* ws_present;     /* SALT_LOVASZ_ONLY_PRESENT: [B*C] words, the positives of every row */
 } salt_lovasz_softmax_args;
 int salt_lovasz_softmax(const salt_lovasz_softmax_args*, void* stream);
 

@@ -35,9 +35,11 @@ class _NativeLoss(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, logits, target, kind, *weights):
-        """``weights``: nothing, or the (dice_weight, cross_entropy_weight, smooth) tuple of 'dice_ce'"""
+        """``weights``: nothing, or the (dice_weight, cross_entropy_weight, smooth) tuple of 'dice_ce' / the lovasz_params tuple of
+        'lovasz' and 'lovasz_softmax'"""
         from . import losses
-        params = dict(zip(losses.DICE_CE_DEFAULTS, weights[0])) if weights else None
+        names = losses.LOVASZ_DEFAULTS.get(kind, losses.DICE_CE_DEFAULTS)
+        params = dict(zip(names, weights[0])) if weights else None
         loss, dl = losses.native_loss(logits.detach(), target, kind, want_grad=True, params=params)
         ctx.save_for_backward(dl)
         ctx.n_inputs = 3 + len(weights)

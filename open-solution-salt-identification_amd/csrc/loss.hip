@@ -176,10 +176,21 @@ __global__ __launch_bounds__(256) void iou_sweep_kernel(IouKP k) {
 
 extern "C" int64_t salt_lovasz_split_words(int P) { return lovasz_split_words(P); }
 
+extern "C" int64_t salt_lovasz_flat_words(int64_t N) { return lovasz_flat_words(N); }
+
 extern "C" int salt_lovasz_hinge(const salt_lovasz_args* a, void* stream) {
     if (!a || !a->logits || !a->target || a->B < 1 || a->P < 0 || !a->ws_keys || !a->ws_vals || !a->loss_per_image || !a->loss)
         SALT_FAIL(SALT_E_BADARG, "lovasz: bad args");
-    return lovasz_launch<HingeElu>(a, (hipStream_t)stream);
+    if (const char* why = lovasz_flags_refusal(a->flags, a->ignore, false)) SALT_FAIL(SALT_E_BADARG, "lovasz: %s (flags 0x%x)", why, a->flags);
+    const bool has_void = a->flags & SALT_LOVASZ_HAS_IGNORE;
+    const int64_t N = (a->flags & SALT_LOVASZ_BATCH_FLAT) ? (int64_t)a->B * a->P : a->P;
+    if (N > (has_void ? LOVASZ_MAX_ROW_VOID : LOVASZ_MAX_ROW)) SALT_FAIL(SALT_E_BADARG, "lovasz: a row of %lld elements", (long long)N);
+    salt_lovasz_args r = *a;
+    if (a->flags & SALT_LOVASZ_BATCH_FLAT) { r.B = 1; r.P = (int)N; }        // the batch as it lies in memory is the one row
+    if (!has_void) return lovasz_launch<HingeElu>(&r, (hipStream_t)stream);
+    LovaszX x{};
+    x.ignore = a->ignore; x.flags = XF_VOID;
+    return lovasz_launch_x<HingeElu, XOpt>(&r, x, nullptr, (hipStream_t)stream);
 }
 
 extern "C" int salt_bce_dice_parts(const salt_bce_dice_args* a) {

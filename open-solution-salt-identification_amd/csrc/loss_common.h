@@ -28,6 +28,56 @@ struct AbsError {                        // lovasz_losses.py:173-210: e = |fg - 
     static __device__ __forceinline__ float dvalue(float e, unsigned lab) { return e == 0.f ? 0.f : (lab ? -1.f : 1.f); }
 };
 
+// The options of a row are a second policy.  XPlain is the call without options: contiguous rows, no void label,
+// every class; its kernels hold no trace of the rest.  XOpt reads LovaszX at run time:
+//   void     an element whose target equals `ignore` gets the largest key (no finite error maps to it) and bit 1 of the payload, so it
+//            is sorted behind every valid element and the valid ones keep the positions of the compacted list; it counts in neither
+//            k, c_k nor G and its gradient is written as 0
+//   gather   row c of the batch-flat softmax form: flat index j = b HW + i lives at ((b C + c) HW + i)
+//   present  rowpos[row] = positives of the row (lovasz_rowpos_kernel); rows come in groups of C classes, a row without positives is
+//            skipped (loss 0, gradient 0) and the others scale by loss_scale / (groups * present classes of the group)
+// The payload is (index << 1 | label) for XPlain and (index << 2 | void << 1 | label) for XOpt.
+__device__ __forceinline__ unsigned desc_key(float e);
+constexpr int XF_VOID = 1, XF_GATHER = 2;
+struct LovaszX { float ignore; int flags; int HW; int C; const unsigned* rowpos; };
+struct XPlain { static constexpr bool on = false; static constexpr int shift = 1; };
+struct XOpt { static constexpr bool on = true; static constexpr int shift = 2; };
+
+// offset of element i of row b in logits / target / dlogits
+template <class X>
+__device__ __forceinline__ int64_t x_off(const salt_lovasz_args& a, const LovaszX& x, int b, int64_t i) {
+    if constexpr (X::on) {
+        if (x.flags & XF_GATHER) { const int64_t im = i / x.HW; return (im * x.C + b) * x.HW + (i - im * x.HW); }
+    }
+    return (int64_t)b * a.P + i;
+}
+
+template <class Pol, class X>
+__device__ __forceinline__ void x_keyval(float zi, float yi, unsigned i, const LovaszX& x, unsigned& key, unsigned& val, float& lab) {
+    if constexpr (X::on) {
+        if ((x.flags & XF_VOID) && yi == x.ignore) { key = 0xffffffffu; val = (i << 2) | 2u; lab = 0.f; return; }   // before the > 0.5 test
+    }
+    lab = yi > 0.5f ? 1.f : 0.f;                                  // target.long() of a {0.,1.} mask
+    key = desc_key(Pol::error(zi, lab));
+    val = (i << X::shift) | (lab > 0.5f ? 1u : 0u);
+}
+
+// gradient scale of row b; *skip: the row is left out (only-present and no positives)
+template <class X>
+__device__ __forceinline__ float x_gscale(const salt_lovasz_args& a, const LovaszX& x, int b, bool* skip) {
+    *skip = false;
+    if constexpr (X::on) {
+        if (x.rowpos) {
+            const int g0 = (b / x.C) * x.C;
+            int present = 0;
+            for (int c = 0; c < x.C; ++c) present += x.rowpos[g0 + c] > 0u ? 1 : 0;
+            *skip = x.rowpos[b] == 0u;
+            return *skip ? 0.f : a.loss_scale / (float)((a.B / x.C) * present);
+        }
+    }
+    return a.loss_scale / (float)a.B;
+}
+
 constexpr int LT = 1024;                 // threads per image
 constexpr int LW = LT / 64;              // waves
 
@@ -53,8 +103,8 @@ __device__ __forceinline__ float key_to_float(unsigned k) {
 //   g_k = J_k - J_(k-1)  (g_1 = J_1),  loss += value(e_k) g_k,  d loss / d input = dvalue g_k loss_scale / B
 //   (hinge: value = elu, dvalue = -sign d).
 constexpr int LG = 4;                    // chunks per prefetch group
-template <class Pol>
-__global__ __launch_bounds__(LT) void lovasz_pf_kernel(salt_lovasz_args a) {
+template <class Pol, class X>
+__global__ __launch_bounds__(LT) void lovasz_pf_kernel(salt_lovasz_args a, LovaszX x) {
     __shared__ unsigned hist[2][256];
     __shared__ unsigned base[256];
     __shared__ unsigned wcount[LW][256];
@@ -76,11 +126,11 @@ __global__ __launch_bounds__(LT) void lovasz_pf_kernel(salt_lovasz_args a) {
     __syncthreads();
     float gsum = 0.f;
     for (int i = tid; i < P; i += LT) {
-        const float lab = y[i] > 0.5f ? 1.f : 0.f;              // target.long() of a {0.,1.} mask
-        const float e = Pol::error(z[i], lab);
-        const unsigned key = desc_key(e);
+        unsigned key, val; float lab;
+        if constexpr (X::on) { const int64_t o = x_off<X>(a, x, b, i); x_keyval<Pol, X>(a.logits[o], a.target[o], (unsigned)i, x, key, val, lab); }
+        else x_keyval<Pol, X>(z[i], y[i], (unsigned)i, x, key, val, lab);
         k0[i] = key;
-        v0[i] = ((unsigned)i << 1) | (lab > 0.5f ? 1u : 0u);
+        v0[i] = val;
         atomicAdd(&hist[0][key & 255u], 1u);
         gsum += lab;
     }
@@ -162,7 +212,8 @@ __global__ __launch_bounds__(LT) void lovasz_pf_kernel(salt_lovasz_args a) {
     if (tid == 0) carry_s = 0;
     __syncthreads();
     float lsum = 0.f;
-    const float gscale = a.loss_scale / (float)a.B;
+    bool skip;
+    const float gscale = x_gscale<X>(a, x, b, &skip);
     float* dz = a.dlogits ? a.dlogits + (int64_t)b * P : nullptr;
     unsigned ck[LG], cv[LG], nk[LG], nv[LG];
 #pragma unroll
@@ -199,8 +250,14 @@ __global__ __launch_bounds__(LT) void lovasz_pf_kernel(salt_lovasz_args a) {
                 if (i > 0) jm = __fsub_rn(1.f, __fdiv_rn(G - ckm, G + ((kf - 1.f) - ckm)));
                 const float gk = (i > 0) ? __fsub_rn(jk, jm) : jk;
                 const float el = Pol::value(e);
-                lsum += el * gk;
-                if (dz) dz[val >> 1] = Pol::dvalue(e, lab) * gk * gscale;
+                if constexpr (X::on) {
+                    const bool live = !(val & 2u) && !skip;       // a void element or a skipped row: no loss, a gradient of exactly 0
+                    if (live) lsum += el * gk;
+                    if (a.dlogits && (val >> 2) < (unsigned)P) a.dlogits[x_off<X>(a, x, b, val >> 2)] = live ? Pol::dvalue(e, lab) * gk * gscale : 0.f;
+                } else {
+                    lsum += el * gk;
+                    if (dz) dz[val >> 1] = Pol::dvalue(e, lab) * gk * gscale;
+                }
             }
             __syncthreads();
         }
@@ -234,10 +291,38 @@ __global__ __launch_bounds__(LT) void lovasz_pf_kernel(salt_lovasz_args a) {
 // lovasz_pf_kernel, so gradients are bit-identical to it; the loss differs in the last bits (different summation tree).
 // Only the keys and the scan kernel see the policy; the passes move (key, payload) pairs.
 constexpr int ST = 256, SWV = ST / 64, SL = 2048, SCH = SL / ST, SMAXSEG = 64;
-struct LovaszSplit { int S; unsigned* hist; unsigned* pos; float* part; };      // hist [3][B][S][256], pos [B][S], part [B][S]
+struct LovaszSplit {                                                            // hist [3][B][S][256], pos [B][S], part [B][S]
+    int S; unsigned* hist; unsigned* pos; float* part;
+    static constexpr bool guard = false;
+    __device__ __forceinline__ void first_histogram(int B, int b, int seg, int tid, unsigned count) const {
+        const int64_t slot = ((int64_t)b * S + seg) * 256 + tid, hb = (int64_t)B * S * 256;
+        hist[slot] = count;
+        hist[hb + slot] = 0;                                      // buffer 1 collects digit 1 during pass 0
+        if (tid == 0) pos[b * S + seg] = 0;
+    }
+    // positives of the row in the segments before `seg`, and in the whole row
+    __device__ __forceinline__ void positives(int b, int seg, unsigned* carry, unsigned* gtot) const {
+        unsigned g = 0, c = 0;
+        for (int s2 = 0; s2 < S; ++s2) { const unsigned v = pos[b * S + s2]; g += v; if (s2 < seg) c += v; }
+        *carry = c; *gtot = g;
+    }
+};
+// The long-row form (rows above SMAXSEG segments): the histograms live in global memory, digit-major so that one digit's counts over
+// the segments are contiguous - hist [rows][256][S], tot [rows][256], pos [rows][S], postot [rows], part [rows][S].
+struct LovaszLong {
+    int S; unsigned* hist; unsigned* tot; unsigned* pos; unsigned* postot; float* part;
+    static constexpr bool guard = true;                           // new code checks a payload's index before it stores through it
+    __device__ __forceinline__ void first_histogram(int, int b, int seg, int tid, unsigned count) const {
+        hist[((int64_t)b * 256 + tid) * S + seg] = count;
+    }
+    __device__ __forceinline__ void positives(int b, int seg, unsigned* carry, unsigned* gtot) const {
+        *carry = pos[(int64_t)b * S + seg];                       // exclusive prefix (lovasz_segscan_kernel)
+        *gtot = postot[b];
+    }
+};
 
-template <class Pol>
-__global__ __launch_bounds__(ST) void lovasz_keys_kernel(salt_lovasz_args a, LovaszSplit sp) {
+template <class Pol, class X, class SP>
+__global__ __launch_bounds__(ST) void lovasz_keys_kernel(salt_lovasz_args a, SP sp, LovaszX x) {
     __shared__ unsigned h[256];
     const int b = blockIdx.x / sp.S, seg = blockIdx.x % sp.S, tid = threadIdx.x;
     const int P = a.P, i0 = seg * SL, i1 = min(i0 + SL, P);
@@ -248,18 +333,15 @@ __global__ __launch_bounds__(ST) void lovasz_keys_kernel(salt_lovasz_args a, Lov
     h[tid] = 0;
     __syncthreads();
     for (int i = i0 + tid; i < i1; i += ST) {
-        const float lab = y[i] > 0.5f ? 1.f : 0.f;
-        const float e = Pol::error(z[i], lab);
-        const unsigned key = desc_key(e);
+        unsigned key, val; float lab;
+        if constexpr (X::on) { const int64_t o = x_off<X>(a, x, b, i); x_keyval<Pol, X>(a.logits[o], a.target[o], (unsigned)i, x, key, val, lab); }
+        else x_keyval<Pol, X>(z[i], y[i], (unsigned)i, x, key, val, lab);
         k0[i] = key;
-        v0[i] = ((unsigned)i << 1) | (lab > 0.5f ? 1u : 0u);
+        v0[i] = val;
         atomicAdd(&h[key & 255u], 1u);
     }
     __syncthreads();
-    const int64_t slot = ((int64_t)b * sp.S + seg) * 256 + tid, hb = (int64_t)a.B * sp.S * 256;
-    sp.hist[slot] = h[tid];
-    sp.hist[hb + slot] = 0;                                       // buffer 1 collects digit 1 during pass 0
-    if (tid == 0) sp.pos[b * sp.S + seg] = 0;
+    sp.first_histogram(a.B, b, seg, tid, h[tid]);
 }
 
 __global__ __launch_bounds__(ST) void lovasz_pass_kernel(salt_lovasz_args a, LovaszSplit sp, int pass) {
@@ -342,8 +424,8 @@ __global__ __launch_bounds__(ST) void lovasz_pass_kernel(salt_lovasz_args a, Lov
     }
 }
 
-template <class Pol>
-__global__ __launch_bounds__(ST) void lovasz_scan_kernel(salt_lovasz_args a, LovaszSplit sp) {
+template <class Pol, class X, class SP>
+__global__ __launch_bounds__(ST) void lovasz_scan_kernel(salt_lovasz_args a, SP sp, LovaszX x) {
     __shared__ unsigned scan_w[SWV];
     __shared__ float red[SWV];
     const int b = blockIdx.x / sp.S, seg = blockIdx.x % sp.S, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -354,9 +436,10 @@ __global__ __launch_bounds__(ST) void lovasz_scan_kernel(salt_lovasz_args a, Lov
 #pragma unroll
     for (int u = 0; u < SCH; ++u) { const int i = i0 + u * ST + tid; ck[u] = i < P ? k0[i] : 0u; cv[u] = i < P ? v0[i] : 0u; }
     unsigned gtot = 0, carry = 0;
-    for (int s2 = 0; s2 < S; ++s2) { const unsigned c = sp.pos[b * S + s2]; gtot += c; if (s2 < seg) carry += c; }
+    sp.positives(b, seg, &carry, &gtot);
     const float G = (float)gtot;
-    const float gscale = a.loss_scale / (float)a.B;
+    bool skip;
+    const float gscale = x_gscale<X>(a, x, b, &skip);
     float* dz = a.dlogits ? a.dlogits + (int64_t)b * P : nullptr;
     float lsum = 0.f;
 #pragma unroll
@@ -386,8 +469,14 @@ __global__ __launch_bounds__(ST) void lovasz_scan_kernel(salt_lovasz_args a, Lov
             if (i > 0) jm = __fsub_rn(1.f, __fdiv_rn(G - ckm, G + ((kf - 1.f) - ckm)));
             const float gk = (i > 0) ? __fsub_rn(jk, jm) : jk;
             const float el = Pol::value(e);
-            lsum += el * gk;
-            if (dz) dz[val >> 1] = Pol::dvalue(e, lab) * gk * gscale;
+            if constexpr (X::on) {
+                const bool live = !(val & 2u) && !skip;           // a void element or a skipped row: no loss, a gradient of exactly 0
+                if (live) lsum += el * gk;
+                if (a.dlogits && (val >> 2) < (unsigned)P) a.dlogits[x_off<X>(a, x, b, val >> 2)] = live ? Pol::dvalue(e, lab) * gk * gscale : 0.f;
+            } else {
+                lsum += el * gk;
+                if (dz && (!SP::guard || (val >> 1) < (unsigned)P)) dz[val >> 1] = Pol::dvalue(e, lab) * gk * gscale;
+            }
         }
     }
 #pragma unroll
@@ -398,7 +487,7 @@ __global__ __launch_bounds__(ST) void lovasz_scan_kernel(salt_lovasz_args a, Lov
     if (tid == 0) {
         float t = 0.f;
         for (int w = 0; w < SWV; ++w) t += red[w];
-        sp.part[b * S + seg] = t;
+        sp.part[(int64_t)b * S + seg] = t;
     }
 }
 
@@ -427,6 +516,184 @@ __global__ void mean_kernel(const float* v, int n, float scale, float* out) {
     }
 }
 
+// ---------------------------------------------------------------- long rows: more than SMAXSEG segments
+// The [S][256] next-digit table of lovasz_pass_kernel does not fit LDS beyond 64 segments (512 segments: 512 KB), so the long-row form
+// keeps the SAME stable LSD radix sort and moves the histograms to global memory, digit-major (LovaszLong).  Per pass:
+//   count    (pass 0: the keys kernel) digit histogram of every source segment                  -> hist[row][digit][seg]
+//   segscan  one workgroup per (row, digit): exclusive prefix over the segments in place, the digit's total -> tot[row][digit]
+//   scatter  digit base = (exclusive prefix of tot over the digits) + hist[row][digit][seg]; ranking chunk by chunk exactly as
+//            lovasz_pass_kernel
+// then poscount (positives per sorted segment, plain stores), segscan over them (carry of the earlier segments and G), and
+// lovasz_scan_kernel.  Launch boundaries are the only cross-workgroup synchronisation; there is no floating-point atomic and no
+// global atomic at all, every sum has a fixed order: reruns are bit-identical.  Positions, ties and the fp32 sequence of g_k are
+// lovasz_pf_kernel's, so the gradients equal it bit for bit.
+__global__ __launch_bounds__(ST) void lovasz_count_kernel(salt_lovasz_args a, LovaszLong sp, int pass) {
+    __shared__ unsigned h[256];
+    const int b = blockIdx.x / sp.S, seg = blockIdx.x % sp.S, tid = threadIdx.x;
+    const int P = a.P, i0 = seg * SL, i1 = min(i0 + SL, P);
+    const unsigned* ki = a.ws_keys + ((int64_t)((pass & 1) ? a.B : 0) + b) * P;
+    h[tid] = 0;
+    __syncthreads();
+    for (int i = i0 + tid; i < i1; i += ST) atomicAdd(&h[(ki[i] >> (pass * 8)) & 255u], 1u);
+    __syncthreads();
+    sp.first_histogram(a.B, b, seg, tid, h[tid]);
+}
+
+// workgroup w: arr[w][0 .. S) becomes its exclusive prefix, tot[w] its sum
+__global__ __launch_bounds__(ST) void lovasz_segscan_kernel(unsigned* arr, unsigned* tot, int S) {
+    __shared__ unsigned scan_w[SWV];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    unsigned* v = arr + (int64_t)blockIdx.x * S;
+    unsigned carry = 0;
+    for (int c0 = 0; c0 < S; c0 += ST) {
+        const int i = c0 + tid;
+        const unsigned c = i < S ? v[i] : 0u;
+        unsigned incl = c;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) { const unsigned t = __shfl_up(incl, o); if (lane >= o) incl += t; }
+        __syncthreads();                                          // scan_w of the previous chunk has been read
+        if (lane == 63) scan_w[wave] = incl;
+        __syncthreads();
+        unsigned woff = carry, ctot = 0;
+        for (int w = 0; w < SWV; ++w) { if (w < wave) woff += scan_w[w]; ctot += scan_w[w]; }
+        if (i < S) v[i] = woff + incl - c;
+        carry += ctot;
+    }
+    if (tid == 0) tot[blockIdx.x] = carry;
+}
+
+__global__ __launch_bounds__(ST) void lovasz_scatter_kernel(salt_lovasz_args a, LovaszLong sp, int pass) {
+    __shared__ unsigned base[256];
+    __shared__ unsigned wcount2[2][SWV][256];
+    __shared__ unsigned scan_w[SWV];
+    const int b = blockIdx.x / sp.S, seg = blockIdx.x % sp.S, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int P = a.P, S = sp.S, i0 = seg * SL;
+    const unsigned* ki = a.ws_keys + ((int64_t)((pass & 1) ? a.B : 0) + b) * P;
+    const unsigned* vi = a.ws_vals + ((int64_t)((pass & 1) ? a.B : 0) + b) * P;
+    unsigned* ko = a.ws_keys + ((int64_t)((pass & 1) ? 0 : a.B) + b) * P;
+    unsigned* vo = a.ws_vals + ((int64_t)((pass & 1) ? 0 : a.B) + b) * P;
+    const int shift = pass * 8;
+    unsigned ck[SCH], cv[SCH];
+#pragma unroll
+    for (int u = 0; u < SCH; ++u) { const int i = i0 + u * ST + tid; ck[u] = i < P ? ki[i] : 0u; cv[u] = i < P ? vi[i] : 0u; }
+    {
+        const unsigned tot = sp.tot[(int64_t)b * 256 + tid], before = sp.hist[((int64_t)b * 256 + tid) * S + seg];
+        unsigned incl = tot;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) { const unsigned t = __shfl_up(incl, o); if (lane >= o) incl += t; }
+        if (lane == 63) scan_w[wave] = incl;
+        __syncthreads();
+        unsigned woff = 0;
+        for (int w = 0; w < wave; ++w) woff += scan_w[w];
+        base[tid] = woff + incl - tot + before;
+    }
+    const unsigned long long lt_mask = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
+#pragma unroll
+    for (int u = 0; u < SCH; ++u) {
+        const int c0 = i0 + u * ST;
+        if (c0 >= P) break;                                       // uniform
+        unsigned (*wcount)[256] = wcount2[u & 1];
+#pragma unroll
+        for (int w = 0; w < SWV; ++w) wcount[w][tid] = 0;
+        __syncthreads();                                          // also publishes base[] on the first round
+        const bool ok = c0 + tid < P;
+        const unsigned key = ck[u];
+        const unsigned d = ok ? ((key >> shift) & 255u) : 256u;
+        unsigned long long m = __ballot(ok);
+#pragma unroll
+        for (int bit = 0; bit < 8; ++bit) {
+            const unsigned long long bm = __ballot((d >> bit) & 1u);
+            m &= ((d >> bit) & 1u) ? bm : ~bm;
+        }
+        const unsigned rank = (unsigned)__popcll(m & lt_mask);
+        if (ok && rank == 0) wcount[wave][d] = (unsigned)__popcll(m);
+        __syncthreads();
+        {
+            unsigned run = base[tid];
+#pragma unroll
+            for (int w = 0; w < SWV; ++w) { const unsigned c = wcount[w][tid]; wcount[w][tid] = run; run += c; }
+            base[tid] = run;
+        }
+        __syncthreads();
+        if (ok) {
+            const unsigned dst = wcount[wave][d] + rank;
+            if (dst < (unsigned)P) { ko[dst] = key; vo[dst] = cv[u]; }       // always true for consistent histograms; never write outside the row
+        }
+    }
+}
+
+__global__ __launch_bounds__(ST) void lovasz_poscount_kernel(salt_lovasz_args a, LovaszLong sp) {
+    __shared__ unsigned cnt[SWV];
+    const int b = blockIdx.x / sp.S, seg = blockIdx.x % sp.S, tid = threadIdx.x;
+    const int P = a.P, i0 = seg * SL, i1 = min(i0 + SL, P);
+    const unsigned* v0 = a.ws_vals + (int64_t)b * P;
+    unsigned c = 0;
+    for (int i = i0 + tid; i < i1; i += ST) c += v0[i] & 1u;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o);
+    if ((tid & 63) == 0) cnt[tid >> 6] = c;
+    __syncthreads();
+    if (tid == 0) { unsigned t = 0; for (int w = 0; w < SWV; ++w) t += cnt[w]; sp.pos[(int64_t)b * sp.S + seg] = t; }
+}
+
+// ---------------------------------------------------------------- only-present: positives of every row before anything is sorted
+constexpr int RPL = 8192;                // elements per workgroup of lovasz_rowpos_kernel
+__global__ void lovasz_zero_kernel(unsigned* v, int n) {
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) v[i] = 0u;
+}
+__global__ __launch_bounds__(ST) void lovasz_rowpos_kernel(salt_lovasz_args a, LovaszX x, unsigned* rowpos, int parts) {
+    const int b = blockIdx.x / parts, part = blockIdx.x % parts, tid = threadIdx.x;
+    const int P = a.P, i0 = part * RPL, i1 = min(i0 + RPL, P);
+    unsigned c = 0;
+    for (int i = i0 + tid; i < i1; i += ST) {
+        const float yi = a.target[x_off<XOpt>(a, x, b, i)];
+        if (!((x.flags & XF_VOID) && yi == x.ignore) && yi > 0.5f) ++c;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o);
+    if ((tid & 63) == 0 && c) atomicAdd(&rowpos[b], c);           // integer: the sum does not depend on the order
+}
+
+// Row losses from the per-segment partials (`part` NULL: per_row holds them already), then the mean in fixed order: over all rows, or
+// (rowpos given) over the groups of C classes of the mean over each group's present classes, 0 for a group with none.
+__global__ __launch_bounds__(ST) void lovasz_mean_x_kernel(const float* part, int S, float* per_row, int rows, int C, const unsigned* rowpos,
+                                                           float scale, float* out) {
+    __shared__ float red[ST];
+    const int tid = threadIdx.x;
+    if (part && S <= SMAXSEG) {
+        for (int b = tid; b < rows; b += ST) {
+            float t = 0.f;
+            for (int s2 = 0; s2 < S; ++s2) t += part[(int64_t)b * S + s2];
+            per_row[b] = t;
+        }
+    } else if (part) {
+        for (int b = 0; b < rows; ++b) {
+            float t = 0.f;
+            for (int j = tid; j < S; j += ST) t += part[(int64_t)b * S + j];
+            red[tid] = t;
+            __syncthreads();
+            for (int o = ST / 2; o > 0; o >>= 1) { if (tid < o) red[tid] += red[tid + o]; __syncthreads(); }
+            if (tid == 0) per_row[b] = red[0];
+            __syncthreads();
+        }
+    }
+    __syncthreads();
+    if (tid != 0) return;
+    float t = 0.f;
+    if (!rowpos) {
+        for (int b = 0; b < rows; ++b) t += per_row[b];
+        out[0] = t * scale / (float)rows;
+        return;
+    }
+    const int groups = rows / C;
+    for (int g = 0; g < groups; ++g) {
+        float lg = 0.f; int present = 0;
+        for (int c = 0; c < C; ++c) if (rowpos[g * C + c] > 0u) { lg += per_row[g * C + c]; ++present; }
+        if (present) t += lg / (float)present;
+    }
+    out[0] = t * scale / (float)groups;
+}
+
 // words per row of salt_lovasz_args.ws_split (0: the split form does not apply to this size)
 inline int64_t lovasz_split_words(int P) {
     const int S = (P + SL - 1) / SL;
@@ -434,21 +701,87 @@ inline int64_t lovasz_split_words(int P) {
     return (int64_t)3 * S * 256 + 2 * S;
 }
 
-// The launches of one Lovasz loss over a->B rows of a->P elements (arguments already checked by the entry point).
+// words per row of salt_lovasz_args.ws_flat (0: the long-row form does not apply to this size)
+constexpr int64_t LOVASZ_MAX_ROW = ((int64_t)1 << 31) - 2 * SL, LOVASZ_MAX_ROW_VOID = (int64_t)1 << 30;
+inline int64_t lovasz_flat_words(int64_t N) {
+    const int64_t S = (N + SL - 1) / SL;
+    if (N < 1 || N > LOVASZ_MAX_ROW || S <= SMAXSEG) return 0;
+    return 258 * S + 257;
+}
+
+// The launches of one Lovasz loss with row options (X) and / or long rows; `rowpos`: NULL, or [a->B] words for only-present.
+template <class Pol, class X>
+int lovasz_launch_x(const salt_lovasz_args* a, LovaszX x, unsigned* rowpos, hipStream_t st) {
+    const int S = (int)(((int64_t)a->P + SL - 1) / SL), R = a->B;
+    if ((int64_t)R * S > 0x7fffffff) SALT_FAIL(SALT_E_BADARG, "lovasz: %d rows of %d segments", R, S);
+    x.rowpos = nullptr;
+    if constexpr (X::on) {
+        if (rowpos) {
+            const int parts = a->P > 0 ? (a->P + RPL - 1) / RPL : 1;
+            SALT_TRY(salt_launch(lovasz_zero_kernel, dim3((R + 255) / 256), dim3(256), 0, st, rowpos, R));
+            SALT_TRY(salt_launch(lovasz_rowpos_kernel, dim3(R * parts), dim3(ST), 0, st, *a, x, rowpos, parts));
+            x.rowpos = rowpos;
+        }
+    }
+    const int C = x.rowpos ? x.C : 1;
+    const dim3 grid(R * S);
+    if (a->ws_flat && S > SMAXSEG) {
+        unsigned* w = a->ws_flat;
+        LovaszLong sp;
+        sp.S = S;
+        sp.hist = w; w += (int64_t)R * 256 * S;
+        sp.tot = w; w += (int64_t)R * 256;
+        sp.pos = w; w += (int64_t)R * S;
+        sp.postot = w; w += R;
+        sp.part = reinterpret_cast<float*>(w);
+        SALT_TRY(salt_launch(lovasz_keys_kernel<Pol, X, LovaszLong>, grid, dim3(ST), 0, st, *a, sp, x));
+        for (int pass = 0; pass < 4; ++pass) {
+            if (pass) SALT_TRY(salt_launch(lovasz_count_kernel, grid, dim3(ST), 0, st, *a, sp, pass));
+            SALT_TRY(salt_launch(lovasz_segscan_kernel, dim3(R * 256), dim3(ST), 0, st, sp.hist, sp.tot, S));
+            SALT_TRY(salt_launch(lovasz_scatter_kernel, grid, dim3(ST), 0, st, *a, sp, pass));
+        }
+        SALT_TRY(salt_launch(lovasz_poscount_kernel, grid, dim3(ST), 0, st, *a, sp));
+        SALT_TRY(salt_launch(lovasz_segscan_kernel, dim3(R), dim3(ST), 0, st, sp.pos, sp.postot, S));
+        SALT_TRY(salt_launch(lovasz_scan_kernel<Pol, X, LovaszLong>, grid, dim3(ST), 0, st, *a, sp, x));
+        return salt_launch(lovasz_mean_x_kernel, dim3(1), dim3(ST), 0, st, (const float*)sp.part, S, a->loss_per_image, R, C, x.rowpos, a->loss_scale, a->loss);
+    }
+    if (a->ws_split && a->P >= 2 * SL && S <= SMAXSEG) {
+        LovaszSplit sp{S, a->ws_split, a->ws_split + (int64_t)3 * R * S * 256, reinterpret_cast<float*>(a->ws_split + (int64_t)3 * R * S * 256 + (int64_t)R * S)};
+        SALT_TRY(salt_launch(lovasz_keys_kernel<Pol, X, LovaszSplit>, grid, dim3(ST), 0, st, *a, sp, x));
+        const size_t lds = (size_t)(S * 256 + S) * sizeof(unsigned);
+        for (int pass = 0; pass < 4; ++pass) SALT_TRY(salt_launch(lovasz_pass_kernel, grid, dim3(ST), lds, st, *a, sp, pass));
+        SALT_TRY(salt_launch(lovasz_scan_kernel<Pol, X, LovaszSplit>, grid, dim3(ST), 0, st, *a, sp, x));
+        return salt_launch(lovasz_mean_x_kernel, dim3(1), dim3(ST), 0, st, (const float*)sp.part, S, a->loss_per_image, R, C, x.rowpos, a->loss_scale, a->loss);
+    }
+    SALT_TRY(salt_launch(lovasz_pf_kernel<Pol, X>, dim3(R), dim3(LT), 0, st, *a, x));
+    return salt_launch(lovasz_mean_x_kernel, dim3(1), dim3(ST), 0, st, (const float*)nullptr, 0, a->loss_per_image, R, C, x.rowpos, a->loss_scale, a->loss);
+}
+
+// The launches of one Lovasz loss without row options over a->B rows of a->P elements (arguments already checked by the entry point):
+// the shortest form that fits the row - one workgroup, the split form, the long-row form.
 template <class Pol>
 int lovasz_launch(const salt_lovasz_args* a, hipStream_t st) {
-    const int S = (a->P + SL - 1) / SL;
+    const int S = (int)(((int64_t)a->P + SL - 1) / SL);
+    if (a->ws_flat && S > SMAXSEG) return lovasz_launch_x<Pol, XPlain>(a, LovaszX{}, nullptr, st);
     if (a->ws_split && a->P >= 2 * SL && S <= SMAXSEG) {
         LovaszSplit sp{S, a->ws_split, a->ws_split + (int64_t)3 * a->B * S * 256, reinterpret_cast<float*>(a->ws_split + (int64_t)3 * a->B * S * 256 + (int64_t)a->B * S)};
         const dim3 grid(a->B * S);
-        SALT_TRY(salt_launch(lovasz_keys_kernel<Pol>, grid, dim3(ST), 0, st, *a, sp));
+        SALT_TRY(salt_launch(lovasz_keys_kernel<Pol, XPlain, LovaszSplit>, grid, dim3(ST), 0, st, *a, sp, LovaszX{}));
         const size_t lds = (size_t)(S * 256 + S) * sizeof(unsigned);
         for (int pass = 0; pass < 4; ++pass) SALT_TRY(salt_launch(lovasz_pass_kernel, grid, dim3(ST), lds, st, *a, sp, pass));
-        SALT_TRY(salt_launch(lovasz_scan_kernel<Pol>, grid, dim3(ST), 0, st, *a, sp));
+        SALT_TRY(salt_launch(lovasz_scan_kernel<Pol, XPlain, LovaszSplit>, grid, dim3(ST), 0, st, *a, sp, LovaszX{}));
         return salt_launch(lovasz_mean_split_kernel, dim3(1), dim3(256), 0, st, sp.part, a->B, S, a->loss_scale, a->loss_per_image, a->loss);
     }
-    SALT_TRY(salt_launch(lovasz_pf_kernel<Pol>, dim3(a->B), dim3(LT), 0, st, *a));
+    SALT_TRY(salt_launch(lovasz_pf_kernel<Pol, XPlain>, dim3(a->B), dim3(LT), 0, st, *a, LovaszX{}));
     return salt_launch(mean_kernel, dim3(1), dim3(64), 0, st, a->loss_per_image, a->B, a->loss_scale, a->loss);
+}
+
+// The option fields shared by salt_lovasz_args and salt_lovasz_softmax_args, checked on the host: 0 or the reason of the refusal.
+inline const char* lovasz_flags_refusal(int flags, float ignore, bool softmax) {
+    if (flags & ~(SALT_LOVASZ_BATCH_FLAT | SALT_LOVASZ_ONLY_PRESENT | SALT_LOVASZ_HAS_IGNORE)) return "unknown flag bit";
+    if ((flags & SALT_LOVASZ_ONLY_PRESENT) && !softmax) return "only-present is an option of the softmax form";
+    if ((flags & SALT_LOVASZ_HAS_IGNORE) && ignore != ignore) return "the ignore value is NaN";
+    return nullptr;
 }
 
 // parts per plane of the partial-sum losses: one up to 4096 positions, never more than 16; *per = positions per part

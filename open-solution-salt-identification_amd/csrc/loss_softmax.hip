@@ -166,7 +166,18 @@ extern "C" int salt_lovasz_softmax(const salt_lovasz_softmax_args* a, void* stre
     salt_lovasz_args r{};
     r.logits = a->probas; r.target = a->target; r.B = a->B * a->C; r.P = a->HW; r.ws_keys = a->ws_keys; r.ws_vals = a->ws_vals;
     r.loss_per_image = a->loss_per_row; r.loss = a->loss; r.dlogits = a->dprobas; r.loss_scale = a->loss_scale; r.ws_split = a->ws_split;
-    return lovasz_launch<AbsError>(&r, (hipStream_t)stream);
+    r.ws_flat = a->ws_flat;
+    if (const char* why = lovasz_flags_refusal(a->flags, a->ignore, true)) SALT_FAIL(SALT_E_BADARG, "lovasz_softmax: %s (flags 0x%x)", why, a->flags);
+    if ((a->flags & SALT_LOVASZ_ONLY_PRESENT) && !a->ws_present) SALT_FAIL(SALT_E_BADARG, "lovasz_softmax: only-present needs ws_present");
+    const bool flat = a->flags & SALT_LOVASZ_BATCH_FLAT;
+    const int64_t N = flat ? (int64_t)a->B * a->HW : a->HW;
+    if (N > (a->flags ? LOVASZ_MAX_ROW_VOID : LOVASZ_MAX_ROW)) SALT_FAIL(SALT_E_BADARG, "lovasz_softmax: a row of %lld elements", (long long)N);
+    if (!a->flags) return lovasz_launch<AbsError>(&r, (hipStream_t)stream);
+    LovaszX x{};
+    x.ignore = a->ignore; x.HW = a->HW; x.C = a->C;
+    x.flags = ((a->flags & SALT_LOVASZ_HAS_IGNORE) ? XF_VOID : 0) | (flat ? XF_GATHER : 0);
+    if (flat) { r.B = a->C; r.P = (int)N; }                          // C rows of B HW elements gathered across the images
+    return lovasz_launch_x<AbsError, XOpt>(&r, x, (a->flags & SALT_LOVASZ_ONLY_PRESENT) ? a->ws_present : nullptr, (hipStream_t)stream);
 }
 
 extern "C" int salt_dice_ce_parts(const salt_dice_ce_args* a) {

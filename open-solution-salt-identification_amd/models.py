@@ -21,7 +21,7 @@ from . import architectures as A
 from . import parallel
 from . import switches
 from ._abi import SaltError
-from .losses import dice_ce_params, lovasz_loss, lovasz_softmax_loss, mixed_dice_bce_loss, mixed_dice_cross_entropy_loss
+from .losses import LOVASZ_DEFAULTS, dice_ce_params, lovasz_params, lovasz_loss, lovasz_softmax_loss, mixed_dice_bce_loss, mixed_dice_cross_entropy_loss
 from .optim import FusedAdam, weight_regularization
 
 ARCHITECTURES = {
@@ -105,7 +105,7 @@ class Model:
         self.model = None
         self.optimizer = None
         self.loss_function = None
-        self.loss_params = None               # weights of the 'dice_ce' loss (model_params['loss_params']): set_loss writes, _fused_step reads
+        self.loss_params = None               # weights of 'dice_ce' / options of the Lovasz losses (model_params['loss_params']): set_loss writes, _fused_step reads
         self.callbacks = None
         self.validation_loss = {}
         self.validation_masks = None          # (loader_mode, original-size masks) set by ValidationMonitor.set_params, or None
@@ -202,6 +202,12 @@ class SegmentationModel(Model):
             loss_function = {'lovasz': lovasz_loss, 'bce_dice': mixed_dice_bce_loss}[name]
         else:
             raise Exception('Only softmax and sigmoid activations are allowed')
+        if name in LOVASZ_DEFAULTS and mp.get('loss_params'):
+            # the options of the Lovasz losses: per_image / ignore (/ only_present), read by the fused step like the weights above
+            lovasz_params(name, mp['loss_params'])
+            self.loss_params = dict(mp['loss_params'])
+            loss_function = functools.partial(loss_function, **self.loss_params)
+            loss_function.native_kind = name
         self.loss_function = [('mask', loss_function, 1.0)]
 
     def fit(self, datagen, validation_datagen=None, meta_valid=None):
@@ -260,6 +266,9 @@ class SegmentationModel(Model):
         """``D``: the depth input [B,1] of a depth-conditioned network (SegmentationModelWithDepth), fp32 on X's device."""
         eng = self.model.engine(X.device)
         eng.loss_params = self.loss_params
+        if kind in LOVASZ_DEFAULTS and self.dp._active() and not dict(self.loss_params or {}).get('per_image', True):
+            # every rank would sort its own shard; the reference computes the batch-flat loss on the gathered batch
+            raise SaltError("loss %r with per_image=False is one sort over the whole batch: it does not train data-parallel" % kind)
         # 'first step of a shape ran eagerly' is remembered ON the engine (a rebuilt engine starts empty - no recycled id() can skip it)
         if self.step_graph and not self.dp._active() and (tuple(X.shape), kind) in eng.eager_done:
             # the whole step (pack, forward, loss, backward, Adam; both streams) replayed as ONE hipGraph launch (the first step of

@@ -18,7 +18,7 @@ import torch
 from . import _abi
 from ._abi import SaltError, lib
 from .engine import Graph, Program, StepInput, set_path, DT_CODE, TORCH_DT
-from .losses import dice_ce_params
+from .losses import LOVASZ_DEFAULTS, dice_ce_params, lovasz_launch_shape, lovasz_params
 
 
 def _require_gpu(device):
@@ -89,9 +89,13 @@ class CompiledNet:
                 and t.data_ptr() % 16 == 0)
 
     def loss_key(self, kind, loss_scale):
-        """Cache key of a loss program (and of a captured step that contains it): the kind, the scale, and for 'dice_ce' the weights
-        the engine holds (Engine.loss_params, from model_params['loss_params'])."""
-        return (kind, float(loss_scale)) + (dice_ce_params(self.engine.loss_params) if kind == 'dice_ce' else ())
+        """Cache key of a loss program (and of a captured step that contains it): the kind, the scale, and for 'dice_ce' the weights /
+        for 'lovasz' and 'lovasz_softmax' the options the engine holds (Engine.loss_params, from model_params['loss_params'])."""
+        if kind == 'dice_ce':
+            return (kind, float(loss_scale)) + dice_ce_params(self.engine.loss_params)
+        if kind in LOVASZ_DEFAULTS:
+            return (kind, float(loss_scale)) + lovasz_params(kind, self.engine.loss_params)
+        return (kind, float(loss_scale))
 
     def loss_program(self, kind, loss_scale):
         key = self.loss_key(kind, loss_scale)
@@ -104,11 +108,15 @@ class CompiledNet:
             P = K * H * W
             wk = g.alloc((2, B, P), torch.int32, zero=False)
             wv = g.alloc((2, B, P), torch.int32, zero=False)
-            sw = int(lib.salt_lovasz_split_words(P))             # > 0: several workgroups per image (segments of the sort)
-            ws = g.alloc((B * sw,), torch.int32, zero=False) if sw else None
+            flags, ignore, rows, n = lovasz_launch_shape(kind, self.engine.loss_params, B, K, H * W)
+            sw = int(lib.salt_lovasz_split_words(n)) if n < 2 ** 31 else 0    # > 0: several workgroups per row (segments of the sort)
+            ws = g.alloc((rows * sw,), torch.int32, zero=False) if sw else None
+            fw = int(lib.salt_lovasz_flat_words(n))              # > 0: a long row (batch-flat, or an image above 131072 elements)
+            wf = g.alloc((rows * fw,), torch.int32, zero=False) if fw else None
             p.add('lovasz_hinge', logits=self.logits.data_ptr(), target=StepInput('target', self.target.data_ptr()), B=B, P=P, ws_keys=wk.data_ptr(),
                   ws_vals=wv.data_ptr(), loss_per_image=self.loss_per_image.data_ptr(), loss=StepInput('loss', self.loss.data_ptr()),
-                  dlogits=self.dlogits.data_ptr(), loss_scale=loss_scale, ws_split=ws.data_ptr() if ws is not None else None)
+                  dlogits=self.dlogits.data_ptr(), loss_scale=loss_scale, ws_split=ws.data_ptr() if ws is not None else None,
+                  flags=flags, ignore=ignore, ws_flat=wf.data_ptr() if wf is not None else None)
         elif kind == 'bce_dice':
             S = _abi.STRUCTS['salt_bce_dice_args']()
             _abi.fill(S, B=B, C=K, HW=H * W)
@@ -126,12 +134,17 @@ class CompiledNet:
             wk = g.alloc((2, B * K, HW), torch.int32, zero=False)
             wv = g.alloc((2, B * K, HW), torch.int32, zero=False)
             rows = g.alloc((B * K,), torch.float32)
-            sw = int(lib.salt_lovasz_split_words(HW))
-            ws = g.alloc((B * K * sw,), torch.int32, zero=False) if sw else None
+            flags, ignore, nrows, n = lovasz_launch_shape(kind, self.engine.loss_params, B, K, HW)
+            sw = int(lib.salt_lovasz_split_words(n)) if n < 2 ** 31 else 0
+            ws = g.alloc((nrows * sw,), torch.int32, zero=False) if sw else None
+            fw = int(lib.salt_lovasz_flat_words(n))
+            wf = g.alloc((nrows * fw,), torch.int32, zero=False) if fw else None
+            wp = g.alloc((B * K,), torch.int32, zero=False) if flags & _abi.CONSTS['SALT_LOVASZ_ONLY_PRESENT'] else None
             p.add('softmax', x=self.logits.data_ptr(), y=probas.data_ptr(), B=B, C=K, HW=HW)
             p.add('lovasz_softmax', probas=probas.data_ptr(), target=StepInput('target', self.target.data_ptr()), B=B, C=K, HW=HW, ws_keys=wk.data_ptr(),
                   ws_vals=wv.data_ptr(), loss_per_row=rows.data_ptr(), loss=StepInput('loss', self.loss.data_ptr()), dprobas=self.dlogits.data_ptr(),
-                  loss_scale=loss_scale, ws_split=ws.data_ptr() if ws is not None else None)
+                  loss_scale=loss_scale, ws_split=ws.data_ptr() if ws is not None else None, flags=flags, ignore=ignore,
+                  ws_flat=wf.data_ptr() if wf is not None else None, ws_present=wp.data_ptr() if wp is not None else None)
             p.add('softmax_bwd', p=probas.data_ptr(), dp=self.dlogits.data_ptr(), dz=self.dlogits.data_ptr(), B=B, C=K, HW=HW)
         elif kind == 'dice_ce':
             dw, cw, smooth = key[2:]
@@ -358,7 +371,7 @@ class Engine:
         self.side_stream = torch.cuda.Stream(device=device)     # weight-gradient kernels overlap the data-gradient chain
         self._graph_stream = None       # capture / replay stream of the step graphs: step_graph creates it, run_step_graph reads
         self.eager_done = set()          # (shape, loss kind) whose first training step already ran eagerly (models.SegmentationModel._fused_step)
-        self.loss_params = None          # weights of the 'dice_ce' loss programs (model_params['loss_params']): SegmentationModel._fused_step writes, CompiledNet.loss_key reads
+        self.loss_params = None          # weights of the 'dice_ce' / options of the Lovasz loss programs (model_params['loss_params']): SegmentationModel._fused_step writes, CompiledNet.loss_key reads
 
     # ------------------------------------------------------------------ flat parameter storage
     def _flatten(self):
